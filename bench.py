@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: mel-frames/s of the full Kokoro train step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,11 @@ A step = one pass of the hot path over one synthetic padded batch already reside
 full backward, (N>1: gradient SUM all-reduce over RCCL), pre-clip + global clip, fused AdamW + EMA, weight-norm
 projection.  Workload at every N: BASELINE.json configs[1]'s shape per GPU (8 x 512 mel frames, 64 phonemes,
 default 49.4 M-parameter model, bf16 MFMA arithmetic with fp32 accumulate/master weights) — weak scaling.
-Rank 0 prints ONE JSON line (contract in the task description) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly K steps (one region) and prints the line;
+--dump-outputs DIR also writes what one timed step computes from the seeded initial state (a twin engine built like the
+timed one replays the step's graphs once from that state; dump_outputs).  --full adds everything else: the
+timed region repeated 5 times (median reported), the event-timed `roofline` leg, `stacks`, `extra_shapes` (8x1024x128
+and dyn16384) and the `torch_rocm_baseline` / `cpu_baseline` objects.
 """
 from __future__ import annotations
 
@@ -497,13 +501,60 @@ def extra_shapes(eng, kk, math, steps_1024=30, passes=3, n_batches=24):
     return out
 
 
+DUMP_SAMPLE = 1 << 21          # elements per sampled array: 8 MB of float32, 4 arrays stay far below 64 MB
+
+
+def dump_sample(flat: torch.Tensor, n: int = DUMP_SAMPLE, seed: int = 0) -> torch.Tensor:
+    """`flat` itself when it has at most n elements, else n positions of it drawn with a fixed seed (sorted; the positions depend on
+    the length alone, so equally long arrays are sampled at the same places)."""
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randint(flat.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def device_state(eng):
+    """Every device tensor the engine and its arena hold right now — parameters, bf16 shadow, gradients, Adam moments, EMA, optimizer
+    state (step counters), RNG seed, accumulators — with a copy of its contents, for restore_device_state()."""
+    return [(o, n, t, t.clone()) for o in (eng, eng.arena) for n, t in vars(o).items() if isinstance(t, torch.Tensor) and t.is_cuda]
+
+
+def restore_device_state(state) -> None:
+    """Write the copies back IN PLACE (graphs captured since keep pointing at the same storage)."""
+    for o, n, t, c in state:
+        if getattr(o, n) is not t:
+            raise RuntimeError(f"engine tensor {n} was replaced since device_state(): cannot restore it in place")
+        t.copy_(c)
+
+
+def dump_outputs(eng, out_dir: str) -> None:
+    """What the timed path hands its caller after `eng`'s last step, as out_dir/<name>.npy (float32): `losses`, the 6 losses the step
+    returns, and the model it trained — `params`, `grads` (that step's gradients) and `ema`, each the concatenation of the 311
+    tensors of the state dict in state-dict order (`grads`: 0 for its 3 buffers, so that element i of every array belongs to the
+    same weight), sampled by dump_sample at the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = lambda ts: torch.cat([t.reshape(-1) for t in ts]).float()
+    sd, g = eng.state_dict(), eng.grads()
+    arrays = {"losses": eng.losses, "params": dump_sample(flat(sd.values())),
+              "grads": dump_sample(flat(g[n] if n in g else torch.zeros_like(t) for n, t in sd.items()))}
+    if eng.arena.ema is not None:
+        arrays["ema"] = dump_sample(flat(eng.state_dict(ema=True).values()))
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region of --steps steps is repeated this many times; the line "
-                    "reports the MEDIAN region (ms_per_step, value) and every region's ms_per_step")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: 5 timed regions by default, the "
+                    "roofline leg, stacks, extra shapes and the torch / CPU baselines (each can still be dropped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed step computes "
+                    "from the seeded initial state as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region of --steps steps is repeated this many times (default "
+                    "1, with --full 5); the line reports the MEDIAN region (ms_per_step, value) and every region's ms_per_step")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--phonemes", type=int, default=64)
@@ -523,9 +574,11 @@ def main():
                     "the environment (python -m kokoro_ruslan_amd.build --tuning), or the name of a --variant build")
     ap.add_argument("--set", action="append", default=[], metavar="ATTR=VALUE", help="tools: set an engine attribute (a fusion switch such "
                     "as attn_bwd_pair=0) for an A/B run; the line records it under config.engine_overrides")
-    ap.add_argument("--kernel-table", default="")
+    ap.add_argument("--kernel-table", default="", help="with --full: write the roofline leg's per-kernel table to this JSON file")
     ap.add_argument("--gemm16", default="", help="tuning sweep hook: enable,thr128,thr12864,split_target for the bf16 GEMM core")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     from kokoro_ruslan_amd import dp, lib as kk
     from kokoro_ruslan_amd.engine import KokoroEngine
@@ -543,17 +596,21 @@ def main():
     set_device_cus(torch.cuda.get_device_properties(local).multi_processor_count)      # (what the library's tile policy reads: hipDeviceAttributeMultiprocessorCount)
     B, T, P = args.batch, args.frames, args.phonemes
     hp = StepHyper(gradient_accumulation_steps=1)
-    eng = KokoroEngine(ModelDims(), hp, math_mode=args.math, total_steps=20000, seed=0,
-                       storage=args.storage)                           # same seed ⇒ identical replicas
-    eng.train_dropout = not args.no_dropout          # reference-faithful: dropout, stochastic depth, SpecAugment on
-    for kv in args.set:
-        name, val = kv.split("=", 1)
-        if not hasattr(eng, name):
-            raise SystemExit(f"--set {kv}: KokoroEngine has no attribute {name}")
-        setattr(eng, name, type(getattr(eng, name))(int(val)) if isinstance(getattr(eng, name), (bool, int)) else float(val))
     force = os.environ.get("KK_DP_FORCE") == "1"       # run the data-parallel code path (1-rank group) on a single GPU
     sync = dp.GradSync(world, force=force)
-    eng.dp_loss_scale = sync.loss_scale
+
+    def new_engine():
+        e = KokoroEngine(ModelDims(), hp, math_mode=args.math, total_steps=20000, seed=0,
+                         storage=args.storage)                         # same seed ⇒ identical replicas
+        e.train_dropout = not args.no_dropout        # reference-faithful: dropout, stochastic depth, SpecAugment on
+        for kv in args.set:
+            name, val = kv.split("=", 1)
+            if not hasattr(e, name):
+                raise SystemExit(f"--set {kv}: KokoroEngine has no attribute {name}")
+            setattr(e, name, type(getattr(e, name))(int(val)) if isinstance(getattr(e, name), (bool, int)) else float(val))
+        e.dp_loss_scale = sync.loss_scale
+        return e
+    eng = new_engine()
     batch = {k: v.cuda() for k, v in synthetic_batch(B, T, P, seed=1234 + rank).items()}
     use_sync = world > 1 or force
     # default data-parallel exchange: bucket by bucket INSIDE the step graph over the C ABI's kk_comm_* (RCCL);
@@ -644,13 +701,36 @@ def main():
     stats = eng.opt_stats()
     if eng.encoder_stack_error():
         raise RuntimeError("a group barrier of the fused encoder launch timed out during the timed region: the number is void")
+    if rank == 0 and args.dump_outputs:
+        # The timed engine's state after W + K steps carries the rounding of every step's float atomics (order-dependent), which
+        # training amplifies far beyond rounding over hundreds of steps.  A twin built exactly like it runs ONE timed step from the
+        # seeded initial state instead: identical inputs every run, outputs equal up to that step's rounding.  A shape's first
+        # train_step_graphed call runs eagerly (it sizes the workspaces; nothing is captured), so the twin takes that call, is put
+        # back to the seeded state in place, and its second call captures the step's graphs and REPLAYS them: the launch sequence
+        # the timed steps replay.  Loss scale 1: the twin runs alone (no gradient exchange), like a 1-GPU run.
+        twin = new_engine()
+        twin.dp_loss_scale = 1.0
+        b0 = dyn["batches"][0] if dyn is not None else batch
+        if args.no_graph:
+            twin.train_step(b0)
+        else:
+            seeded = device_state(twin)
+            twin.train_step_graphed(b0)
+            torch.cuda.synchronize()
+            restore_device_state(seeded)
+            del seeded
+            twin.train_step_graphed(b0)
+        if twin.encoder_stack_error():
+            raise RuntimeError("a group barrier of the fused encoder launch timed out during the dumped step: the outputs are void")
+        dump_outputs(twin, args.dump_outputs)
+        del twin
 
     roof, table = None, {}
     # From here on rank 0 works ALONE (roofline leg, extra shapes, baselines) while the other ranks wait at the barrier below: the
     # in-step exchange must be detached first — an eager forward_backward with eng.dp_comm set would issue RCCL collectives that no
     # other rank matches (a hang, not an error).  The timed numbers are already taken.
     eng.dp_comm = None
-    if rank == 0 and not args.no_roofline and dyn is None:
+    if rank == 0 and args.full and not args.no_roofline and dyn is None:
         # Roofline leg: the same step, eager, every launch bracketed by events on the launch stream.
         roof, table, shapes = roofline_leg(eng, kk, [batch], args.math, (B, T, P))
         if args.kernel_table:
@@ -660,9 +740,9 @@ def main():
                 srows = sorted(shapes.items(), key=lambda kv: -kv[1]["ms"])
                 json.dump({"total_ms_2_steps": tot, "kernels": {k: v for k, v in rows}, "shapes": {k: v for k, v in srows}}, f, indent=1)
     extra = stacks = None
-    if rank == 0 and not args.no_roofline and not args.no_graph and dyn is None:
+    if rank == 0 and args.full and not args.no_roofline and not args.no_graph and dyn is None:
         stacks = stack_fraction(eng, batch)
-    if rank == 0 and world == 1 and not args.no_extra_shapes and not args.no_graph and args.math == "bf16" and dyn is None:
+    if rank == 0 and args.full and world == 1 and not args.no_extra_shapes and not args.no_graph and args.math == "bf16" and dyn is None:
         extra = extra_shapes(eng, kk, args.math)
         if eng.encoder_stack_error():
             raise RuntimeError("a group barrier of the fused encoder launch timed out during the extra shapes")
@@ -710,7 +790,7 @@ def main():
            "model_mfma_frac": round(frames / dt * fl / (B * T) / 1e12 / world / (PEAK_BF16_TFLOPS if args.math == "bf16" else PEAK_F32_TFLOPS), 4)}
     if extra is not None:
         out["extra_shapes"] = extra
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["torch_rocm_baseline"] = torch_rocm_baseline(B, T, P)
         out["cpu_baseline"] = cpu_baseline(B, T, P, full=args.cpu_baseline_full)
     print(json.dumps(out), flush=True)

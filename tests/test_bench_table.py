@@ -1,7 +1,9 @@
 """CPU suite: bench.py's kernel table (the roofline leg's bookkeeping) — names and algorithmic FLOPs / bytes of the launches
-the engine makes at the bench shape, from synthetic profile records (no GPU)."""
+the engine makes at the bench shape, from synthetic profile records (no GPU); --dump-outputs; and (GPU) a plain run end to end."""
 import importlib.util
 import os
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -92,3 +94,97 @@ def test_bench_detaches_the_in_step_exchange_before_rank0_only_legs():
     first_alone = min(src.index("roofline_leg(eng, kk, [batch]", timed), src.index("stack_fraction(eng, batch)", timed),
                       src.index("extra_shapes(eng, kk, args.math)", timed))
     assert timed < detach < first_alone
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: an array longer than DUMP_SAMPLE is cut to DUMP_SAMPLE elements at positions fixed by its length alone (two
+    runs, and the parameters and their EMA, are sampled at the same places); a shorter one is written whole."""
+    import torch
+    b = _bench()
+    n = 3 * b.DUMP_SAMPLE + 7
+    x = torch.arange(n, dtype=torch.float64)
+    s1, s2 = b.dump_sample(x), b.dump_sample(x.clone())
+    assert s1.numel() == b.DUMP_SAMPLE and torch.equal(s1, s2)
+    assert bool((s1[1:] >= s1[:-1]).all()) and float(s1.min()) >= 0 and float(s1.max()) < n
+    small = torch.randn(1000)
+    assert torch.equal(b.dump_sample(small), small)
+    assert (4 * b.DUMP_SAMPLE + 6) * 4 <= 64 << 20, "losses + params + grads + ema in float32 stay within 64 MB"
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """dump_outputs writes losses / params / grads / ema as float32 .npy, the named tensors concatenated in state-dict order; grads
+    carries 0 for a buffer, so that element i of every array belongs to the same weight."""
+    from collections import OrderedDict
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(0)
+    P = OrderedDict((f"w{i}", torch.randn(5, 7 + i, generator=g)) for i in range(4))
+
+    class Arena:
+        ema = torch.zeros(1)
+
+    class Eng:
+        arena = Arena()
+        losses = torch.arange(6, dtype=torch.float32)
+        state_dict = lambda self, ema=False: OrderedDict([(n, t + 1 if ema else t) for n, t in P.items()] + [("buf", torch.ones(3))])
+        grads = lambda self: OrderedDict((n, 2 * t) for n, t in P.items())
+
+    b.dump_outputs(Eng(), str(tmp_path / "out"))
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("losses", "params", "grads", "ema")}
+    flat = torch.cat([t.reshape(-1) for t in P.values()]).numpy()
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["losses"], np.arange(6, dtype=np.float32))
+    np.testing.assert_array_equal(got["params"], np.concatenate([flat, np.ones(3, np.float32)]))
+    np.testing.assert_array_equal(got["grads"], np.concatenate([2 * flat, np.zeros(3, np.float32)]))     # a buffer has no gradient: 0
+    np.testing.assert_array_equal(got["ema"], np.concatenate([flat + 1, np.ones(3, np.float32)]))
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_exactly_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --steps K --warmup W --dump-outputs DIR` times ONE region of exactly K steps, prints the headline keys and
+    none of what --full adds, and leaves finite float32 outputs (at most 64 MB) in DIR.  The dump is one step from the seeded initial
+    weights: the parameters moved away from them, and an eager step (--no-graph) from the same seed computes the same outputs.  Two
+    runs with the same arguments dump the same outputs up to rounding: the step's float atomics may round in another order."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from kokoro_ruslan_amd import spec
+    b = _bench()
+    dumps = []
+    for run, extra in enumerate(([], [], ["--no-graph"])):
+        out = tmp_path / f"dump{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(out)] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == 3 and line["timed_regions"]["repeats"] == 1 and line["optimizer_steps"] == 5.0
+        assert line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "bf16"
+        assert line["roofline"] is None and line["stacks"] is None
+        assert not {"extra_shapes", "cpu_baseline", "torch_rocm_baseline"} & set(line)
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["ema.npy", "grads.npy", "losses.npy", "params.npy"], files
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+        d = {p.stem: np.load(p) for p in out.iterdir()}
+        for n, a in d.items():
+            assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), n
+        dumps.append(d)
+    # the seeded initial state, sampled like the dump: the step moved the weights it has gradients for, and only those
+    dims = spec.ModelDims()
+    P0, buf = spec.init_params(dims, 0), spec.make_buffers(dims)
+    init = b.dump_sample(torch.cat([(P0[n] if n in P0 else buf[n]).reshape(-1).float() for n in spec.state_dict_order(dims)])).numpy()
+    d = dumps[0]
+    assert d["params"].shape == d["grads"].shape == d["ema"].shape == init.shape
+    moved, has_grad = d["params"] != init, d["grads"] != 0
+    assert has_grad.mean() > 0.5 and moved.mean() > 0.5
+    for other in dumps[1:]:
+        for n, a in d.items():
+            c = other[n]
+            tol = (1e-5 if n == "grads" else 1e-6) * float(np.abs(c).max())       # fp32 rounding of the backward's atomics, with margin
+            assert a.shape == c.shape and float(np.abs(a.astype(np.float64) - c).max()) <= tol, n
