@@ -355,6 +355,26 @@ int kk_decode_cache_append(const void *nrm, void *q, void *kcache, void *vcache,
 int kk_decode_epilogue(const float *frame_out, const float *stop, float *mel_all, float *stop_all, int *t_dev, int B, int L1, int M,
                        void *stream);
 
+/* ---- batched synthesis (KokoroEngine.generate_batch; kk_synth.hip): row b of a padded batch gets what the B = 1 path gives
+ * utterance b alone.  lens [B] (int32) is each row's sequence length; it takes the place of L at B = 1.
+ * im2col3_rows: kk_im2col3_fwd, except that a tap at a position >= lens[b] reads 0 (chunk boundaries unchanged).
+ * groupnorm_relu_rows: kk_groupnorm_relu_fwd with the statistics of (row b, chunk k) over frames [512k, min(512(k+1), lens[b]));
+ *   zeros at positions >= lens[b] and in a chunk with < 2 valid frames (variance_predictor.py:94-99).
+ * varpred_row_mask: mask_out[b,l] = mask_in[b,l] (mask_in may be NULL) | l >= lens[b] | the chunk of l has < 2 valid frames of row b
+ *   (the kk_rowdot_fwd mask of a predictor's Linear(C->1), with chunk = 0 there).
+ * decode_epilogue_rows: kk_decode_epilogue for the rows with done[b] == 0, then the stop rule of model/generator.py:67-88 applied to
+ *   row b alone: from t >= min_b[b], stop when sigmoid(stop[b]) > (t < expected_b[b] ? thr : min(thr, post_thr)), else, once 30
+ *   frames exist, when the mean of the row's last 30 frames < -9.5; also when t + 1 == max_b[b].  A row that stops gets
+ *   frames[b] = t + 1, done[b] = 1 and *live -= 1, and is never written again.  *t_dev = t + 1. */
+int kk_im2col3_rows_fwd(const float *x, float *col, const int *lens, int B, int L, int C, int chunk, int col_bf16, void *stream);
+int kk_groupnorm_relu_rows_fwd(const float *x, const float *gamma, const float *beta, float *y, float *stats, double *scratch,
+                               const int *lens, int B, int L, int C, int chunk, const uint32_t *seed, uint32_t site, float p,
+                               void *stream);
+int kk_varpred_row_mask(const uint8_t *mask_in, const int *lens, uint8_t *mask_out, int B, int L, int chunk, void *stream);
+int kk_decode_epilogue_rows(const float *frame_out, const float *stop, float *mel_all, float *stop_all, int *t_dev, uint8_t *done,
+                            int *frames, int *live, const int *min_b, const int *expected_b, const int *max_b, int B, int L1, int M,
+                            float stop_threshold, float post_expected_stop_threshold, void *stream);
+
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}
  * (transformers.py:16-40,482-487,569-581; the FFN has two dropouts in series, :111).  *seed is read on the device. */

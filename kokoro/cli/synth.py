@@ -1,0 +1,100 @@
+"""`kokoro-synth`: mel spectrograms of many utterances from a kokoro-train checkpoint, decoded in batches on the engine.
+
+    kokoro-synth --checkpoint CKPT (--features CACHE_DIR [--indices ...] | --ids FILE.jsonl) --output DIR
+                 [--batch-size 32] [--weights auto|ema|model] [--stop-threshold X] [--max-len N] [--min-len-ratio R]
+                 [--min-len-floor N] [--trim] [--math bf16|f32]
+
+Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
+--features reads phoneme_indices / stress_indices from a precomputed feature cache (kokoro.data.cached); --ids reads JSON lines
+{"name", "phoneme_indices", "stress_indices"?}.  --trim applies the reference's clamp + trailing-silence trim (:588-619)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import List, Optional, Tuple
+
+import torch
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Batched mel synthesis from a Kokoro checkpoint (MI355X engine)")
+    p.add_argument("--checkpoint", required=True)
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--features", metavar="CACHE_DIR", help="precomputed feature cache (*.pt)")
+    src.add_argument("--ids", metavar="FILE.jsonl", help='JSON lines {"name", "phoneme_indices", "stress_indices"?}')
+    p.add_argument("--indices", type=int, nargs="*", default=None, help="utterances of the feature cache (its length-sorted order)")
+    p.add_argument("--output", required=True)
+    p.add_argument("--batch-size", type=int, default=32)
+    p.add_argument("--weights", choices=("auto", "ema", "model"), default="auto")
+    p.add_argument("--stop-threshold", type=float, default=None)
+    p.add_argument("--max-len", type=int, default=None)
+    p.add_argument("--min-len-ratio", type=float, default=None)
+    p.add_argument("--min-len-floor", type=int, default=None)
+    p.add_argument("--trim", action="store_true")
+    p.add_argument("--math", choices=("bf16", "f32"), default="bf16")
+    return p
+
+
+def read_ids(path: str) -> Tuple[List[str], List[torch.Tensor], Optional[List[torch.Tensor]]]:
+    """(names, phoneme id vectors, stress vectors or None) of a JSON-lines file; stress is given on every line or on none."""
+    names, ids, stress = [], [], []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            rec = json.loads(line)
+            if "name" not in rec or "phoneme_indices" not in rec:
+                raise ValueError(f"{path}:{n}: needs 'name' and 'phoneme_indices'")
+            names.append(str(rec["name"]))
+            ids.append(torch.tensor(rec["phoneme_indices"], dtype=torch.int64))
+            st = rec.get("stress_indices")
+            stress.append(torch.tensor(st, dtype=torch.int64) if st is not None else None)
+            if st is not None and len(st) != len(rec["phoneme_indices"]):
+                raise ValueError(f"{path}:{n}: stress_indices and phoneme_indices differ in length")
+    if len(set(names)) != len(names):
+        raise ValueError(f"{path}: duplicate names")
+    if all(s is None for s in stress):
+        return names, ids, None
+    if any(s is None for s in stress):
+        raise ValueError(f"{path}: stress_indices must be given on every line or on none")
+    return names, ids, stress
+
+
+def read_features(cache_dir: str, indices=None) -> Tuple[List[str], List[torch.Tensor], List[torch.Tensor]]:
+    from kokoro.data.cached import CachedFeatureDataset
+    ds = CachedFeatureDataset(cache_dir, indices=indices, memory_cache=False)
+    names, ids, stress = [], [], []
+    for i in range(len(ds)):
+        it = ds[i]
+        names.append(os.path.splitext(ds.samples[i]["file"].name)[0])
+        ids.append(it["phoneme_indices"].to(torch.int64))
+        stress.append(it["stress_indices"].to(torch.int64))
+    return names, ids, stress
+
+
+def main(argv=None) -> int:
+    import numpy as np
+    from kokoro.inference.synth import load_for_inference, synthesize, trim_trailing_silence
+    args = build_parser().parse_args(argv)
+    if args.ids:
+        names, ids, stress = read_ids(args.ids)
+    else:
+        names, ids, stress = read_features(args.features, args.indices)
+    engine, controls, used = load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,
+                                                stop_threshold=args.stop_threshold, min_len_ratio=args.min_len_ratio,
+                                                min_len_floor=args.min_len_floor)
+    mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **controls.kwargs())
+    os.makedirs(args.output, exist_ok=True)
+    for name, mel in zip(names, mels):
+        mel = mel.float().cpu()
+        if args.trim:
+            mel = trim_trailing_silence(mel)
+        np.save(os.path.join(args.output, f"{name}.npy"), mel.t().contiguous().numpy().astype(np.float32))
+    print(f"kokoro-synth: {len(mels)} mels ({used} weights, {controls}) -> {args.output}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

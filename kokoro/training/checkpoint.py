@@ -162,20 +162,25 @@ def find_latest_checkpoint(output_dir: str) -> Optional[str]:
     return str(files[-1])
 
 
-def load_checkpoint(engine, path: str) -> Dict[str, Any]:
-    """Strict resume: validates the architecture metadata like the reference (checkpoint_manager.py:309-358)."""
-    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+def check_metadata(ckpt: Dict[str, Any], d: spec.ModelDims) -> Dict[str, Any]:
+    """The architecture metadata of a checkpoint, validated against the dims `d` like the reference (checkpoint_manager.py:309-358)."""
     arch = (ckpt.get("model_metadata") or {}).get("architecture") or {}
     required = ["mel_dim", "hidden_dim", "n_encoder_layers", "n_decoder_layers", "max_decoder_seq_len", "use_variance_predictor"]
     missing = [k for k in required if k not in arch]
     if missing:
         raise RuntimeError(f"Checkpoint metadata is incomplete. Missing fields: {missing}.")
-    d = engine.dims
     cur = {"mel_dim": d.mel, "hidden_dim": d.hidden, "n_encoder_layers": d.enc_layers, "n_decoder_layers": d.dec_layers,
            "max_decoder_seq_len": d.max_len, "use_variance_predictor": True, "vocab_size": d.vocab}
     bad = {k: (arch[k], v) for k, v in cur.items() if k in arch and arch[k] != v}
     if bad:
         raise RuntimeError(f"Checkpoint architecture mismatch (checkpoint, current): {bad}")
+    return arch
+
+
+def load_checkpoint(engine, path: str) -> Dict[str, Any]:
+    """Strict resume: validates the architecture metadata like the reference (checkpoint_manager.py:309-358)."""
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    check_metadata(ckpt, engine.dims)
     engine.load_state_dict(ckpt["model_state_dict"], strict=True)
     if "ema_model_state_dict" in ckpt and engine.arena.ema is not None:
         for n, t in ckpt["ema_model_state_dict"].items():

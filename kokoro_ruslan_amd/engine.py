@@ -24,7 +24,7 @@ import math
 import os
 import threading
 from collections import OrderedDict
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -777,9 +777,10 @@ class KokoroEngine:
 
     # ------------------------------------------------------------------ attention sub-layer
     def _attn_fwd(self, key, prefix, xq, xkv, B, Sq, Sk, rope, causal, key_mask, x_res, x_out, site=0, p=0.0, dpr=0.0, next_ln=None,
-                  layer=0):
+                  layer=0, kv_ns=""):
         """x_out = x_res + w_o(attention(...)) + b_o.  xq [B*Sq,H] (post-LN), xkv [B*Sk,H] (None = self-attention).
-        Returns LayerNorm_next_ln(x_out) when the fused dropout tail computed it, else None."""
+        Returns LayerNorm_next_ln(x_out) when the fused dropout tail computed it, else None.  kv_ns: key prefix of the cross-attention
+        K|V buffers (_cross_kv)."""
         P, H, h = self.arena.P, self.dims.hidden, self.dims.heads
         Nq, Nk = B * Sq, B * Sk
         dt = xq.dtype                                   # storage of every activation of the sub-layer
@@ -792,7 +793,7 @@ class KokoroEngine:
             q_raw, k_raw, v_raw, q_n, k_n, v_n = raw, raw[:, H:], raw[:, 2 * H:], nrm, nrm[:, H:], nrm[:, 2 * H:]
         else:
             q_raw, q_n = self._buf(key + ".q_raw", Nq, H, dtype=dt), self._buf(key + ".q_n", Nq, H, dtype=dt)
-            kv_raw, kv_n = self._cross_kv(layer, Nk, dt)                              # filled by _cross_kv_fwd_all
+            kv_raw, kv_n = self._cross_kv(layer, Nk, dt, ns=kv_ns)                    # filled by _cross_kv_fwd_all
             self._proj_headnorm(xq, self._W(prefix + ".w_q.weight"), q_raw, q_n, Sq, (gq,), 0, None, None)
             k_raw, v_raw, k_n, v_n = kv_raw, kv_raw[:, H:], kv_n, kv_n[:, H:]
         ctx, lse = self._buf(key + ".ctx", Nq, H, dtype=dt), self._buf(key + ".lse", B, h, Sq)
@@ -858,12 +859,12 @@ class KokoroEngine:
             kk.call("kk_attn_keep_gen", table, len(part), self.rng, seed_offset, max_wgs)
         return bool(ents)
 
-    def _cross_kv(self, layer, Nk, dt, which=""):
+    def _cross_kv(self, layer, Nk, dt, which="", ns=""):
         """(raw, normed) K|V of cross-attention layer `layer`: column slices [.., 2H] of the all-layer buffers (row stride
-        layers*2H); which = "d" for their gradients."""
+        layers*2H); which = "d" for their gradients; ns = a key prefix of the buffers (generate_batch: its own)."""
         H, L = self.dims.hidden, self.dims.dec_layers
-        raw = self._buf(f"dec.ca.{which}kv_raw_all", Nk, 2 * H * L, dtype=dt)
-        nrm = self._buf(f"dec.ca.{which}kv_n_all", Nk, 2 * H * L, dtype=dt)
+        raw = self._buf(f"{ns}dec.ca.{which}kv_raw_all", Nk, 2 * H * L, dtype=dt)
+        nrm = self._buf(f"{ns}dec.ca.{which}kv_n_all", Nk, 2 * H * L, dtype=dt)
         return raw[:, 2 * H * layer:2 * H * (layer + 1)], nrm[:, 2 * H * layer:2 * H * (layer + 1)]
 
     def _proj_headnorm(self, x, W, raw, nrm, S, gains, rope_mask, cos, sin):
@@ -883,13 +884,13 @@ class KokoroEngine:
             kk.call("kk_headnorm_rope_fwd", raw[:, p0 * H:], raw.stride(0), nrm[:, p0 * H:], nrm.stride(0), rows, h, S, n,
                     g[0], g[1], g[2], (rope_mask >> p0) & 7, cos, sin, _b16(raw))
 
-    def _cross_kv_fwd_all(self, xkv, Nk, Sk, dt, first=0, last=None):
+    def _cross_kv_fwd_all(self, xkv, Nk, Sk, dt, first=0, last=None, ns=""):
         """K/V projections of ALL decoder cross-attention layers in one GEMM (they depend on the memory alone and their
         weights are contiguous in the arena), then the per-head RMSNorm of each layer's slice (no RoPE:
         transformers.py:268-277 applies it to self-attention only)."""
         P, H, h, L = self.arena.P, self.dims.hidden, self.dims.heads, self.dims.dec_layers
-        raw_all = self._buf("dec.ca.kv_raw_all", Nk, 2 * H * L, dtype=dt)
-        nrm_all = self._buf("dec.ca.kv_n_all", Nk, 2 * H * L, dtype=dt)
+        raw_all = self._buf(f"{ns}dec.ca.kv_raw_all", Nk, 2 * H * L, dtype=dt)
+        nrm_all = self._buf(f"{ns}dec.ca.kv_n_all", Nk, 2 * H * L, dtype=dt)
         last = L if last is None else last                 # layers [first, last): a column slice of the all-layer buffers
         gains = [P[f"decoder.layers.{l}.cross_attn.{kv}_norm.weight"] for l in range(first, last) for kv in ("k", "v")]
         c0, c1 = 2 * H * first, 2 * H * last
@@ -1610,6 +1611,54 @@ class KokoroEngine:
         return out
 
     # ------------------------------------------------------------------ inference
+    def _decode_step(self, ns, B, T, max_expected, memory, fm2):
+        """The launches of one decoder step at Sq = 1 up to the stop logits (generate / generate_batch add their own epilogue).  The
+        step's buffers are the caller's workspace entries under the key prefix `ns` (see generate), fetched by the same keys and shapes;
+        the cross-attention K|V are those of _cross_kv_fwd_all(..., ns=`ns` + "." or "" for "gen")."""
+        d, P, H, M, h = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dims.heads
+        ddt = self.dec_dt
+        BH, L1 = B * H, max_expected + 1
+        kv_ns = "" if ns == "gen" else ns + "."
+        pe = P["positional_encoding.pe"].view(d.max_len, H)
+        cos, sin = self._rope_tables(d.max_len)
+        Kc = [self._buf(f"{ns}.dec{i}.kcache", max_expected, BH, dtype=ddt) for i in range(d.dec_layers)]
+        Vc = [self._buf(f"{ns}.dec{i}.vcache", max_expected, BH, dtype=ddt) for i in range(d.dec_layers)]
+        mel_out, y = self._buf(f"{ns}.mel", B, L1, M), self._buf(f"{ns}.y", B, H)
+        t_dev, kmask = self._buf(f"{ns}.t", 1, dtype=torch.int32), self._buf(f"{ns}.kmask", 1, max_expected, dtype=torch.uint8)
+        frame_in, frame_out, stop_now = self._buf(f"{ns}.frame_in", B, M), self._buf(f"{ns}.frame_out", B, M), self._buf(f"{ns}.stop_now", B)
+        pe_row, cos_row, sin_row = self._buf(f"{ns}.pe_row", 1, H), self._buf(f"{ns}.cos_row", 1, 64), self._buf(f"{ns}.sin_row", 1, 64)
+        kk.call("kk_decode_prologue", mel_out, frame_in, pe, pe_row, cos, sin, cos_row, sin_row, kmask, t_dev, B, L1, M, H)
+        # mel_projection_in + positional encoding at offset t (model.py:541-545)
+        self._linear(frame_in, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], y, res=pe_row, res_mod=1)
+        n1 = self._ln_fwd(f"{ns}.dec0.ln1", y, "decoder.layers.0.norm1", ddt)
+        yl = y
+        for i in range(d.dec_layers):
+            pf, key = f"decoder.layers.{i}", f"{ns}.dec{i}"
+            gq, gk, gv = P[pf + ".self_attn.q_norm.weight"], P[pf + ".self_attn.k_norm.weight"], P[pf + ".self_attn.v_norm.weight"]
+            raw, nrm = self._buf(key + ".qkv_raw", B, 3 * H, dtype=ddt), self._buf(key + ".qkv_n", B, 3 * H, dtype=ddt)
+            self._proj_headnorm(n1, self._Wf(pf + ".self_attn.w_q.weight", 3), raw, nrm, 1, (gq, gk, gv), 2, cos_row, sin_row)
+            qb = self._buf(key + ".q", 1, BH, dtype=ddt)
+            kk.call("kk_decode_cache_append", nrm, qb, Kc[i], Vc[i], t_dev, B, H, _b16(nrm))
+            ctx, lse = self._buf(key + ".ctx", 1, BH, dtype=ddt), self._buf(key + ".lse", 1, B * h, 1)
+            kk.call("kk_attn_fwd", qb, Kc[i], Vc[i], ctx, lse, 1, B * h, 1, max_expected, BH, BH, BH, BH, kmask, 0, 0.125, self.rng,
+                    0, 0.0, self.math, _b16(qb))
+            proj = self._buf(f"tmp.{ns}_proj", B, H)
+            self._linear(ctx.view(B, H), self._W(pf + ".self_attn.w_o.weight"), P[pf + ".self_attn.w_o.bias"], proj)
+            ya = self._buf(key + ".xa", B, H)
+            n2 = self._sublayer_tail(proj, yl, ya, 1, 0, 0.0, 0.0, 0.0, None, None, (key + ".ln2", pf + ".norm2", ddt))
+            yc = self._buf(key + ".xc", B, H)
+            n3 = self._attn_fwd(key + ".ca", pf + ".cross_attn", n2, memory, B, 1, T, False, False, fm2, ya, yc,
+                                next_ln=(key + ".ln3", pf + ".norm3", ddt), layer=i, kv_ns=kv_ns)
+            yo = self._buf(key + ".xo", B, H)
+            nxt = ((f"{ns}.dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", ddt) if i + 1 < d.dec_layers
+                   else (f"{ns}.dec.norm", "decoder.norm", ddt))
+            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=nxt)
+            yl = yo
+        dec_out = n1
+        self._linear(dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out)
+        kk.call("kk_rowdot_fwd", dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now,
+                B, H, 1, 0, _b16(dec_out))
+
     @torch.no_grad()
     def generate(self, ids: torch.Tensor, stress: Optional[torch.Tensor] = None, max_len: int = 4000,
                  stop_threshold: float = 0.5, min_len_ratio: float = 0.7, min_len_floor: int = 12,
@@ -1715,37 +1764,7 @@ class KokoroEngine:
             pe_row, cos_row, sin_row = self._buf("gen.pe_row", 1, H), self._buf("gen.cos_row", 1, 64), self._buf("gen.sin_row", 1, 64)
 
             def decode_step():
-                kk.call("kk_decode_prologue", mel_out, frame_in, pe, pe_row, cos, sin, cos_row, sin_row, kmask, t_dev, B, L1, M, H)
-                # mel_projection_in + positional encoding at offset t (model.py:541-545)
-                self._linear(frame_in, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], y, res=pe_row, res_mod=1)
-                n1 = self._ln_fwd("gen.dec0.ln1", y, "decoder.layers.0.norm1", ddt)
-                yl = y
-                for i in range(d.dec_layers):
-                    pf, key = f"decoder.layers.{i}", f"gen.dec{i}"
-                    gq, gk, gv = P[pf + ".self_attn.q_norm.weight"], P[pf + ".self_attn.k_norm.weight"], P[pf + ".self_attn.v_norm.weight"]
-                    raw, nrm = self._buf(key + ".qkv_raw", B, 3 * H, dtype=ddt), self._buf(key + ".qkv_n", B, 3 * H, dtype=ddt)
-                    self._proj_headnorm(n1, self._Wf(pf + ".self_attn.w_q.weight", 3), raw, nrm, 1, (gq, gk, gv), 2, cos_row, sin_row)
-                    qb = self._buf(key + ".q", 1, BH, dtype=ddt)
-                    kk.call("kk_decode_cache_append", nrm, qb, Kc[i], Vc[i], t_dev, B, H, _b16(nrm))
-                    ctx, lse = self._buf(key + ".ctx", 1, BH, dtype=ddt), self._buf(key + ".lse", 1, B * h, 1)
-                    kk.call("kk_attn_fwd", qb, Kc[i], Vc[i], ctx, lse, 1, B * h, 1, max_expected, BH, BH, BH, BH, kmask, 0, 0.125, self.rng,
-                            0, 0.0, self.math, _b16(qb))
-                    proj = self._buf("tmp.gen_proj", B, H)
-                    self._linear(ctx.view(B, H), self._W(pf + ".self_attn.w_o.weight"), P[pf + ".self_attn.w_o.bias"], proj)
-                    ya = self._buf(key + ".xa", B, H)
-                    n2 = self._sublayer_tail(proj, yl, ya, 1, 0, 0.0, 0.0, 0.0, None, None, (key + ".ln2", pf + ".norm2", ddt))
-                    yc = self._buf(key + ".xc", B, H)
-                    n3 = self._attn_fwd(key + ".ca", pf + ".cross_attn", n2, memory, B, 1, T, False, False, fm2, ya, yc,
-                                        next_ln=(key + ".ln3", pf + ".norm3", ddt), layer=i)
-                    yo = self._buf(key + ".xo", B, H)
-                    nxt = ((f"gen.dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", ddt) if i + 1 < d.dec_layers
-                           else ("gen.dec.norm", "decoder.norm", ddt))
-                    n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=nxt)
-                    yl = yo
-                dec_out = n1
-                self._linear(dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out)
-                kk.call("kk_rowdot_fwd", dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now,
-                        B, H, 1, 0, _b16(dec_out))
+                self._decode_step("gen", B, T, max_expected, memory, fm2)
                 kk.call("kk_decode_epilogue", frame_out, stop_now, mel_out, stop_logit, t_dev, B, L1, M)
 
             frames = max_expected
@@ -1781,6 +1800,189 @@ class KokoroEngine:
                         frames = stop_at + 1
                         break
             return mel_out[:, 1:frames + 1].clamp(min=-11.5, max=2.0).clone()
+        finally:
+            self.train_dropout = saved_drop
+
+    # ------------------------------------------------------------------ batched inference: each row as if alone
+    def _varpred_rows_fwd(self, key, prefix, x, col1, B, L, lens, mask, out):
+        """_varpred_fwd (dropout off) with the row kernels of kk_synth.hip: row b is a sequence of lens[b] positions (int32), as the
+        B = 1 predictor sees it.  col1 = kk_im2col3_rows_fwd(x, lens); mask = kk_varpred_row_mask(...) (the rowdot's own chunk
+        guard is off: the mask carries the per-row one)."""
+        P, Fv = self.arena.P, self.dims.var_filter
+        rows, nch = B * L, -(-L // CHUNK)
+        scratch = self._buf("tmp.gn_scratch", 2 * B * nch, dtype=torch.float64)
+        inp_col, cin = col1, x.shape[1]
+        for li in range(2):
+            c, y = self._buf(f"{key}.c{li}", rows, Fv), self._buf(f"{key}.y{li}", rows, Fv)
+            stats = self._buf(f"{key}.st{li}", B * nch, 2)
+            self._linear(inp_col, self._Wconv(f"{prefix}.conv_layers.{li}.weight", Fv, 3 * cin), P[f"{prefix}.conv_layers.{li}.bias"], c)
+            kk.call("kk_groupnorm_relu_rows_fwd", c, P[f"{prefix}.norms.{li}.weight"], P[f"{prefix}.norms.{li}.bias"], y, stats,
+                    scratch, lens, B, L, Fv, CHUNK, self.rng, 0, 0.0)
+            if li == 0:
+                inp_col, cin = self._buf(f"{key}.col2", rows, 3 * Fv, dtype=col1.dtype), Fv
+                kk.call("kk_im2col3_rows_fwd", y, inp_col, lens, B, L, Fv, CHUNK, _b16(inp_col))
+        kk.call("kk_rowdot_fwd", y, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, out, rows, Fv, L, 0, 0)
+
+    @torch.no_grad()
+    def generate_batch(self, utterances: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]] = None, *, max_len: int = 4000,
+                       stop_threshold: float = 0.5, min_len_ratio: float = 0.7, min_len_floor: int = 12, max_len_ratio: float = 3.0,
+                       max_len_cap: int = 1600, post_expected_stop_threshold: float = 0.2, check_every: int = 16,
+                       decode_graph: bool = True, want_info: bool = False):
+        """Synthesise a batch of utterances of different lengths; row b of the result equals generate() on utterance b alone (the
+        reference's B = 1 forward_inference), not generate() on the padded batch, whose stop rule and predictors see the whole batch.
+
+        utterances: phoneme-id vectors [P_b]; stress: one vector per utterance, or None.  Returns [mel_b [frames_b, mel]] in input
+        order, clamped to [-11.5, 2]; with want_info also a dict of per-row "durations" [P_b], "T" (= T_b) and "bounds" (min_b,
+        expected_b, max_b).
+
+        Row lengths are those of the single-utterance call: L_b = P_b phonemes, T_b = max(sum(dur_b), 3) frames (frames in
+        [sum(dur_b), T_b) are zero inputs that count in the predictors' convolutions and GroupNorms, as at B = 1).  The duration,
+        pitch and energy predictors run with the row kernels (_varpred_rows_fwd); the encoder (key mask), length regulator, bucket
+        embeddings and cross-attention (frame mask) are row-independent already.  Each row has its own bounds (model.py:741-750)
+        and its own stop rule, applied on the device by kk_decode_epilogue_rows inside the replayed step; the host reads only the
+        count of live rows, every `check_every` frames."""
+        d, P, H, M = self.dims, self.arena.P, self.dims.hidden, self.dims.mel
+        B = len(utterances)
+        if B == 0:
+            return ([], {"durations": [], "T": [], "bounds": []}) if want_info else []
+        if stress is not None and len(stress) != B:
+            raise ValueError(f"stress: {len(stress)} vectors for {B} utterances")
+        if stress is not None and any(s is None for s in stress):
+            if not all(s is None for s in stress):
+                raise ValueError("stress must be given for every utterance or for none")
+            stress = None
+        lens_p = [int(u.numel()) for u in utterances]
+        if min(lens_p) < 1:
+            raise ValueError("empty utterance")
+        if stress is not None and [int(s.numel()) for s in stress] != lens_p:
+            raise ValueError("stress and phoneme vectors differ in length")
+        Pn = max(lens_p)
+        if Pn > d.max_len:
+            raise ValueError(f"utterance of {Pn} phonemes exceeds the positional table ({d.max_len})")
+        ids_h = torch.zeros(B, Pn, dtype=torch.int64)
+        st_h = torch.zeros(B, Pn, dtype=torch.int64) if stress is not None else None
+        for b, u in enumerate(utterances):
+            ids_h[b, :lens_p[b]] = u.reshape(-1).to("cpu", torch.int64)
+            if st_h is not None:
+                st_h[b, :lens_p[b]] = stress[b].reshape(-1).to("cpu", torch.int64)
+        ids = ids_h.to(self.device)
+        st = st_h.to(self.device) if st_h is not None else None
+        Ne = B * Pn
+        edt, ddt = self.enc_dt, self.dec_dt
+        pe = P["positional_encoding.pe"].view(d.max_len, H)
+        saved_drop, self.train_dropout = self.train_dropout, False
+        try:
+            # ---- encode_text (model.py:375-388): generate's launch sequence under the key mask ----
+            text_mask = self._buf("syn.text_mask", B, Pn, dtype=torch.uint8)
+            kk.call("kk_ids_eq_zero", ids, text_mask, Ne)
+            x = self._buf("syn.enc.x0", Ne, H)
+            kk.call("kk_embed_fwd", ids, st, P["text_embedding.weight"], P["stress_embedding.weight"] if st is not None else None,
+                    pe, x, B, Pn, H, float(H ** 0.5), self.rng, 1, 0.0)
+            y1 = None
+            for i in range(d.enc_layers):
+                pf, key = f"transformer_encoder_layers.{i}", f"syn.enc{i}"
+                if y1 is None:
+                    y1 = self._ln_fwd(key + ".ln1", x, pf + ".norm1", edt)
+                xm = self._buf(key + ".xm", Ne, H)
+                y2 = self._attn_fwd(key + ".sa", pf + ".self_attn", y1, None, B, Pn, Pn, True, False, text_mask, x, xm,
+                                    next_ln=(key + ".ln2", pf + ".norm2", edt))
+                xo = self._buf(key + ".xo", Ne, H)
+                nxt = ((f"syn.enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", edt) if i + 1 < d.enc_layers
+                       else ("syn.enc.norm", "encoder_norm", torch.float32))
+                y1 = self._ffn_fwd(key + ".ff", pf + ".ff", y2, xm, xo, d.enc_ff, Pn, next_ln=nxt)
+                x = xo
+            enc = y1
+            # ---- duration predictor, each row over its own P_b phonemes ----
+            plens = torch.tensor(lens_p, dtype=torch.int32).to(self.device)
+            log_dur = self._buf("syn.log_dur", B, Pn)
+            col_e = self._buf("syn.vp.col_enc", Ne, 3 * H, dtype=edt)
+            kk.call("kk_im2col3_rows_fwd", enc, col_e, plens, B, Pn, H, CHUNK, _b16(col_e))
+            dmask = self._buf("syn.vp.dur_mask", B, Pn, dtype=torch.uint8)
+            kk.call("kk_varpred_row_mask", text_mask, plens, dmask, B, Pn, CHUNK)
+            self._varpred_rows_fwd("syn.vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, plens, dmask, log_dur)
+            dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
+            sums = dur.sum(dim=1).cpu().tolist()                   # (host sync: the row lengths size everything below)
+            Tb = [max(int(s_), 3) for s_ in sums]
+            for b, tb in enumerate(Tb):
+                if tb > d.max_len:
+                    raise ValueError(f"utterance {b}: predicted length {tb} exceeds the positional table ({d.max_len})")
+            T = max(Tb)
+            Nd = B * T
+            flens = torch.tensor(Tb, dtype=torch.int32).to(self.device)
+            idx, lens, tot = (self._buf("syn.lr.idx", B, T, dtype=torch.int64), self._buf("syn.lr.lens", B, dtype=torch.int64),
+                              self._buf("syn.lr.total", B, dtype=torch.int64))
+            kk.call("kk_length_regulate_index", dur, idx, lens, tot, B, Pn, T)
+            xf = self._buf("syn.va.xf", Nd, H)
+            kk.call("kk_length_regulate_gather", enc, idx, xf, B, Pn, T, H)
+            fmask = (torch.arange(T, device=self.device)[None, :] >= lens[:, None]).to(torch.uint8).contiguous()
+            vmask = self._buf("syn.vp.frame_mask", B, T, dtype=torch.uint8)
+            kk.call("kk_varpred_row_mask", fmask, flens, vmask, B, T, CHUNK)
+            col_f = self._buf("syn.vp.col_frames", Nd, 3 * H, dtype=ddt)
+            kk.call("kk_im2col3_rows_fwd", xf, col_f, flens, B, T, H, CHUNK, _b16(col_f))
+            pitch, energy = self._buf("syn.pitch", B, T), self._buf("syn.energy", B, T)
+            self._varpred_rows_fwd("syn.vp.pitch", f"{VA}.pitch_predictor", xf, col_f, B, T, flens, vmask, pitch)
+            self._varpred_rows_fwd("syn.vp.energy", f"{VA}.energy_predictor", xf, col_f, B, T, flens, vmask, energy)
+            memory, fm2 = self._buf("syn.va.memory", Nd, H, dtype=ddt), self._buf("syn.va.fmask", B, T, dtype=torch.uint8)
+            pidx, eidx = self._buf("syn.va.pidx", B, T, dtype=torch.int32), self._buf("syn.va.eidx", B, T, dtype=torch.int32)
+            kk.call("kk_bucket_embed_add_fwd", xf, pitch.clamp(0.0, 1.0), energy.clamp(0.0, 1.0), P[f"{VA}.pitch_bins"],
+                    P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
+                    pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
+            self._cross_kv_fwd_all(memory, Nd, T, ddt, ns="syn.")
+            # ---- generation bounds of each row (model.py:741-750) ----
+            bounds = []
+            for b, expected in enumerate(Tb):
+                lo = max(min_len_floor, int(expected * min_len_ratio))
+                hi = min(max_len, max(expected + 80, int(expected * max_len_ratio)), max_len_cap)
+                if hi <= lo:
+                    hi = min(max_len, lo + 1)
+                if hi > d.max_len:
+                    raise ValueError(f"utterance {b}: generation bound {hi} exceeds the positional table ({d.max_len})")
+                if hi < 1:
+                    raise ValueError(f"utterance {b}: generation bound {hi} leaves no frame")
+                bounds.append((lo, expected, hi))
+            max_expected = max(hi for _, _, hi in bounds)
+            rb = torch.tensor([[r[k] for r in bounds] for k in range(3)], dtype=torch.int32).to(self.device)   # [3, B]: min | expected | max
+            BH, L1 = B * H, max_expected + 1
+            for i in range(d.dec_layers):
+                self._buf(f"syn.dec{i}.kcache", max_expected, BH, dtype=ddt).zero_()
+                self._buf(f"syn.dec{i}.vcache", max_expected, BH, dtype=ddt).zero_()
+            mel_out = self._buf("syn.mel", B, L1, M)                               # row 0 = the all-zero first input
+            mel_out.zero_()
+            stop_logit = self._buf("syn.stop", max_expected, B)
+            t_dev = self._buf("syn.t", 1, dtype=torch.int32)
+            t_dev.zero_()
+            self._buf("syn.kmask", 1, max_expected, dtype=torch.uint8).fill_(1)
+            done, frames_d = self._buf("syn.done", B, dtype=torch.uint8), self._buf("syn.frames", B, dtype=torch.int32)
+            live = self._buf("syn.live", 1, dtype=torch.int32)
+            done.zero_()
+            frames_d.zero_()
+            live.fill_(B)
+            frame_out, stop_now = self._buf("syn.frame_out", B, M), self._buf("syn.stop_now", B)
+
+            def decode_step():
+                self._decode_step("syn", B, T, max_expected, memory, fm2)
+                kk.call("kk_decode_epilogue_rows", frame_out, stop_now, mel_out, stop_logit, t_dev, done, frames_d, live, rb[0], rb[1],
+                        rb[2], B, L1, M, float(stop_threshold), float(post_expected_stop_threshold))
+
+            step_graph = None
+            for t in range(max_expected):
+                if step_graph is not None:
+                    step_graph.replay()
+                else:
+                    decode_step()                          # frame 0 eagerly: it sizes the workspaces a capture may not allocate
+                    if decode_graph and max_expected > 1:
+                        with self.capture_lock:
+                            torch.cuda.synchronize()
+                            step_graph = torch.cuda.CUDAGraph()
+                            with torch.cuda.graph(step_graph, capture_error_mode="thread_local"):
+                                decode_step()
+                if ((t + 1) % check_every == 0 or t + 1 == max_expected) and int(live.item()) == 0:
+                    break
+            nf = frames_d.cpu().tolist()
+            mels = [mel_out[b, 1:nf[b] + 1].clamp(min=-11.5, max=2.0).clone() for b in range(B)]
+            if want_info:
+                return mels, {"durations": [dur[b, :lens_p[b]].clone() for b in range(B)], "T": Tb, "bounds": bounds}
+            return mels
         finally:
             self.train_dropout = saved_drop
 
