@@ -375,6 +375,29 @@ int kk_decode_epilogue_rows(const float *frame_out, const float *stop, float *me
                             int *frames, int *live, const int *min_b, const int *expected_b, const int *max_b, int B, int L1, int M,
                             float stop_threshold, float post_expected_stop_threshold, void *stream);
 
+/* ---- HiFi-GAN vocoder (kokoro_ruslan_amd/vocoder.py; kk_vocoder.hip): mels -> waveforms for a packed batch ----
+ * Activations are channels-last fp32 [rows, C]; the utterances are packed back to back along time and seg[0..nseg] holds their
+ * start rows in the layer's INPUT row units (seg[0] = 0, seg[nseg] = rows).  A tap never reads outside its own utterance: each
+ * conv zero-pads at its utterance's ends.  The operand is leaky_relu(x, slope) (slope 1: identity), rounded to bf16 when w_bf16.
+ * w: tap-major [taps][npad][kpad] (bf16 when w_bf16, else fp32), K = input channels contiguous, zero padded (kpad % 32 == 0,
+ * npad % 64 == 0).  The reduction order of an output element depends on the layer shape only (no split-K, no atomics). */
+/* Conv1d(cin, cout, k odd, dilation, padding (k-1)*dilation/2) + bias, then + res (residual, may alias y), then mrf + . (the
+ * multi-receptive-field sum, may alias y), then / mrf_div when mrf_div > 0.  y: [rows, cout] */
+int kk_voc_conv1d(const float *x, int64_t rows, int cin, const void *w, int kpad, int npad, const float *bias, float *y, int cout, int k,
+                  int dilation, float slope, const int *seg, int nseg, const float *res, const float *mrf, int mrf_div, int w_bf16,
+                  void *stream);
+/* ConvTranspose1d(cin, cout, k, stride, padding (k-stride)/2) in polyphase form: output row q of the INPUT holds stride * cout
+ * channels, i.e. y viewed as [rows * stride, cout] is the transposed conv's output.  Taps q + off0 .. q + off0 + taps - 1 (see
+ * kk_voc_convt_taps); w[tap][r * cout + co][ci] = W[ci][co][kk] where input q + tap + off0 feeds output q * stride + r through kk. */
+int kk_voc_convt1d(const float *x, int64_t rows, int cin, const void *w, int kpad, int npad, const float *bias, float *y, int cout, int k,
+                   int stride, float slope, const int *seg, int nseg, int w_bf16, void *stream);
+/* taps of the polyphase form of ConvTranspose1d(k, stride, padding (k-stride)/2) (*off0: the first tap's row offset), 0 when the pair
+ * is not supported (k < stride or k - stride odd) */
+int kk_voc_convt_taps(int k, int stride, int *off0);
+/* conv_post: y[r] = tanh(bias[0] + sum_{j,c} w[j][c] * leaky_relu(x[r + j - (k-1)/2][c], slope)), fp32; w: [k][cin] */
+int kk_voc_post(const float *x, int64_t rows, int cin, const float *w, const float *bias, float *y, int k, float slope, const int *seg,
+                int nseg, void *stream);
+
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}
  * (transformers.py:16-40,482-487,569-581; the FFN has two dropouts in series, :111).  *seed is read on the device. */

@@ -3,10 +3,13 @@
     kokoro-synth --checkpoint CKPT (--features CACHE_DIR [--indices ...] | --ids FILE.jsonl) --output DIR
                  [--batch-size 32] [--weights auto|ema|model] [--stop-threshold X] [--max-len N] [--min-len-ratio R]
                  [--min-len-floor N] [--trim] [--math bf16|f32]
+                 [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32]]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
 --features reads phoneme_indices / stress_indices from a precomputed feature cache (kokoro.data.cached); --ids reads JSON lines
-{"name", "phoneme_indices", "stress_indices"?}.  --trim applies the reference's clamp + trailing-silence trim (:588-619)."""
+{"name", "phoneme_indices", "stress_indices"?}.  --trim applies the reference's clamp + trailing-silence trim (:588-619).
+--vocoder (a HiFi-GAN generator checkpoint: a directory with generator.pth + config.json, or a file) also writes <name>.wav: the
+saved mel, clamped to [-11.5, 2] (:590), vocoded on the device in batches, int16 PCM at the vocoder config's sampling_rate."""
 from __future__ import annotations
 
 import argparse
@@ -34,6 +37,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min-len-floor", type=int, default=None)
     p.add_argument("--trim", action="store_true")
     p.add_argument("--math", choices=("bf16", "f32"), default="bf16")
+    p.add_argument("--vocoder", metavar="PATH", default=None, help="HiFi-GAN generator: directory or checkpoint file")
+    p.add_argument("--vocoder-config", metavar="JSON", default=None, help="HiFi-GAN config (default: the checkpoint's config.json)")
+    p.add_argument("--vocoder-math", choices=("bf16", "f32"), default="bf16")
     return p
 
 
@@ -87,12 +93,22 @@ def main(argv=None) -> int:
                                                 min_len_floor=args.min_len_floor)
     mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **controls.kwargs())
     os.makedirs(args.output, exist_ok=True)
+    saved = []
     for name, mel in zip(names, mels):
         mel = mel.float().cpu()
         if args.trim:
             mel = trim_trailing_silence(mel)
         np.save(os.path.join(args.output, f"{name}.npy"), mel.t().contiguous().numpy().astype(np.float32))
+        saved.append(mel)
     print(f"kokoro-synth: {len(mels)} mels ({used} weights, {controls}) -> {args.output}")
+    if args.vocoder:
+        from kokoro.inference.audio import vocode, write_wav
+        from kokoro_ruslan_amd.vocoder import HifiganVocoder
+        voc = HifiganVocoder.from_checkpoint(args.vocoder, args.vocoder_config, device=engine.device, math_mode=args.vocoder_math)
+        audio = vocode(voc, saved)
+        for name, a in zip(names, audio):
+            write_wav(os.path.join(args.output, f"{name}.wav"), a, voc.sampling_rate)
+        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({args.vocoder_math} vocoder) -> {args.output}")
     return 0
 
 

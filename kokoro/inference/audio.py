@@ -1,0 +1,27 @@
+"""Mels to audio: the engine-side counterpart of the reference's HiFi-GAN step (inference/inference.py:588-634) and of
+AudioUtils.save_audio.  `vocode` runs a batch of mels through a kokoro_ruslan_amd.vocoder.HifiganVocoder; `write_wav` writes one
+waveform as 16-bit PCM."""
+from __future__ import annotations
+
+from typing import List, Sequence
+
+import numpy as np
+import torch
+
+
+def vocode(vocoder, mels: Sequence[torch.Tensor], clamp: bool = True, **kwargs) -> List[torch.Tensor]:
+    """Waveforms of mels [frames_b, n_mels], in input order.  clamp: the reference's unconditional clamp(-11.5, 2.0) before the
+    vocoder (inference.py:590).  kwargs go to vocoder.vocode (max_samples)."""
+    if clamp:
+        mels = [torch.clamp(m, min=-11.5, max=2.0) for m in mels]
+    return vocoder.vocode(list(mels), **kwargs)
+
+
+def write_wav(path: str, audio, sample_rate: int) -> None:
+    """AudioUtils.save_audio's scipy path: peak-normalise (not below a peak of 1e-8), scale by 32767, write int16 PCM mono."""
+    from scipy.io import wavfile
+    a = audio.detach().float().cpu().reshape(-1) if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio)).float().reshape(-1)
+    peak = torch.max(torch.abs(a)) if a.numel() else torch.tensor(0.0)
+    if float(peak) >= 1e-8:
+        a = a / peak
+    wavfile.write(str(path), int(sample_rate), (a.numpy() * 32767).astype(np.int16))

@@ -228,6 +228,10 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_groupnorm_relu_rows_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _U, _F, _P],
     "kk_varpred_row_mask": [_P, _P, _P, _I, _I, _I, _P],
     "kk_decode_epilogue_rows": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "kk_voc_conv1d": [_P, _L, _I, _P, _I, _I, _P, _P, _I, _I, _I, _F, _P, _I, _P, _P, _I, _I, _P],
+    "kk_voc_convt1d": [_P, _L, _I, _P, _I, _I, _P, _P, _I, _I, _I, _F, _P, _I, _I, _P],
+    "kk_voc_convt_taps": [_I, _I, _P],
+    "kk_voc_post": [_P, _L, _I, _P, _P, _P, _I, _F, _P, _I, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
     "kk_losses_finalize": [_P, C.POINTER(KkLossCfg), _P, _I, _P, _P, _P, _I, _P],
     "kk_losses_bwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _P, _P],
