@@ -398,6 +398,24 @@ int kk_voc_convt_taps(int k, int stride, int *off0);
 int kk_voc_post(const float *x, int64_t rows, int cin, const float *w, const float *bias, float *y, int k, float slope, const int *seg,
                 int nseg, void *stream);
 
+/* ---- Griffin-Lim vocoder (kokoro_ruslan_amd/griffinlim.py; kk_griffinlim.hip): log-mels -> waveforms for a packed batch ----
+ * n_fft = win = 1024, hop = 256, periodic Hann, center = True, reflect padding, onesided; fp32 throughout.  Spectra are [frames, 513]
+ * complex (interleaved fp32 pairs); the utterances are packed back to back along frames.  tiles: int32 [ntiles][4] = {utterance start
+ * frame, utterance frames (>= 4), first frame of the tile (a multiple of kk_gl_tile_frames()), utterance's first sample in the packed
+ * waveform}; the tiles of an utterance cover its frames.  tw: exp(-2 pi i j / 1024) for j < 1024 (complex); win: the window, 1024.
+ * Every sum runs in an order fixed by the position within the utterance: a waveform does not depend on the rest of the batch. */
+/* frames of one tile */
+int kk_gl_tile_frames(void);
+/* S = sqrt(relu(pinv . exp(mel))) (mel [frames, 80], pinv [513, 80]); Y = S . angles (angles [frames, 513] complex, or null: 1);
+ * rebuilt = 0 */
+int kk_gl_init(const float *mel, int64_t frames, const float *pinv, const void *angles, float *S, void *Y, void *rebuilt, void *stream);
+/* one iteration: X = stft(istft(y_in)); c = X - beta . rebuilt (beta = 0: c = X); rebuilt = X; y_out = S . c / (|c| + 1e-16).
+ * y_out != y_in (neighbouring tiles read y_in) */
+int kk_gl_iter(const void *y_in, void *y_out, void *rebuilt, const float *S, const int *tiles, int ntiles, const void *tw,
+               const float *win, float beta, void *stream);
+/* wave = istft(y): 256 (frames - 1) samples per utterance at its offset */
+int kk_gl_istft(const void *y, const int *tiles, int ntiles, const void *tw, const float *win, float *wave, void *stream);
+
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}
  * (transformers.py:16-40,482-487,569-581; the FFN has two dropouts in series, :111).  *seed is read on the device. */

@@ -4,12 +4,15 @@
                  [--batch-size 32] [--weights auto|ema|model] [--stop-threshold X] [--max-len N] [--min-len-ratio R]
                  [--min-len-floor N] [--trim] [--math bf16|f32]
                  [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32]]
+                 [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
 --features reads phoneme_indices / stress_indices from a precomputed feature cache (kokoro.data.cached); --ids reads JSON lines
 {"name", "phoneme_indices", "stress_indices"?}.  --trim applies the reference's clamp + trailing-silence trim (:588-619).
 --vocoder (a HiFi-GAN generator checkpoint: a directory with generator.pth + config.json, or a file) also writes <name>.wav: the
-saved mel, clamped to [-11.5, 2] (:590), vocoded on the device in batches, int16 PCM at the vocoder config's sampling_rate."""
+saved mel, clamped to [-11.5, 2] (:590), vocoded on the device in batches, int16 PCM at the vocoder config's sampling_rate.
+--griffin-lim writes the same <name>.wav with the reference's Griffin-Lim vocoder instead (kokoro_ruslan_amd.griffinlim, 80 mels,
+22050 Hz; :684-739), no checkpoint needed: N iterations (default 60) from random phases drawn under seed S (default: unseeded)."""
 from __future__ import annotations
 
 import argparse
@@ -40,7 +43,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--vocoder", metavar="PATH", default=None, help="HiFi-GAN generator: directory or checkpoint file")
     p.add_argument("--vocoder-config", metavar="JSON", default=None, help="HiFi-GAN config (default: the checkpoint's config.json)")
     p.add_argument("--vocoder-math", choices=("bf16", "f32"), default="bf16")
+    p.add_argument("--griffin-lim", action="store_true", help="vocode with Griffin-Lim (no checkpoint; not with --vocoder)")
+    p.add_argument("--griffin-lim-iters", type=int, default=60, metavar="N")
+    p.add_argument("--griffin-lim-seed", type=int, default=None, metavar="S", help="seed of the initial random phases")
     return p
+
+
+def check_args(p: argparse.ArgumentParser, args) -> None:
+    if args.griffin_lim and args.vocoder:
+        p.error("--griffin-lim and --vocoder are alternatives: give one")
+    if not args.griffin_lim and (args.griffin_lim_iters != 60 or args.griffin_lim_seed is not None):
+        p.error("--griffin-lim-iters / --griffin-lim-seed need --griffin-lim")
+    if args.griffin_lim_iters < 0:
+        p.error("--griffin-lim-iters must be >= 0")
 
 
 def read_ids(path: str) -> Tuple[List[str], List[torch.Tensor], Optional[List[torch.Tensor]]]:
@@ -83,7 +98,9 @@ def read_features(cache_dir: str, indices=None) -> Tuple[List[str], List[torch.T
 def main(argv=None) -> int:
     import numpy as np
     from kokoro.inference.synth import load_for_inference, synthesize, trim_trailing_silence
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_args(parser, args)
     if args.ids:
         names, ids, stress = read_ids(args.ids)
     else:
@@ -91,6 +108,8 @@ def main(argv=None) -> int:
     engine, controls, used = load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,
                                                 stop_threshold=args.stop_threshold, min_len_ratio=args.min_len_ratio,
                                                 min_len_floor=args.min_len_floor)
+    if args.griffin_lim and engine.dims.mel != 80:
+        parser.error(f"--griffin-lim needs an 80-mel model; this checkpoint makes {engine.dims.mel} mel channels")
     mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **controls.kwargs())
     os.makedirs(args.output, exist_ok=True)
     saved = []
@@ -109,6 +128,16 @@ def main(argv=None) -> int:
         for name, a in zip(names, audio):
             write_wav(os.path.join(args.output, f"{name}.wav"), a, voc.sampling_rate)
         print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({args.vocoder_math} vocoder) -> {args.output}")
+    if args.griffin_lim:
+        from kokoro.inference.audio import vocode, write_wav
+        from kokoro_ruslan_amd.griffinlim import GriffinLimVocoder
+        gen = torch.Generator().manual_seed(args.griffin_lim_seed) if args.griffin_lim_seed is not None else None
+        voc = GriffinLimVocoder(device=engine.device)
+        audio = vocode(voc, saved, n_iter=args.griffin_lim_iters, generator=gen)
+        for name, a in zip(names, audio):
+            write_wav(os.path.join(args.output, f"{name}.wav"), a, voc.sampling_rate)
+        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz (Griffin-Lim, {args.griffin_lim_iters} iterations) "
+              f"-> {args.output}")
     return 0
 
 

@@ -1,6 +1,6 @@
-"""Mels to audio: the engine-side counterpart of the reference's HiFi-GAN step (inference/inference.py:588-634) and of
-AudioUtils.save_audio.  `vocode` runs a batch of mels through a kokoro_ruslan_amd.vocoder.HifiganVocoder; `write_wav` writes one
-waveform as 16-bit PCM."""
+"""Mels to audio: the engine-side counterpart of the reference's vocoder step (inference/inference.py:588-634, 684-739) and of
+AudioUtils.save_audio.  `vocode` runs a batch of mels through a kokoro_ruslan_amd.vocoder.HifiganVocoder or a
+kokoro_ruslan_amd.griffinlim.GriffinLimVocoder; `write_wav` writes one waveform as 16-bit PCM."""
 from __future__ import annotations
 
 from typing import List, Sequence
@@ -11,7 +11,7 @@ import torch
 
 def vocode(vocoder, mels: Sequence[torch.Tensor], clamp: bool = True, **kwargs) -> List[torch.Tensor]:
     """Waveforms of mels [frames_b, n_mels], in input order.  clamp: the reference's unconditional clamp(-11.5, 2.0) before the
-    vocoder (inference.py:590).  kwargs go to vocoder.vocode (max_samples)."""
+    vocoder (inference.py:590).  kwargs go to vocoder.vocode (HiFi-GAN: max_samples; Griffin-Lim: n_iter, generator, ...)."""
     if clamp:
         mels = [torch.clamp(m, min=-11.5, max=2.0) for m in mels]
     return vocoder.vocode(list(mels), **kwargs)

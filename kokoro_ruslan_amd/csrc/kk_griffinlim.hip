@@ -1,0 +1,287 @@
+// Griffin-Lim kernels (kokoro_ruslan_amd/griffinlim.py): a batch of log-mels to waveforms on the device, with n_fft = win = 1024,
+// hop = 256, periodic Hann window, center = True, reflect padding, onesided (the reference's torchaudio GriffinLim settings).
+//
+//  init       S = sqrt(relu(pinv(fb^T) . exp(mel))) per frame (513 bins from 80 mels, fp32), Y = S . angles0, rebuilt = 0
+//  iterate    one launch per Griffin-Lim iteration: x = istft(Y); X = stft(x); c = X - beta . rebuilt; rebuilt = X;
+//             Y' = S . c / (|c| + 1e-16)
+//  istft      the final waveform istft(Y) (the iterate kernel's first half)
+//
+// Layout: spectra are [frames, 513] complex (float2), S is [frames, 513] fp32.  The utterances of a batch are packed back to back
+// along frames with no padding.  Work is split into tiles of GTF frames of ONE utterance (a host-built table of {start, frames,
+// f0, wave offset}); a tile's inverse FFTs cover its frames and a halo of 3 frames on each side (n_fft / hop - 1), clipped to the
+// utterance (4 on the left for a one-frame last tile), which is every frame that overlaps the samples the tile's forward frames
+// read, reflect padding included.
+//
+// FFT: a 1024-point real transform is a 512-point complex one plus the split step.  One wave64 per frame, 8 points per lane, three
+// radix-8 passes in registers with two LDS exchanges (XOR-swizzled so each b64 access is conflict-free within its lane group).
+// Twiddles and the window come from host tables computed in fp64.
+//
+// Determinism: every sum runs in an order fixed by the frame's (or sample's) position in its own utterance: the overlap-add of a
+// sample sums its frames in ascending order whichever tile computes it.  So a waveform's bits do not depend on the rest of the batch.
+#include "kk_common.h"
+
+namespace {
+
+constexpr int GN = 1024, GHOP = 256, GBINS = 513, GMELS = 80;
+constexpr int GTF = 8, GHALO = 3, GHF = GTF + 2 * GHALO;     // tile frames, halo frames per side, inverse FFTs per tile (at most)
+constexpr int GXS = GHF * GHOP + GN - GHOP;                  // samples the halo frames cover
+constexpr int GTHREADS = 256, GWAVES = GTHREADS / 64;
+constexpr int GINIT_F = 8;                                   // frames per init workgroup
+
+struct GlIter {
+    const float2 *yin;     // [frames, 513]
+    float2 *yout;          // [frames, 513] (iterate) — ping-pong: neighbouring tiles read yin
+    float2 *reb;           // [frames, 513] rebuilt of the previous iteration, overwritten with this one's (iterate)
+    const float *S;        // [frames, 513] (iterate)
+    const int4 *tiles;     // {utterance start frame, utterance frames, first frame of the tile, utterance's first wave sample}
+    const float2 *tw;      // exp(-2 pi i j / 1024), j < 1024
+    const float *win;      // periodic Hann, 1024
+    float *wave;           // packed waveform, 256 (frames_b - 1) samples per utterance (istft)
+    float beta;            // momentum / (1 + momentum); 0: no momentum term
+    int final_istft;
+};
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+template <int SIGN> __device__ __forceinline__ float2 dirw(float2 w) { return SIGN < 0 ? w : make_float2(w.x, -w.y); }
+template <int SIGN> __device__ __forceinline__ float2 mul_i(float2 a) {      // a . (SIGN i)
+    return SIGN < 0 ? make_float2(a.y, -a.x) : make_float2(-a.y, a.x);
+}
+
+// In-place 8-point DFT, natural order in and out: X[k] = sum_n v[n] exp(SIGN 2 pi i n k / 8).
+template <int SIGN> __device__ __forceinline__ void dft8(float2 *v) {
+    constexpr float R = 0.70710678118654752f;
+    float2 e[4], o[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                            // DFT4 of the even (h = 0) and odd (h = 1) samples
+        const float2 a = v[h], b = v[h + 2], c = v[h + 4], d = v[h + 6];
+        const float2 s0 = make_float2(a.x + c.x, a.y + c.y), s1 = make_float2(a.x - c.x, a.y - c.y);
+        const float2 s2 = make_float2(b.x + d.x, b.y + d.y), s3 = mul_i<SIGN>(make_float2(b.x - d.x, b.y - d.y));
+        float2 *y = h ? o : e;
+        y[0] = make_float2(s0.x + s2.x, s0.y + s2.y);
+        y[2] = make_float2(s0.x - s2.x, s0.y - s2.y);
+        y[1] = make_float2(s1.x + s3.x, s1.y + s3.y);
+        y[3] = make_float2(s1.x - s3.x, s1.y - s3.y);
+    }
+    o[1] = cmul(o[1], make_float2(R, SIGN * R));
+    o[2] = mul_i<SIGN>(o[2]);
+    o[3] = cmul(o[3], make_float2(-R, SIGN * R));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        v[k] = make_float2(e[k].x + o[k].x, e[k].y + o[k].y);
+        v[k + 4] = make_float2(e[k].x - o[k].x, e[k].y - o[k].y);
+    }
+}
+
+// 512-point complex DFT of one wave: lane l holds v[m] = z[l + 64 m]; on return lane q holds v[k2] = Z[(q >> 3) + 8 (q & 7) + 64 k2].
+// Z[k0 + 8 k1 + 64 k2] = sum_{l0} w8^(l0 k2) w64^(l0 k1) sum_{l1} w8^(l1 k1) w512^(l k0) sum_m w8^(m k0) z[l + 64 m], l = l0 + 8 l1.
+// sl: this wave's 512-float2 LDS exchange slot.  tw1[j] = w512^(lane j), tw2[j] = w512^(8 (lane & 7) j) (forward sign).
+template <int SIGN> __device__ __forceinline__ void fft512(float2 *v, float2 *sl, const float2 *tw1, const float2 *tw2, int lane) {
+    dft8<SIGN>(v);
+#pragma unroll
+    for (int j = 1; j < 8; ++j) v[j] = cmul(v[j], dirw<SIGN>(tw1[j]));
+    const int a = lane >> 3, b = lane & 7;
+    __syncwarp();                                            // the slot's previous readers are done
+#pragma unroll
+    for (int k0 = 0; k0 < 8; ++k0) sl[k0 * 64 + 8 * (a ^ k0) + b] = v[k0];          // element (k0, l = b + 8 a)
+    __syncwarp();
+#pragma unroll
+    for (int l1 = 0; l1 < 8; ++l1) v[l1] = sl[a * 64 + 8 * (l1 ^ a) + b];           // lane (k0 = a, l0 = b)
+    dft8<SIGN>(v);
+#pragma unroll
+    for (int j = 1; j < 8; ++j) v[j] = cmul(v[j], dirw<SIGN>(tw2[j]));
+    __syncwarp();
+#pragma unroll
+    for (int k1 = 0; k1 < 8; ++k1) sl[a * 64 + 8 * (k1 ^ a) + (b ^ k1)] = v[k1];    // element (k0 = a, k1, l0 = b)
+    __syncwarp();
+#pragma unroll
+    for (int l0 = 0; l0 < 8; ++l0) v[l0] = sl[a * 64 + 8 * (b ^ a) + (l0 ^ b)];     // lane (k0 = a, k1 = b)
+    dft8<SIGN>(v);
+}
+
+__global__ __launch_bounds__(GTHREADS) void gl_init_kernel(const float *__restrict__ mel, int64_t frames, const float *__restrict__ pinv,
+                                                           const float2 *__restrict__ ang, float *__restrict__ S, float2 *__restrict__ Y,
+                                                           float2 *__restrict__ R) {
+    __shared__ float e[GINIT_F][GMELS];
+    const int64_t r0 = (int64_t)blockIdx.x * GINIT_F;
+    for (int i = threadIdx.x; i < GINIT_F * GMELS; i += GTHREADS) {
+        const int f = i / GMELS, m = i % GMELS;
+        e[f][m] = r0 + f < frames ? expf(mel[(r0 + f) * GMELS + m]) : 0.f;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < GBINS; k += GTHREADS) {
+        float acc[GINIT_F];
+#pragma unroll
+        for (int f = 0; f < GINIT_F; ++f) acc[f] = 0.f;
+        const float *pr = pinv + k * GMELS;
+        for (int m = 0; m < GMELS; ++m) {
+            const float w = pr[m];
+#pragma unroll
+            for (int f = 0; f < GINIT_F; ++f) acc[f] = fmaf(w, e[f][m], acc[f]);
+        }
+#pragma unroll
+        for (int f = 0; f < GINIT_F; ++f) {
+            const int64_t row = r0 + f;
+            if (row >= frames) break;
+            const int64_t i = row * GBINS + k;
+            const float s = sqrtf(fmaxf(acc[f], 0.f));
+            const float2 a = ang ? ang[i] : make_float2(1.f, 0.f);
+            S[i] = s;
+            Y[i] = make_float2(s * a.x, s * a.y);
+            R[i] = make_float2(0.f, 0.f);
+        }
+    }
+}
+
+__global__ __launch_bounds__(GTHREADS) void gl_iter_kernel(const GlIter a) {
+    __shared__ __attribute__((aligned(16))) float frm[GHF][GN];     // windowed inverse FFTs of the halo frames; then FFT slots
+    __shared__ float xs[GXS];                                       // istft samples the tile reads, by overlap-add position
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int4 tl = a.tiles[blockIdx.x];
+    const int start = tl.x, T = tl.y, f0 = tl.z;
+    // the reflection at the end reads sample 256 (T - 1) - 1, which frames T - 5 .. T - 2 cover: a one-frame last tile reaches 4 back
+    const int f1 = min(f0 + GTF, T), h0 = max(min(f0 - GHALO, T - 5), 0), h1 = min(f1 + GHALO, T);
+    const int pbase = h0 * GHOP, L = GHOP * (T - 1);
+
+    float2 tw1[8], tw2[8], twk[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        tw1[j] = a.tw[(2 * lane * j) & (GN - 1)];
+        tw2[j] = a.tw[(16 * (lane & 7) * j) & (GN - 1)];
+        twk[j] = a.tw[lane + 64 * j];                              // w1024^k of bin k = lane + 64 j (the split step)
+    }
+    const int qa = lane >> 3, qb = lane & 7;                       // output lane q holds index qa + 8 qb + 64 k2
+
+    // 1. inverse real FFTs of the halo frames, windowed, into frm
+    for (int i = wave; i < h1 - h0; i += GWAVES) {
+        const float2 *yr = a.yin + (int64_t)(start + h0 + i) * GBINS;
+        float2 v[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {                              // Z[k] = X[k] + conj X[512-k] + i w^-k (X[k] - conj X[512-k])
+            const int k = lane + 64 * m;
+            float2 xk = yr[k], xm = yr[GN / 2 - k];
+            if (k == 0) { xk.y = 0.f; xm.y = 0.f; }               // c2r ignores the imaginary parts of bins 0 and 512
+            const float2 A = make_float2(xk.x + xm.x, xk.y - xm.y);
+            const float2 C = cmul(make_float2(xk.x - xm.x, xk.y + xm.y), make_float2(twk[m].x, -twk[m].y));
+            v[m] = make_float2(A.x - C.y, A.y + C.x);
+        }
+        float2 *sl = reinterpret_cast<float2 *>(frm[i]);
+        fft512<1>(v, sl, tw1, tw2, lane);
+        __syncwarp();
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) {
+            const int n = qa + 8 * qb + 64 * k2;
+            const float2 w = *reinterpret_cast<const float2 *>(a.win + 2 * n);
+            sl[n] = make_float2(v[k2].x * (1.f / GN) * w.x, v[k2].y * (1.f / GN) * w.y);
+        }
+    }
+    __syncthreads();
+
+    // 2. overlap-add / window-square envelope at every position the halo frames cover, inside the trimmed signal [512, 256 T + 256)
+    const int nxs = (h1 - h0) * GHOP + GN - GHOP;
+    for (int idx = threadIdx.x; idx < nxs; idx += GTHREADS) {
+        const int p = pbase + idx;
+        if (p < GN / 2 || p >= GHOP * T + GHOP) continue;
+        const int tlo = max(p >= GN ? (p - GN) / GHOP + 1 : 0, h0), thi = min(min(T - 1, p / GHOP), h1 - 1);
+        if (tlo > thi) continue;                                    // no halo frame here: never read
+        float acc = 0.f, env = 0.f;
+        for (int t = tlo; t <= thi; ++t) {
+            const int o = p - GHOP * t;
+            const float w = a.win[o];
+            acc += frm[t - h0][o];
+            env += w * w;
+        }
+        xs[idx] = acc / env;
+    }
+    __syncthreads();
+
+    if (a.final_istft) {                                            // 3'. the tile's own samples [256 f0, 256 f1) of the waveform
+        const int j1 = min(GHOP * f1, L);
+        for (int j = GHOP * f0 + threadIdx.x; j < j1; j += GTHREADS) a.wave[tl.w + j] = xs[j + GN / 2 - pbase];
+        return;
+    }
+
+    // 3. forward real FFTs of the tile's frames (reflect padding at the utterance's ends), momentum, normalisation
+    float2 *sl = reinterpret_cast<float2 *>(frm[wave]);            // frm is free now: one exchange slot per wave
+    for (int i = wave; i < f1 - f0; i += GWAVES) {
+        const int t = f0 + i;
+        float2 v[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int n = lane + 64 * m;
+            float s[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int j = GHOP * t - GN / 2 + 2 * n + h;
+                j = j < 0 ? -j : (j >= L ? 2 * (L - 1) - j : j);
+                s[h] = xs[j + GN / 2 - pbase];
+            }
+            const float2 w = *reinterpret_cast<const float2 *>(a.win + 2 * n);
+            v[m] = make_float2(s[0] * w.x, s[1] * w.y);
+        }
+        fft512<-1>(v, sl, tw1, tw2, lane);
+        __syncwarp();
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) sl[qa + 8 * qb + 64 * k2] = v[k2];
+        __syncwarp();
+        const int64_t row = (int64_t)(start + t) * GBINS;
+#pragma unroll
+        for (int j = 0; j <= 8; ++j) {
+            if (j == 8 && lane != 0) break;
+            const int k = j < 8 ? lane + 64 * j : GN / 2;
+            const float2 zk = sl[k & (GN / 2 - 1)], zm = sl[(GN / 2 - k) & (GN / 2 - 1)];
+            float2 X;
+            if (j < 8) {                                            // X[k] = (Z[k] + conj Z[512-k]) / 2 + w^k (Z[k] - conj Z[512-k]) / 2i
+                const float2 fe = make_float2((zk.x + zm.x) * 0.5f, (zk.y - zm.y) * 0.5f);
+                const float2 fo = make_float2((zk.y + zm.y) * 0.5f, (zm.x - zk.x) * 0.5f);
+                const float2 c = cmul(twk[j], fo);
+                X = make_float2(fe.x + c.x, fe.y + c.y);
+            } else {
+                X = make_float2(zk.x - zk.y, 0.f);                  // bin 512: even sum minus odd sum
+            }
+            float2 c = X;
+            if (a.beta != 0.f) {
+                const float2 p = a.reb[row + k];
+                c = make_float2(X.x - a.beta * p.x, X.y - a.beta * p.y);
+            }
+            a.reb[row + k] = X;
+            const float d = sqrtf(c.x * c.x + c.y * c.y) + 1e-16f;
+            const float s = a.S[row + k];
+            a.yout[row + k] = make_float2(s * (c.x / d), s * (c.y / d));
+        }
+    }
+}
+
+int launch_iter(const GlIter &g, int ntiles, hipStream_t s, const char *name) {
+    kk_note_kernel(g.final_istft ? "gl_istft" : "gl_iter");
+    hipLaunchKernelGGL(gl_iter_kernel, dim3(ntiles), dim3(GTHREADS), 0, s, g);
+    KK_LAUNCH_CHECK(name);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int kk_gl_tile_frames(void) { return GTF; }
+
+extern "C" int kk_gl_init(const float *mel, int64_t frames, const float *pinv, const void *angles, float *S, void *Y, void *rebuilt,
+                          void *stream) {
+    KK_REQUIRE(mel && pinv && S && Y && rebuilt && frames > 0, "kk_gl_init: bad args");
+    kk_note_kernel("gl_init");
+    hipLaunchKernelGGL(gl_init_kernel, dim3(kk_cdiv(frames, GINIT_F)), dim3(GTHREADS), 0, (hipStream_t)stream, mel, frames, pinv,
+                       (const float2 *)angles, S, (float2 *)Y, (float2 *)rebuilt);
+    KK_LAUNCH_CHECK("kk_gl_init");
+    return 0;
+}
+
+extern "C" int kk_gl_iter(const void *y_in, void *y_out, void *rebuilt, const float *S, const int *tiles, int ntiles, const void *tw,
+                          const float *win, float beta, void *stream) {
+    KK_REQUIRE(y_in && y_out && rebuilt && S && tiles && tw && win && ntiles > 0 && y_in != y_out,
+               "kk_gl_iter: bad args (y_in != y_out: neighbouring tiles read the old spectrum)");
+    GlIter g{(const float2 *)y_in, (float2 *)y_out, (float2 *)rebuilt, S, (const int4 *)tiles, (const float2 *)tw, win, nullptr, beta, 0};
+    return launch_iter(g, ntiles, (hipStream_t)stream, "kk_gl_iter");
+}
+
+extern "C" int kk_gl_istft(const void *y, const int *tiles, int ntiles, const void *tw, const float *win, float *wave, void *stream) {
+    KK_REQUIRE(y && tiles && tw && win && wave && ntiles > 0, "kk_gl_istft: bad args");
+    GlIter g{(const float2 *)y, nullptr, nullptr, nullptr, (const int4 *)tiles, (const float2 *)tw, win, wave, 0.f, 1};
+    return launch_iter(g, ntiles, (hipStream_t)stream, "kk_gl_istft");
+}

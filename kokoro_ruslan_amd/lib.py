@@ -232,6 +232,10 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_voc_convt1d": [_P, _L, _I, _P, _I, _I, _P, _P, _I, _I, _I, _F, _P, _I, _I, _P],
     "kk_voc_convt_taps": [_I, _I, _P],
     "kk_voc_post": [_P, _L, _I, _P, _P, _P, _I, _F, _P, _I, _P],
+    "kk_gl_tile_frames": [],
+    "kk_gl_init": [_P, _L, _P, _P, _P, _P, _P, _P],
+    "kk_gl_iter": [_P, _P, _P, _P, _P, _I, _P, _P, _F, _P],
+    "kk_gl_istft": [_P, _P, _I, _P, _P, _P, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
     "kk_losses_finalize": [_P, C.POINTER(KkLossCfg), _P, _I, _P, _P, _P, _I, _P],
     "kk_losses_bwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _P, _P],
