@@ -416,6 +416,31 @@ int kk_gl_iter(const void *y_in, void *y_out, void *rebuilt, const float *S, con
 /* wave = istft(y): 256 (frames - 1) samples per utterance at its offset */
 int kk_gl_istft(const void *y, const int *tiles, int ntiles, const void *tw, const float *win, float *wave, void *stream);
 
+/* ---- audio feature extraction (kokoro_ruslan_amd/features.py; kk_features.hip): waveforms -> log-mel, pitch, energy ----
+ * The reference's per-utterance front-end (22050 Hz, n_fft = win = 1024, hop 256, 80 HTK mels; pitch window 2048, lags 27..441), fp32.
+ * The waveforms of a batch are packed back to back: woff int64 [B + 1] sample offsets.  moff int32 [B + 1]: offsets of the mel frames
+ * kept per utterance, min(1 + max(n, 1024) / 256, max_seq_length); poff int32 [B + 1]: offsets of the pitch frames, 1 + max(n, 2048) /
+ * 256 each (all of them: the pitch statistics run over the whole utterance).  An utterance's output does not depend on the batch. */
+/* mel frames of one tile */
+int kk_feat_mel_tile_frames(void);
+/* peak[b] = max |x| over utterance b (max_samples: the longest utterance) */
+int kk_feat_peak(const float *wave, const int64_t *woff, int B, int64_t max_samples, float *peak, void *stream);
+/* log-mel [80, T_b] per utterance at 80 moff[b] (and the linear mel in the same layout when linmel is not null), eraw = log1p(mean over
+ * mels of the linear mel) per kept frame.  x = wave / (peak + 1e-9) on load.  tiles: int32 [ntiles][2] = {utterance, first frame (a
+ * multiple of kk_feat_mel_tile_frames())}; tw: exp(-2 pi i j / 1024), j < 1024; win: periodic Hann, 1024; fb: [513, 80]; span: int32
+ * [80][2], the bins [lo, hi) where each mel's triangle is non-zero */
+int kk_feat_mel(const float *wave, const int64_t *woff, const float *peak, const int *moff, const int *tiles, int ntiles, const void *tw,
+                const float *win, const float *fb, const int *span, float *logmel, float *linmel, float *eraw, void *stream);
+/* per pitch frame: candidate frequency in Hz (first CMND dip below 0.15 in lags 27..441, else the argmin, parabolic refinement), the
+ * largest normalised autocorrelation over those lags and the windowed frame's mean square.  frames: int32 [nframes][2] = {utterance,
+ * frame}; win: periodic Hann, 2048 */
+int kk_feat_pitch(const float *wave, const int64_t *woff, const float *peak, const int *poff, const int *frames, int nframes,
+                  const float *win, float *cand, float *acmax, float *msq, void *stream);
+/* per utterance: energy = clamp((eraw - q05) / max(q95 - q05, 1e-8), 0, 1); pitch = voicing, gap fill, 5-tap median, (f - 50) / 750
+ * clamped, cut to the kept mel frames.  scratch_a/b: one float per pitch frame each.  variance = 0: zero pitch and energy */
+int kk_feat_finish(const int *moff, const int *poff, int B, const float *eraw, const float *cand, const float *acmax, const float *msq,
+                   float *scratch_a, float *scratch_b, float *pitch, float *energy, int variance, void *stream);
+
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}
  * (transformers.py:16-40,482-487,569-581; the FFN has two dropouts in series, :111).  *seed is read on the device. */

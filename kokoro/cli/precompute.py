@@ -1,0 +1,102 @@
+"""kokoro-precompute: write the feature cache kokoro-train reads, with the acoustic features extracted on the device.
+
+    kokoro-precompute --wavs DIR --ids FILE.jsonl --cache-dir OUT [--force] [--no-variance] [--batch-size N] [--max-seq-length N]
+
+FILE.jsonl is kokoro-synth --ids's format, one utterance per line: {"name", "phoneme_indices"[, "stress_indices"]}, plus optional
+"phoneme_durations" (frames per phoneme, e.g. from an MFA alignment; absent: the reference's even fallback estimate) and "text".
+DIR/<name>.wav is the audio, 22050 Hz.  The phonemizer, MFA alignment and resampling are not part of this tool: it takes their
+results.  Entries of the current cache version are skipped unless --force, as the reference's kokoro-precompute does.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import Dict, List
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="kokoro-precompute", description=__doc__.split("\n\n")[0])
+    p.add_argument("--wavs", required=True, metavar="DIR")
+    p.add_argument("--ids", required=True, metavar="FILE.jsonl")
+    p.add_argument("--cache-dir", required=True, metavar="OUT")
+    p.add_argument("--force", action="store_true", help="recompute entries that exist")
+    p.add_argument("--no-variance", action="store_true", help="zero pitch and energy")
+    p.add_argument("--batch-size", type=int, default=32, help="utterances per device call")
+    p.add_argument("--max-seq-length", type=int, default=1800, help="mel frames kept per utterance")
+    p.add_argument("--n-mels", type=int, default=80)
+    p.add_argument("--hop-length", type=int, default=256)
+    p.add_argument("--sample-rate", type=int, default=22050)
+    return p
+
+
+def check_args(p: argparse.ArgumentParser, args) -> None:
+    for flag, got, want in (("--n-mels", args.n_mels, 80), ("--hop-length", args.hop_length, 256), ("--sample-rate", args.sample_rate, 22050)):
+        if got != want:
+            p.error(f"{flag} {got}: the feature kernels are built for {want} (the reference's default)")
+    if args.batch_size < 1:
+        p.error("--batch-size must be >= 1")
+    if args.max_seq_length < 1:
+        p.error("--max-seq-length must be >= 1")
+
+
+def read_extras(path: str) -> Dict[str, Dict]:
+    """name -> {"phoneme_durations": list | None, "text": str} of the JSON-lines file (read_ids has validated the rest)."""
+    extras = {}
+    with open(path) as f:
+        for line in f:
+            if line.strip():
+                rec = json.loads(line)
+                extras[str(rec["name"])] = {"phoneme_durations": rec.get("phoneme_durations"), "text": str(rec.get("text", ""))}
+    return extras
+
+
+def main(argv=None) -> int:
+    p = build_parser()
+    args = p.parse_args(argv)
+    check_args(p, args)
+    import torch
+    from kokoro.cli.synth import read_ids
+    from kokoro.data import features as DF
+    from kokoro_ruslan_amd.features import FeatureExtractor
+
+    names, ids, stress = read_ids(args.ids)
+    extras = read_extras(args.ids)
+    todo: List[int] = []
+    skipped = 0
+    for i, name in enumerate(names):
+        if not args.force and DF.is_current(DF.cache_path(args.cache_dir, name)):
+            skipped += 1
+        else:
+            todo.append(i)
+    computed = failed = 0
+    ext = FeatureExtractor() if todo else None
+    for s in range(0, len(todo), args.batch_size):
+        batch, waves = [], []
+        for i in todo[s:s + args.batch_size]:
+            try:
+                waves.append(DF.load_wav(os.path.join(args.wavs, names[i] + ".wav")))
+                batch.append(i)
+            except Exception as e:
+                failed += 1
+                print(f"kokoro-precompute: {names[i]}: {e}", file=sys.stderr)
+        if not batch:
+            continue
+        feats = ext.extract(waves, max_seq_length=args.max_seq_length, variance=not args.no_variance)
+        for i, ft in zip(batch, feats):
+            try:
+                x = extras[names[i]]
+                dur = torch.tensor(x["phoneme_durations"], dtype=torch.long) if x["phoneme_durations"] is not None else None
+                entry = DF.cache_entry(ft, names[i], ids[i], stress[i] if stress is not None else None, dur, x["text"])
+                DF.write_cache_entry(args.cache_dir, entry)
+                computed += 1
+            except Exception as e:
+                failed += 1
+                print(f"kokoro-precompute: {names[i]}: {e}", file=sys.stderr)
+    print(f"kokoro-precompute: {computed} computed, {skipped} skipped, {failed} failed ({len(names)} utterances) -> {args.cache_dir}")
+    return 0 if failed == 0 else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -3,7 +3,7 @@
 Reads the per-utterance `.pt` files the reference's `kokoro-precompute` writes under `{corpus}/.feature_cache/`
 (schema v7, reference data/dataset.py:849-862: mel_spec [80,T] f32, phoneme_indices/stress_indices/phoneme_durations
 [P] i64, stop_token_targets/pitch/energy [T] f32, mel_length, phoneme_length, text, audio_file, _cache_version).
-The audio front-end, MFA alignment and the phonemizer that PRODUCE these files stay on the reference (out of scope).
+This repository's `kokoro-precompute` (kokoro/data/features.py) writes the same files; MFA alignment and the phonemizer stay on the reference.
 `collate_fn` reproduces the reference's zero-padded batch dict (data/dataset.py:871-921).  The frame-budget sampler
 restates the reference's DynamicFrameBatchSampler (dataset.py:924-1147: quantile buckets, greedy packing under
 batch_size * longest <= max_frames, heavy-batch spreading) and is pinned against it by tests/golden/sampler.json.
@@ -53,7 +53,7 @@ def scan_cache(cache_dir: str) -> List[Dict]:
     d = Path(cache_dir)
     files = sorted(d.glob("*.pt"))
     if not files:
-        raise FileNotFoundError(f"no cached features (*.pt) under {d}; run the reference's kokoro-precompute")
+        raise FileNotFoundError(f"no cached features (*.pt) under {d}; run kokoro-precompute")
     index_path = d / ".kk_index.json"
     known = {}
     try:

@@ -236,6 +236,11 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_gl_init": [_P, _L, _P, _P, _P, _P, _P, _P],
     "kk_gl_iter": [_P, _P, _P, _P, _P, _I, _P, _P, _F, _P],
     "kk_gl_istft": [_P, _P, _I, _P, _P, _P, _P],
+    "kk_feat_mel_tile_frames": [],
+    "kk_feat_peak": [_P, _P, _I, _L, _P, _P],
+    "kk_feat_mel": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "kk_feat_pitch": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "kk_feat_finish": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
     "kk_losses_finalize": [_P, C.POINTER(KkLossCfg), _P, _I, _P, _P, _P, _I, _P],
     "kk_losses_bwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _P, _P],
