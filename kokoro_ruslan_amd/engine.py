@@ -1129,8 +1129,11 @@ class KokoroEngine:
         self._dgrad(dh1, self._W(prefix + ".linear1.weight"), d_y)
 
     # ------------------------------------------------------------------ variance predictor
-    def _varpred_fwd(self, key, prefix, x, col1, B, L, mask, out, site=0, p=0.0):
-        """x [B*L, H]; col1 = im2col3(x) (shared by pitch & energy predictors); out [B*L]."""
+    def _varpred_fwd(self, key, prefix, x, col1, B, L, mask, out, site=0, p=0.0, lens=None):
+        """x [B*L, H]; col1 = im2col3(x) (shared by pitch & energy predictors); out [B*L].
+        lens (int32 [B], inference only: no dropout): row b is a sequence of lens[b] positions, as the B = 1 predictor sees it (the row
+        kernels of kk_synth.hip).  Then col1 = kk_im2col3_rows_fwd(x, lens) and mask = kk_varpred_row_mask(...), which carries the
+        per-row chunk guard, so the rowdot's own is off."""
         P, Fv = self.arena.P, self.dims.var_filter
         rows, nch = B * L, -(-L // CHUNK)
         scratch = self._buf("tmp.gn_scratch", 2 * B * nch, dtype=torch.float64)
@@ -1139,12 +1142,19 @@ class KokoroEngine:
             c, y = self._buf(f"{key}.c{li}", rows, Fv), self._buf(f"{key}.y{li}", rows, Fv)
             stats = self._buf(f"{key}.st{li}", B * nch, 2)
             self._linear(inp_col, self._Wconv(f"{prefix}.conv_layers.{li}.weight", Fv, 3 * cin), P[f"{prefix}.conv_layers.{li}.bias"], c)
-            kk.call("kk_groupnorm_relu_fwd", c, P[f"{prefix}.norms.{li}.weight"], P[f"{prefix}.norms.{li}.bias"], y, stats,
-                    scratch, B, L, Fv, CHUNK, self.rng, site + li, p)
+            gw, gb = P[f"{prefix}.norms.{li}.weight"], P[f"{prefix}.norms.{li}.bias"]
+            if lens is None:
+                kk.call("kk_groupnorm_relu_fwd", c, gw, gb, y, stats, scratch, B, L, Fv, CHUNK, self.rng, site + li, p)
+            else:
+                kk.call("kk_groupnorm_relu_rows_fwd", c, gw, gb, y, stats, scratch, lens, B, L, Fv, CHUNK, self.rng, 0, 0.0)
             if li == 0:
                 inp_col, cin = self._buf(f"{key}.col2", rows, 3 * Fv, dtype=col1.dtype), Fv
-                kk.call("kk_im2col3_fwd", y, inp_col, B, L, Fv, CHUNK, _b16(inp_col))
-        kk.call("kk_rowdot_fwd", y, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, out, rows, Fv, L, CHUNK, 0)
+                if lens is None:
+                    kk.call("kk_im2col3_fwd", y, inp_col, B, L, Fv, CHUNK, _b16(inp_col))
+                else:
+                    kk.call("kk_im2col3_rows_fwd", y, inp_col, lens, B, L, Fv, CHUNK, _b16(inp_col))
+        kk.call("kk_rowdot_fwd", y, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, out, rows, Fv, L,
+                CHUNK if lens is None else 0, 0)
 
     def _varpred_bwd(self, key, prefix, dout, x, col1, B, L, mask, dx, p=0.0):
         """Accumulate the predictor's parameter grads; write dx (dL/dx) when dx is not None."""
@@ -1612,9 +1622,10 @@ class KokoroEngine:
 
     # ------------------------------------------------------------------ inference
     def _decode_step(self, ns, B, T, max_expected, memory, fm2):
-        """The launches of one decoder step at Sq = 1 up to the stop logits (generate / generate_batch add their own epilogue).  The
-        step's buffers are the caller's workspace entries under the key prefix `ns` (see generate), fetched by the same keys and shapes;
-        the cross-attention K|V are those of _cross_kv_fwd_all(..., ns=`ns` + "." or "" for "gen")."""
+        """The launches of one decoder step at Sq = 1 up to the stop logits; returns (frame_out [B, mel], stop_now [B]), which the
+        epilogue of generate / generate_batch files under frame t.  The step's state is the workspace entries under the key prefix
+        `ns` ("gen" / "syn") that _decode_state_init reset; the cross-attention K|V are those of _expand_fwd ("" for "gen", else
+        `ns` + ".")."""
         d, P, H, M, h = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dims.heads
         ddt = self.dec_dt
         BH, L1 = B * H, max_expected + 1
@@ -1658,6 +1669,108 @@ class KokoroEngine:
         self._linear(dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out)
         kk.call("kk_rowdot_fwd", dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now,
                 B, H, 1, 0, _b16(dec_out))
+        return frame_out, stop_now
+
+    def _encode_text_fwd(self, ns, ids, stress, B, Pn, text_mask):
+        """encode_text (model.py:375-388) with dropout off: embedding, the encoder layers under the key mask `text_mask`
+        (= ids == 0, written here) and encoder_norm.  Workspace keys `ns` + "enc...".  Returns the encoder output [B*Pn, H]."""
+        d, P, H, edt = self.dims, self.arena.P, self.dims.hidden, self.enc_dt
+        Ne = B * Pn
+        kk.call("kk_ids_eq_zero", ids, text_mask, Ne)
+        x = self._buf(ns + "enc.x0", Ne, H)
+        kk.call("kk_embed_fwd", ids, stress, P["text_embedding.weight"], P["stress_embedding.weight"] if stress is not None else None,
+                P["positional_encoding.pe"].view(d.max_len, H), x, B, Pn, H, float(H ** 0.5), self.rng, 1, 0.0)
+        y1 = None
+        for i in range(d.enc_layers):
+            pf, key = f"transformer_encoder_layers.{i}", f"{ns}enc{i}"
+            if y1 is None:
+                y1 = self._ln_fwd(key + ".ln1", x, pf + ".norm1", edt)
+            xm = self._buf(key + ".xm", Ne, H)
+            y2 = self._attn_fwd(key + ".sa", pf + ".self_attn", y1, None, B, Pn, Pn, True, False, text_mask, x, xm,
+                                next_ln=(key + ".ln2", pf + ".norm2", edt))
+            xo = self._buf(key + ".xo", Ne, H)
+            nxt = ((f"{ns}enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", edt) if i + 1 < d.enc_layers
+                   else (ns + "enc.norm", "encoder_norm", torch.float32))
+            y1 = self._ffn_fwd(key + ".ff", pf + ".ff", y2, xm, xo, d.enc_ff, Pn, next_ln=nxt)
+            x = xo
+        return y1
+
+    def _expand_fwd(self, ns, enc, dur, B, Pn, T, flens=None):
+        """The variance adaptor behind the durations, without targets (variance_predictor.py:338-439): repeat phoneme p of
+        each row dur[b, p] times up to T frames, predict pitch and energy, add the bucket embeddings of the clamped predictions,
+        and project the result to the cross-attention K|V of every decoder layer (_cross_kv_fwd_all under `ns`).  flens (int32
+        [B]) makes the predictors see row b as a sequence of flens[b] frames; None = the padded batch as one.  Workspace keys
+        `ns` + "lr.* / va.* / vp.* / out.*".  Returns (memory [B*T, H], fm2 = the frame mask [B, T])."""
+        d, P, H, ddt = self.dims, self.arena.P, self.dims.hidden, self.dec_dt
+        Nd = B * T
+        idx, lens, tot = (self._buf(ns + "lr.idx", B, T, dtype=torch.int64), self._buf(ns + "lr.lens", B, dtype=torch.int64),
+                          self._buf(ns + "lr.total", B, dtype=torch.int64))
+        kk.call("kk_length_regulate_index", dur, idx, lens, tot, B, Pn, T)
+        xf = self._buf(ns + "va.xf", Nd, H)
+        kk.call("kk_length_regulate_gather", enc, idx, xf, B, Pn, T, H)
+        fmask = (torch.arange(T, device=self.device)[None, :] >= lens[:, None]).to(torch.uint8).contiguous()
+        col_f = self._buf(ns + "vp.col_frames", Nd, 3 * H, dtype=ddt)
+        if flens is None:
+            kk.call("kk_im2col3_fwd", xf, col_f, B, T, H, CHUNK, _b16(col_f))
+        else:
+            pad, fmask = fmask, self._buf(ns + "vp.frame_mask", B, T, dtype=torch.uint8)
+            kk.call("kk_varpred_row_mask", pad, flens, fmask, B, T, CHUNK)
+            kk.call("kk_im2col3_rows_fwd", xf, col_f, flens, B, T, H, CHUNK, _b16(col_f))
+        pitch, energy = self._buf(ns + "out.pitch", B, T), self._buf(ns + "out.energy", B, T)
+        self._varpred_fwd(ns + "vp.pitch", f"{VA}.pitch_predictor", xf, col_f, B, T, fmask, pitch, lens=flens)
+        self._varpred_fwd(ns + "vp.energy", f"{VA}.energy_predictor", xf, col_f, B, T, fmask, energy, lens=flens)
+        memory, fm2 = self._buf(ns + "va.memory", Nd, H, dtype=ddt), self._buf(ns + "va.fmask", B, T, dtype=torch.uint8)
+        pidx, eidx = self._buf(ns + "va.pidx", B, T, dtype=torch.int32), self._buf(ns + "va.eidx", B, T, dtype=torch.int32)
+        kk.call("kk_bucket_embed_add_fwd", xf, pitch.clamp(0.0, 1.0), energy.clamp(0.0, 1.0), P[f"{VA}.pitch_bins"],
+                P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
+                pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
+        self._cross_kv_fwd_all(memory, Nd, T, ddt, ns=ns)          # cross-attention K|V of every layer, normalised
+        return memory, fm2
+
+    def _generation_bounds(self, expected, max_len, min_len_ratio, min_len_floor, max_len_ratio, max_len_cap, who=""):
+        """(min, expected, max) frames of an utterance of `expected` predicted frames (model.py:741-750); `who` opens the message
+        of the error."""
+        lo = max(min_len_floor, int(expected * min_len_ratio))
+        hi = min(max_len, max(expected + 80, int(expected * max_len_ratio)), max_len_cap)
+        if hi <= lo:
+            hi = min(max_len, lo + 1)
+        if hi > self.dims.max_len:
+            raise ValueError(f"{who}generation bound {hi} exceeds the positional table ({self.dims.max_len})")
+        return lo, expected, hi
+
+    def _decode_state_init(self, ns, B, max_expected):
+        """Reset what _decode_step(ns, ...) carries from frame to frame: empty K / V caches, the all-zero first input frame,
+        frame counter 0, every cache key masked.  Returns (mel_out [B, max_expected + 1, mel], stop_logit [max_expected, B], t_dev)."""
+        d, ddt = self.dims, self.dec_dt
+        for i in range(d.dec_layers):                              # (rows >= t are masked, but 0 * garbage must stay 0)
+            self._buf(f"{ns}.dec{i}.kcache", max_expected, B * d.hidden, dtype=ddt).zero_()
+            self._buf(f"{ns}.dec{i}.vcache", max_expected, B * d.hidden, dtype=ddt).zero_()
+        mel_out = self._buf(f"{ns}.mel", B, max_expected + 1, d.mel)           # row 0 = the all-zero first input
+        mel_out.zero_()
+        t_dev = self._buf(f"{ns}.t", 1, dtype=torch.int32)
+        t_dev.zero_()
+        self._buf(f"{ns}.kmask", 1, max_expected, dtype=torch.uint8).fill_(1)
+        return mel_out, self._buf(f"{ns}.stop", max_expected, B), t_dev
+
+    def _decode_loop(self, step, stop, max_expected, check_every, decode_graph):
+        """Run step() for up to max_expected frames; every `check_every` frames and after the last the host asks stop(t), t = the
+        frame just decoded (a host sync), and leaves when it says so.  The step's launches take the frame index from device
+        memory (kk_decode_*): their arguments are the same for every frame, so with decode_graph ONE captured hipGraph of the
+        step serves the whole utterance (~100 launches per frame are host-bound when issued one by one)."""
+        step_graph = None
+        for t in range(max_expected):
+            if step_graph is not None:
+                step_graph.replay()
+            else:
+                step()                                     # frame 0 eagerly: it sizes the workspaces a capture may not allocate
+                if decode_graph and max_expected > 1:
+                    with self.capture_lock:
+                        torch.cuda.synchronize()
+                        step_graph = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(step_graph, capture_error_mode="thread_local"):
+                            step()
+            if ((t + 1) % check_every == 0 or t + 1 == max_expected) and stop(t):
+                break
 
     @torch.no_grad()
     def generate(self, ids: torch.Tensor, stress: Optional[torch.Tensor] = None, max_len: int = 4000,
@@ -1677,151 +1790,57 @@ class KokoroEngine:
         incremental path, transformers.py:276).  The stop decision needs the host; the reference syncs every frame,
         here the frames of `check_every` steps are decoded before the host looks (frames past the stop are dropped, so
         the result is the same).  decode_graph: frames 1.. are replays of ONE hipGraph of the step, captured after frame 0 ran
-        eagerly (the step's launches index everything by a device-side frame counter); False issues the same launches one by one."""
-        d, P, H, M, h = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dims.heads
-        VA = "duration_adaptor.variance_adaptor"
+        eagerly (_decode_loop); False issues the same launches one by one.
+
+        The stages are generate_batch's (_encode_text_fwd, _varpred_fwd, _expand_fwd, _generation_bounds, _decode_state_init,
+        _decode_step, _decode_loop).  Up to the decode state they run on the train step's workspace keys (no prefix), so an
+        engine that trains and synthesises shares those buffers; the decode state is under "gen."."""
+        d, H, M = self.dims, self.dims.hidden, self.dims.mel
         ids = ids.to(self.device, torch.int64).contiguous()
         stress = stress.to(self.device, torch.int64).contiguous() if stress is not None else None
         B, Pn = ids.shape
-        Ne = B * Pn
-        edt, ddt = self.enc_dt, self.dec_dt
-        pe = P["positional_encoding.pe"].view(d.max_len, H)
         saved_drop, self.train_dropout = self.train_dropout, False
         try:
-            # ---- encode_text (model.py:375-388) ----
             text_mask = self._buf("gen.text_mask", B, Pn, dtype=torch.uint8)
-            kk.call("kk_ids_eq_zero", ids, text_mask, Ne)
-            x = self._buf("enc.x0", Ne, H)
-            kk.call("kk_embed_fwd", ids, stress, P["text_embedding.weight"], P["stress_embedding.weight"] if stress is not None else None,
-                    pe, x, B, Pn, H, float(H ** 0.5), self.rng, 1, 0.0)
-            y1 = None
-            for i in range(d.enc_layers):
-                pf, key = f"transformer_encoder_layers.{i}", f"enc{i}"
-                if y1 is None:
-                    y1 = self._ln_fwd(key + ".ln1", x, pf + ".norm1", edt)
-                xm = self._buf(key + ".xm", Ne, H)
-                y2 = self._attn_fwd(key + ".sa", pf + ".self_attn", y1, None, B, Pn, Pn, True, False, text_mask, x, xm,
-                                    next_ln=(key + ".ln2", pf + ".norm2", edt))
-                xo = self._buf(key + ".xo", Ne, H)
-                nxt = ((f"enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", edt) if i + 1 < d.enc_layers
-                       else ("enc.norm", "encoder_norm", torch.float32))
-                y1 = self._ffn_fwd(key + ".ff", pf + ".ff", y2, xm, xo, d.enc_ff, Pn, next_ln=nxt)
-                x = xo
-            enc = y1
-            # ---- variance adaptor without targets ----
+            enc = self._encode_text_fwd("", ids, stress, B, Pn, text_mask)
+            # ---- duration predictor ----
             log_dur = self._buf("out.log_dur", B, Pn)
-            col_e = self._buf("vp.col_enc", Ne, 3 * H, dtype=edt)
+            col_e = self._buf("vp.col_enc", B * Pn, 3 * H, dtype=self.enc_dt)
             kk.call("kk_im2col3_fwd", enc, col_e, B, Pn, H, CHUNK, _b16(col_e))
             self._varpred_fwd("vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, text_mask, log_dur)
             dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
-            expected = max(int(dur.sum(dim=1).max()), 3)           # (host sync: the expanded length sizes everything below)
-            T = expected
+            expected = T = max(int(dur.sum(dim=1).max()), 3)       # (host sync: the expanded length sizes everything below)
             if T > d.max_len:
                 raise ValueError(f"predicted length {T} exceeds the positional table ({d.max_len})")
-            Nd = B * T
-            idx, lens, tot = (self._buf("lr.idx", B, T, dtype=torch.int64), self._buf("lr.lens", B, dtype=torch.int64),
-                              self._buf("lr.total", B, dtype=torch.int64))
-            kk.call("kk_length_regulate_index", dur, idx, lens, tot, B, Pn, T)
-            xf = self._buf("va.xf", Nd, H)
-            kk.call("kk_length_regulate_gather", enc, idx, xf, B, Pn, T, H)
-            fmask = (torch.arange(T, device=self.device)[None, :] >= lens[:, None]).to(torch.uint8).contiguous()
-            col_f = self._buf("vp.col_frames", Nd, 3 * H, dtype=ddt)
-            kk.call("kk_im2col3_fwd", xf, col_f, B, T, H, CHUNK, _b16(col_f))
-            pitch, energy = self._buf("out.pitch", B, T), self._buf("out.energy", B, T)
-            self._varpred_fwd("vp.pitch", f"{VA}.pitch_predictor", xf, col_f, B, T, fmask, pitch)
-            self._varpred_fwd("vp.energy", f"{VA}.energy_predictor", xf, col_f, B, T, fmask, energy)
-            memory, fm2 = self._buf("va.memory", Nd, H, dtype=ddt), self._buf("va.fmask", B, T, dtype=torch.uint8)
-            pidx, eidx = self._buf("va.pidx", B, T, dtype=torch.int32), self._buf("va.eidx", B, T, dtype=torch.int32)
-            kk.call("kk_bucket_embed_add_fwd", xf, pitch.clamp(0.0, 1.0), energy.clamp(0.0, 1.0), P[f"{VA}.pitch_bins"],
-                    P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
-                    pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
-            self._cross_kv_fwd_all(memory, Nd, T, ddt)             # cross-attention K|V of every layer, normalised
-            # ---- generation bounds (model.py:741-750) ----
-            min_expected = max(min_len_floor, int(expected * min_len_ratio))
-            max_expected = min(max_len, max(expected + 80, int(expected * max_len_ratio)), max_len_cap)
-            if max_expected <= min_expected:
-                max_expected = min(max_len, min_expected + 1)
-            if max_expected > d.max_len:
-                raise ValueError(f"generation bound {max_expected} exceeds the positional table ({d.max_len})")
-            cos, sin = self._rope_tables(d.max_len)                                # (the whole tables: the step indexes them by t)
-            BH, L1 = B * H, max_expected + 1
-            Kc = [self._buf(f"gen.dec{i}.kcache", max_expected, BH, dtype=ddt) for i in range(d.dec_layers)]
-            Vc = [self._buf(f"gen.dec{i}.vcache", max_expected, BH, dtype=ddt) for i in range(d.dec_layers)]
-            for c_ in Kc + Vc:
-                c_.zero_()                                                         # (rows >= t are masked, but 0 * garbage must stay 0)
-            mel_out = self._buf("gen.mel", B, L1, M)                               # row 0 = the all-zero first input
-            mel_out.zero_()
-            stop_logit = self._buf("gen.stop", max_expected, B)
-            y = self._buf("gen.y", B, H)
-            # The step's launches take the frame index from device memory (kk_decode_*): their arguments are the same for every
-            # frame, so ONE captured hipGraph of the step serves the whole utterance (decode_graph; ~100 launches per frame are
-            # host-bound when issued one by one).  The self-attention runs over the whole cache under a key mask that opens key t.
-            t_dev = self._buf("gen.t", 1, dtype=torch.int32)
-            t_dev.zero_()
-            kmask = self._buf("gen.kmask", 1, max_expected, dtype=torch.uint8)
-            kmask.fill_(1)
-            frame_in, frame_out, stop_now = self._buf("gen.frame_in", B, M), self._buf("gen.frame_out", B, M), self._buf("gen.stop_now", B)
-            pe_row, cos_row, sin_row = self._buf("gen.pe_row", 1, H), self._buf("gen.cos_row", 1, 64), self._buf("gen.sin_row", 1, 64)
+            memory, fm2 = self._expand_fwd("", enc, dur, B, Pn, T)
+            min_expected, _, max_expected = self._generation_bounds(expected, max_len, min_len_ratio, min_len_floor, max_len_ratio,
+                                                                    max_len_cap)
+            mel_out, stop_logit, t_dev = self._decode_state_init("gen", B, max_expected)
 
-            def decode_step():
-                self._decode_step("gen", B, T, max_expected, memory, fm2)
-                kk.call("kk_decode_epilogue", frame_out, stop_now, mel_out, stop_logit, t_dev, B, L1, M)
+            def step():
+                frame_out, stop_now = self._decode_step("gen", B, T, max_expected, memory, fm2)
+                kk.call("kk_decode_epilogue", frame_out, stop_now, mel_out, stop_logit, t_dev, B, max_expected + 1, M)
 
-            frames = max_expected
-            done = 0
-            step_graph = None
-            for t in range(max_expected):
-                if step_graph is not None:
-                    step_graph.replay()
-                else:
-                    decode_step()                          # frame 0 eagerly: it sizes the workspaces a capture may not allocate
-                    if decode_graph and max_expected > 1:
-                        with self.capture_lock:
-                            torch.cuda.synchronize()
-                            step_graph = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(step_graph, capture_error_mode="thread_local"):
-                                decode_step()
-                if (t + 1) % check_every == 0 or t + 1 == max_expected:
-                    sp = torch.sigmoid(stop_logit[done:t + 1]).mean(dim=1).cpu().tolist()
-                    mel_host = mel_out[:, 1:t + 2].float().cpu() if t + 1 >= 30 else None
-                    stop_at = None
-                    for tt in range(done, t + 1):
-                        if tt < min_expected:
-                            continue
-                        thr = stop_threshold if tt < expected else min(stop_threshold, post_expected_stop_threshold)
-                        if sp[tt - done] > thr:
-                            stop_at = tt
-                            break
-                        if tt + 1 >= 30 and float(mel_host[:, tt - 29:tt + 1].mean()) < -9.5:
-                            stop_at = tt
-                            break
-                    done = t + 1
-                    if stop_at is not None:
-                        frames = stop_at + 1
-                        break
+            frames, done = max_expected, 0
+
+            def stop(t):                                   # generator.py:67-88 over the frames [done, t] the host has not seen yet
+                nonlocal frames, done
+                sp = torch.sigmoid(stop_logit[done:t + 1]).mean(dim=1).cpu().tolist()
+                mel_host = mel_out[:, 1:t + 2].float().cpu() if t + 1 >= 30 else None
+                first, done = done, t + 1
+                for tt in range(first, t + 1):
+                    if tt < min_expected:
+                        continue
+                    thr = stop_threshold if tt < expected else min(stop_threshold, post_expected_stop_threshold)
+                    if sp[tt - first] > thr or (tt + 1 >= 30 and float(mel_host[:, tt - 29:tt + 1].mean()) < -9.5):
+                        frames = tt + 1
+                        return True
+                return False
+
+            self._decode_loop(step, stop, max_expected, check_every, decode_graph)
             return mel_out[:, 1:frames + 1].clamp(min=-11.5, max=2.0).clone()
         finally:
             self.train_dropout = saved_drop
-
-    # ------------------------------------------------------------------ batched inference: each row as if alone
-    def _varpred_rows_fwd(self, key, prefix, x, col1, B, L, lens, mask, out):
-        """_varpred_fwd (dropout off) with the row kernels of kk_synth.hip: row b is a sequence of lens[b] positions (int32), as the
-        B = 1 predictor sees it.  col1 = kk_im2col3_rows_fwd(x, lens); mask = kk_varpred_row_mask(...) (the rowdot's own chunk
-        guard is off: the mask carries the per-row one)."""
-        P, Fv = self.arena.P, self.dims.var_filter
-        rows, nch = B * L, -(-L // CHUNK)
-        scratch = self._buf("tmp.gn_scratch", 2 * B * nch, dtype=torch.float64)
-        inp_col, cin = col1, x.shape[1]
-        for li in range(2):
-            c, y = self._buf(f"{key}.c{li}", rows, Fv), self._buf(f"{key}.y{li}", rows, Fv)
-            stats = self._buf(f"{key}.st{li}", B * nch, 2)
-            self._linear(inp_col, self._Wconv(f"{prefix}.conv_layers.{li}.weight", Fv, 3 * cin), P[f"{prefix}.conv_layers.{li}.bias"], c)
-            kk.call("kk_groupnorm_relu_rows_fwd", c, P[f"{prefix}.norms.{li}.weight"], P[f"{prefix}.norms.{li}.bias"], y, stats,
-                    scratch, lens, B, L, Fv, CHUNK, self.rng, 0, 0.0)
-            if li == 0:
-                inp_col, cin = self._buf(f"{key}.col2", rows, 3 * Fv, dtype=col1.dtype), Fv
-                kk.call("kk_im2col3_rows_fwd", y, inp_col, lens, B, L, Fv, CHUNK, _b16(inp_col))
-        kk.call("kk_rowdot_fwd", y, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, out, rows, Fv, L, 0, 0)
 
     @torch.no_grad()
     def generate_batch(self, utterances: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]] = None, *, max_len: int = 4000,
@@ -1836,12 +1855,13 @@ class KokoroEngine:
         expected_b, max_b).
 
         Row lengths are those of the single-utterance call: L_b = P_b phonemes, T_b = max(sum(dur_b), 3) frames (frames in
-        [sum(dur_b), T_b) are zero inputs that count in the predictors' convolutions and GroupNorms, as at B = 1).  The duration,
-        pitch and energy predictors run with the row kernels (_varpred_rows_fwd); the encoder (key mask), length regulator, bucket
-        embeddings and cross-attention (frame mask) are row-independent already.  Each row has its own bounds (model.py:741-750)
-        and its own stop rule, applied on the device by kk_decode_epilogue_rows inside the replayed step; the host reads only the
-        count of live rows, every `check_every` frames."""
-        d, P, H, M = self.dims, self.arena.P, self.dims.hidden, self.dims.mel
+        [sum(dur_b), T_b) are zero inputs that count in the predictors' convolutions and GroupNorms, as at B = 1).  The stages are
+        generate's, on workspace keys of their own ("syn."): the duration, pitch and energy predictors are given the row lengths
+        and so run the row kernels (_varpred_fwd(lens=...), _expand_fwd(flens=...)); the encoder (key mask), length regulator,
+        bucket embeddings and cross-attention (frame mask) are row-independent already.  Each row has its own bounds
+        (_generation_bounds) and its own stop rule, applied on the device by kk_decode_epilogue_rows inside the replayed step; the
+        host reads only the count of live rows, every `check_every` frames."""
+        d, H, M = self.dims, self.dims.hidden, self.dims.mel
         B = len(utterances)
         if B == 0:
             return ([], {"durations": [], "T": [], "bounds": []}) if want_info else []
@@ -1867,39 +1887,18 @@ class KokoroEngine:
                 st_h[b, :lens_p[b]] = stress[b].reshape(-1).to("cpu", torch.int64)
         ids = ids_h.to(self.device)
         st = st_h.to(self.device) if st_h is not None else None
-        Ne = B * Pn
-        edt, ddt = self.enc_dt, self.dec_dt
-        pe = P["positional_encoding.pe"].view(d.max_len, H)
         saved_drop, self.train_dropout = self.train_dropout, False
         try:
-            # ---- encode_text (model.py:375-388): generate's launch sequence under the key mask ----
             text_mask = self._buf("syn.text_mask", B, Pn, dtype=torch.uint8)
-            kk.call("kk_ids_eq_zero", ids, text_mask, Ne)
-            x = self._buf("syn.enc.x0", Ne, H)
-            kk.call("kk_embed_fwd", ids, st, P["text_embedding.weight"], P["stress_embedding.weight"] if st is not None else None,
-                    pe, x, B, Pn, H, float(H ** 0.5), self.rng, 1, 0.0)
-            y1 = None
-            for i in range(d.enc_layers):
-                pf, key = f"transformer_encoder_layers.{i}", f"syn.enc{i}"
-                if y1 is None:
-                    y1 = self._ln_fwd(key + ".ln1", x, pf + ".norm1", edt)
-                xm = self._buf(key + ".xm", Ne, H)
-                y2 = self._attn_fwd(key + ".sa", pf + ".self_attn", y1, None, B, Pn, Pn, True, False, text_mask, x, xm,
-                                    next_ln=(key + ".ln2", pf + ".norm2", edt))
-                xo = self._buf(key + ".xo", Ne, H)
-                nxt = ((f"syn.enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", edt) if i + 1 < d.enc_layers
-                       else ("syn.enc.norm", "encoder_norm", torch.float32))
-                y1 = self._ffn_fwd(key + ".ff", pf + ".ff", y2, xm, xo, d.enc_ff, Pn, next_ln=nxt)
-                x = xo
-            enc = y1
+            enc = self._encode_text_fwd("syn.", ids, st, B, Pn, text_mask)
             # ---- duration predictor, each row over its own P_b phonemes ----
             plens = torch.tensor(lens_p, dtype=torch.int32).to(self.device)
-            log_dur = self._buf("syn.log_dur", B, Pn)
-            col_e = self._buf("syn.vp.col_enc", Ne, 3 * H, dtype=edt)
+            log_dur = self._buf("syn.out.log_dur", B, Pn)
+            col_e = self._buf("syn.vp.col_enc", B * Pn, 3 * H, dtype=self.enc_dt)
             kk.call("kk_im2col3_rows_fwd", enc, col_e, plens, B, Pn, H, CHUNK, _b16(col_e))
             dmask = self._buf("syn.vp.dur_mask", B, Pn, dtype=torch.uint8)
             kk.call("kk_varpred_row_mask", text_mask, plens, dmask, B, Pn, CHUNK)
-            self._varpred_rows_fwd("syn.vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, plens, dmask, log_dur)
+            self._varpred_fwd("syn.vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, dmask, log_dur, lens=plens)
             dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
             sums = dur.sum(dim=1).cpu().tolist()                   # (host sync: the row lengths size everything below)
             Tb = [max(int(s_), 3) for s_ in sums]
@@ -1907,77 +1906,28 @@ class KokoroEngine:
                 if tb > d.max_len:
                     raise ValueError(f"utterance {b}: predicted length {tb} exceeds the positional table ({d.max_len})")
             T = max(Tb)
-            Nd = B * T
-            flens = torch.tensor(Tb, dtype=torch.int32).to(self.device)
-            idx, lens, tot = (self._buf("syn.lr.idx", B, T, dtype=torch.int64), self._buf("syn.lr.lens", B, dtype=torch.int64),
-                              self._buf("syn.lr.total", B, dtype=torch.int64))
-            kk.call("kk_length_regulate_index", dur, idx, lens, tot, B, Pn, T)
-            xf = self._buf("syn.va.xf", Nd, H)
-            kk.call("kk_length_regulate_gather", enc, idx, xf, B, Pn, T, H)
-            fmask = (torch.arange(T, device=self.device)[None, :] >= lens[:, None]).to(torch.uint8).contiguous()
-            vmask = self._buf("syn.vp.frame_mask", B, T, dtype=torch.uint8)
-            kk.call("kk_varpred_row_mask", fmask, flens, vmask, B, T, CHUNK)
-            col_f = self._buf("syn.vp.col_frames", Nd, 3 * H, dtype=ddt)
-            kk.call("kk_im2col3_rows_fwd", xf, col_f, flens, B, T, H, CHUNK, _b16(col_f))
-            pitch, energy = self._buf("syn.pitch", B, T), self._buf("syn.energy", B, T)
-            self._varpred_rows_fwd("syn.vp.pitch", f"{VA}.pitch_predictor", xf, col_f, B, T, flens, vmask, pitch)
-            self._varpred_rows_fwd("syn.vp.energy", f"{VA}.energy_predictor", xf, col_f, B, T, flens, vmask, energy)
-            memory, fm2 = self._buf("syn.va.memory", Nd, H, dtype=ddt), self._buf("syn.va.fmask", B, T, dtype=torch.uint8)
-            pidx, eidx = self._buf("syn.va.pidx", B, T, dtype=torch.int32), self._buf("syn.va.eidx", B, T, dtype=torch.int32)
-            kk.call("kk_bucket_embed_add_fwd", xf, pitch.clamp(0.0, 1.0), energy.clamp(0.0, 1.0), P[f"{VA}.pitch_bins"],
-                    P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
-                    pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
-            self._cross_kv_fwd_all(memory, Nd, T, ddt, ns="syn.")
-            # ---- generation bounds of each row (model.py:741-750) ----
+            memory, fm2 = self._expand_fwd("syn.", enc, dur, B, Pn, T, flens=torch.tensor(Tb, dtype=torch.int32).to(self.device))
             bounds = []
             for b, expected in enumerate(Tb):
-                lo = max(min_len_floor, int(expected * min_len_ratio))
-                hi = min(max_len, max(expected + 80, int(expected * max_len_ratio)), max_len_cap)
-                if hi <= lo:
-                    hi = min(max_len, lo + 1)
-                if hi > d.max_len:
-                    raise ValueError(f"utterance {b}: generation bound {hi} exceeds the positional table ({d.max_len})")
-                if hi < 1:
-                    raise ValueError(f"utterance {b}: generation bound {hi} leaves no frame")
-                bounds.append((lo, expected, hi))
+                bounds.append(self._generation_bounds(expected, max_len, min_len_ratio, min_len_floor, max_len_ratio, max_len_cap,
+                                                      who=f"utterance {b}: "))
+                if bounds[b][2] < 1:       # (max_len < 1; generate returns an empty mel there)
+                    raise ValueError(f"utterance {b}: generation bound {bounds[b][2]} leaves no frame")
             max_expected = max(hi for _, _, hi in bounds)
             rb = torch.tensor([[r[k] for r in bounds] for k in range(3)], dtype=torch.int32).to(self.device)   # [3, B]: min | expected | max
-            BH, L1 = B * H, max_expected + 1
-            for i in range(d.dec_layers):
-                self._buf(f"syn.dec{i}.kcache", max_expected, BH, dtype=ddt).zero_()
-                self._buf(f"syn.dec{i}.vcache", max_expected, BH, dtype=ddt).zero_()
-            mel_out = self._buf("syn.mel", B, L1, M)                               # row 0 = the all-zero first input
-            mel_out.zero_()
-            stop_logit = self._buf("syn.stop", max_expected, B)
-            t_dev = self._buf("syn.t", 1, dtype=torch.int32)
-            t_dev.zero_()
-            self._buf("syn.kmask", 1, max_expected, dtype=torch.uint8).fill_(1)
+            mel_out, stop_logit, t_dev = self._decode_state_init("syn", B, max_expected)
             done, frames_d = self._buf("syn.done", B, dtype=torch.uint8), self._buf("syn.frames", B, dtype=torch.int32)
             live = self._buf("syn.live", 1, dtype=torch.int32)
             done.zero_()
             frames_d.zero_()
             live.fill_(B)
-            frame_out, stop_now = self._buf("syn.frame_out", B, M), self._buf("syn.stop_now", B)
 
-            def decode_step():
-                self._decode_step("syn", B, T, max_expected, memory, fm2)
+            def step():
+                frame_out, stop_now = self._decode_step("syn", B, T, max_expected, memory, fm2)
                 kk.call("kk_decode_epilogue_rows", frame_out, stop_now, mel_out, stop_logit, t_dev, done, frames_d, live, rb[0], rb[1],
-                        rb[2], B, L1, M, float(stop_threshold), float(post_expected_stop_threshold))
+                        rb[2], B, max_expected + 1, M, float(stop_threshold), float(post_expected_stop_threshold))
 
-            step_graph = None
-            for t in range(max_expected):
-                if step_graph is not None:
-                    step_graph.replay()
-                else:
-                    decode_step()                          # frame 0 eagerly: it sizes the workspaces a capture may not allocate
-                    if decode_graph and max_expected > 1:
-                        with self.capture_lock:
-                            torch.cuda.synchronize()
-                            step_graph = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(step_graph, capture_error_mode="thread_local"):
-                                decode_step()
-                if ((t + 1) % check_every == 0 or t + 1 == max_expected) and int(live.item()) == 0:
-                    break
+            self._decode_loop(step, lambda t: int(live.item()) == 0, max_expected, check_every, decode_graph)
             nf = frames_d.cpu().tolist()
             mels = [mel_out[b, 1:nf[b] + 1].clamp(min=-11.5, max=2.0).clone() for b in range(B)]
             if want_info:
