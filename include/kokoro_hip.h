@@ -203,7 +203,8 @@ int kk_attn_fwd_rb(const float *Q, const float *K, const float *V, float *O, flo
  * hn_q's partials differ by the order of the sum over key units.  ws == NULL, a workspace that is too small or a launch the two-pass
  * kernels do not serve (fp32 storage, one key tile, causal with Sq != Sk, unaligned operands): kk_attn_bwd runs.
  * kk_attn_bwd_two_pass(): whether the two passes are the faster form of a shape (the extra 2 bytes per score against the second
- * softmax) — the caller's policy for handing over a workspace; 0 for every shape beside the present kk_attn_bwd kernels. */
+ * softmax) — the caller's policy for handing over a workspace.  0 for every shape: at their best case, full attention at 1024 x 1024,
+ * the two passes take 128 us and kk_attn_bwd's one launch 118 us. */
 int64_t kk_attn_bwd_ws_bytes(int B, int heads, int Sq, int Sk);
 int kk_attn_bwd_two_pass(int B, int heads, int Sq, int Sk, int causal);
 int kk_attn_bwd_ws(const float *Q, const float *K, const float *V, const float *dO, const float *LSE, const float *Delta,

@@ -47,7 +47,7 @@ struct AttnArgs {
     int wt;                              // write-through stores of the [rows, 64] outputs (kk_common.h: kk_write_through(B * S))
     int dbg;                             // timing probes (KK_ATTN_DBG; results are wrong when set)
     int short_first;                     // attn_bwd_pair3: the dK/dV half of a causal launch hands out its SHORT blocks first (see there)
-    void *dS;                            // kk_attn_bwd_ws: bf16 dS tiles, written by the dK/dV kernel, read by the dQ pass (kk_attn_bwd_dkv2.inc)
+    void *dS;                            // kk_attn_bwd_ws: bf16 dS tiles, written by the dK/dV kernel, read by the dQ pass (kk_attn_bwd_dkv3.inc)
     // Packed keep decisions of the probability dropout (kk_attn_fwd_kb / kk_attn_bwd_kb): one bit per score, written by the
     // third-generation forward as the 16 ballots of every 32 x 32 unit it computes, read by the third-generation backward instead of
     // re-hashing — the hash was ~40 % of the backward's vector instructions.  Unit (qu, ku) of (b, head): 128 bytes at
@@ -1881,7 +1881,7 @@ template <int NT = 512, typename HN> __device__ __forceinline__ void hn_dma_inpu
 // that serves both the row fragments of S = K.Q^T and the transpose reads of dQ^T += K^T.dS^T), Q / dO / O rows by DMA (Delta
 // from the fragments), the scores and dP of unit u+1 issued before the exponentials of unit u, the head-norm epilogue's
 // operands prefetched into the prologue's LDS while the loop runs, 16-byte coalesced stores.
-// (body of the dQ kernel: kk_attn_bwd_dq2.inc, included into attn_bwd_dq2_kernel and attn_bwd_pair2_kernel below)
+// (body of the dQ kernel: kk_attn_bwd_dq2.inc, included into attn_bwd_dq2_kernel below; as one wave group: kk_attn_bwd_dq3.inc)
 
 // ------------------------------------------------------------------ backward: dK, dV
 // A lane owns a key; the workgroup sweeps the query tiles.  G = 2: two wave groups take alternate query tiles of the
@@ -2060,47 +2060,20 @@ __global__ __launch_bounds__(256 * G) void attn_bwd_dkv_kernel(AttnArgs a) {
     hn_colsum(colred, a.hn[1].partials);
 }
 
-// ------------------------------------------------------------------ backward: dK, dV, second generation (bf16 storage)
-// attn_bwd_dkv_kernel<true, true, 2>'s arithmetic; Q and dO tiles reach LDS once each by DMA, in the image that serves both
-// the row fragments (S^T = Q.K^T, dP^T = dO.V^T) and the transpose reads (dV^T += dO^T.P, dK^T += Q^T.dS) — the first
-// generation staged four tiles (two of them transposed in registers) per step; lse / Delta rows by DMA; K and V rows, the
-// head-norm epilogues' operands and the outputs as in attn_bwd_dq2_kernel.
-// (body of the dK/dV kernel: kk_attn_bwd_dkv2.inc, included into attn_bwd_dkv2_kernel and attn_bwd_pair2_kernel below)
-
+// ------------------------------------------------------------------ backward: the DMA-staged kernels (bf16 storage)
 // The bodies live in .inc files because they must name a by-value KERNEL parameter: handed to a device function by reference
 // (or read through a pointer to the kernarg segment) the same code spills 5-11 vector registers, and a spill is fatal beside
 // LDS-DMA (scratch reloads queue behind the tile DMAs).
+// Second generation, two wave groups: the dQ kernel that also writes Delta (kk_attn_bwd_dq given O).
 __global__ __launch_bounds__(512) void attn_bwd_dq2_kernel(AttnArgs a) {
 #include "kk_attn_bwd_dq2.inc"
 }
-#ifdef KK_TUNING_HOOKS                                       // (second-generation dK/dV and pair kernels: A/B arms of the tools flavour, KK_ATTN_BWD3=0)
-__global__ __launch_bounds__(512) void attn_bwd_dkv2_kernel(AttnArgs a) {
-#include "kk_attn_bwd_dkv2.inc"
-}
-#endif
-// dQ and dK/dV of one attention in ONE launch (grid z = 0: the dQ workgroups, z = 1: the dK/dV workgroups; Delta is an INPUT of
-// both, see kk_gemm_dgrad_delta).  The two kernels are independent once Delta exists, each keeps one workgroup per CU (148 KB of
-// LDS), and a causal launch is lopsided: dQ blocks near the end of the sequence see the most keys, dK/dV blocks near its start the
-// most queries.  Dispatched in this order (x, y, then z; long blocks first inside each half) the CUs that finish a short dQ block
-// pick up the long dK/dV blocks, so at S = 512 (one workgroup per CU and kernel) the pair takes about 5 block-units instead of
-// 4 + 4, and a non-causal pair saves one launch's ramp and tail.
-#ifdef KK_TUNING_HOOKS
-__global__ __launch_bounds__(512) void attn_bwd_pair2_kernel(AttnArgs a_dq, AttnArgs a_dkv) {
-    if (blockIdx.z == 0) {
-#define a a_dq
-#include "kk_attn_bwd_dq2.inc"
-#undef a
-    } else {
-#define a a_dkv
-#include "kk_attn_bwd_dkv2.inc"
-#undef a
-    }
-}
-#endif
 
 // ------------------------------------------------------------------ backward, third generation: one wave group, two workgroups per CU
 // The second-generation bodies as ONE 256-thread group each (kk_attn_bwd_dq3.inc / kk_attn_bwd_dkv3.inc): <= 70 KB of LDS, so two
-// workgroups share a CU.  The waves per SIMD stay two (256 registers: the dK/dV half holds 64 accumulator registers per wave,
+// workgroups share a CU.  The dK/dV body is attn_bwd_dkv_kernel<true, true, 2>'s arithmetic; Q and dO tiles reach LDS once each by
+// DMA, in the image that serves both the row fragments (S^T = Q.K^T, dP^T = dO.V^T) and the transpose reads (dV^T += dO^T.P,
+// dK^T += Q^T.dS); lse / Delta rows by DMA; K and V rows, the head-norm epilogues' operands and the outputs as in the dQ body.  The waves per SIMD stay two (256 registers: the dK/dV half holds 64 accumulator registers per wave,
 // DESIGN section 9) but they now belong to INDEPENDENT workgroups: no common barrier, one's prologue / epilogue under the other's
 // loop, no merge of group partials, and the 2 x 256 workgroups of an 8 x 8 x 512^2 launch are resident at once (one round).  In the
 // pair launch the dK/dV half of a causal launch hands out its SHORT blocks first: the i-th workgroup of each half land on the same
@@ -2111,6 +2084,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq3_kernel(AttnArgs a) {
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(AttnArgs a) {
 #include "kk_attn_bwd_dkv3.inc"
 }
+// dQ and dK/dV of one attention in ONE launch (grid z picks the half; Delta is an INPUT of both, see kk_gemm_dgrad_delta).  The two
+// kernels are independent once Delta exists, and a causal launch is lopsided: dQ blocks near the end of the sequence see the most
+// keys, dK/dV blocks near its start the most queries; a non-causal pair saves one launch's ramp and tail.
 // Dispatch order: the dK/dV half (z = 0) goes out FIRST.  Its workgroups are the long ones (26.5 against 17.5 us at 512 x 512, four
 // matmuls and two head-norm epilogues against three and one); dispatched last they are what a slot delayed by the side branch's
 // workgroups finishes with.  Stand-alone the order makes no difference (32.5 us either way); inside the step it is -0.5 % at 8 x 512
@@ -2155,13 +2131,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_pair3k_kernel(AttnArgs a_dq, 
 // 512-byte span of a tile per instruction, conflict free without a swizzle); the head-norm epilogue of the dQ kernel follows.
 // dS is bit-identical to what the dQ kernel computes for itself (same MFMA sums, same rounding), so dQ differs from the pair
 // launch's only by the order in which the key units are added (all of them in sequence here; two interleaved halves there).
-#ifdef KK_TUNING_HOOKS
-__global__ __launch_bounds__(512) void attn_bwd_dkv2s_kernel(AttnArgs a) {
-#define KK_DKV_STORE_DS 1
-#include "kk_attn_bwd_dkv2.inc"
-#undef KK_DKV_STORE_DS
-}
-#endif
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3s_kernel(AttnArgs a) {      // (the one-group body: what kk_attn_bwd's dK/dV half runs)
 #define KK_DKV_STORE_DS 1
 #include "kk_attn_bwd_dkv3.inc"
@@ -2300,7 +2269,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const T *__restrict__ O
 }
 
 int g_attn_groups = 2;
-static int attn_v2_mask() {              // bit 0: forward, bit 1: dQ, bit 2: dK/dV second-generation kernels
+static int attn_v2_mask() {              // bit 0: forward, bit 1: dQ, bit 2: dK/dV DMA-staged kernels (second generation and later)
     static const int v = kk_tune_env("KK_ATTN_V2", 7);
     return v;
 }
@@ -2324,14 +2293,12 @@ static int attn_pair() {                 // KK_ATTN_PAIR=0: kk_attn_bwd issues t
     static const int v = kk_tune_env("KK_ATTN_PAIR", 1);
     return v;
 }
-#ifdef KK_TUNING_HOOKS
-static int attn_gen3() {                 // KK_ATTN_BWD3: bit 0 the one-group backward kernels (two workgroups per CU), bit 1 short-first dK/dV half
+// KK_ATTN_BWD3 (tools) bit 1: the dK/dV half of a causal pair launch hands out its short blocks first (default).  Bit 0 once chose
+// between the second- and the third-generation dK/dV and pair kernels; the third generation is the only one left and the bit is ignored.
+static bool attn_short_first() {
     static const int v = kk_tune_env("KK_ATTN_BWD3", 3);
-    return v;
+    return (v & 2) != 0;
 }
-#else
-static constexpr int attn_gen3() { return 3; }        // (the product carries the third generation only; the second-generation dK/dV / pair kernels are tools arms)
-#endif
 static int g_attn_cus() {
     static const int n = [] {
         int dev = 0, v = 0;
@@ -2351,25 +2318,68 @@ static int attn_xcd_map(int causal = 0) {
     return v == 2 ? (causal ? 2 : 1) : v;
 }
 
-// Launch KERNEL<BF16, ST16, G> with G*256 threads and its dynamic LDS (buffers x groups x NT tiles; above 64 KB the
-// kernel attribute has to be raised once).
+// What every launch of one attention has in common.  An entry point adds what is its own: outputs, dO / LSE / Delta, head-norm
+// descriptors, keep, warm, dS, short_first.
+AttnArgs attn_args(const float *Q, const float *K, const float *V, int B, int heads, int Sq, int Sk, int64_t ldq, int64_t ldk, int64_t ldv,
+                   const uint8_t *key_mask, int causal, float scale, const uint32_t *seed, uint32_t site, float p_drop) {
+    AttnArgs a = {};
+    a.Q = Q; a.K = K; a.V = V; a.key_mask = key_mask;
+    a.B = B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.causal = causal;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.scale = scale;
+    a.seed = p_drop > 0.f ? seed : nullptr; a.site = site; a.p_drop = p_drop;
+    a.xcd_map = attn_xcd_map(causal); a.dbg = attn_dbg(); a.wt = kk_write_through((int64_t)B * std::max(Sq, Sk));
+    return a;
+}
+
+// Which backward launches take the DMA-staged bf16 kernels (dq2 / dq3, dkv3, pair3 / pair3k, dkv3s + dqpass); everything else runs the
+// first-generation templates.  One row per route, one column per condition; "-" = the route does not ask.
+//
+//                  KK_ATTN_V2  more than one 64-row  Sk <=  16-byte aligned   head-norm    32-bit byte     the route's own
+//                  bits        tile of ...           4096                     descriptors  offsets of
+//   kk_attn_bwd_dq      2      keys, or small        yes    Q K V dO dQ (O)   q            K / V           -
+//   kk_attn_bwd_dkv     4      queries, or small     -      Q K V dO dK dV    kv           Q / dO          -
+//   kk_attn_bwd (pair)  2 | 4  both, or small        yes    all seven         q and kv     both            KK_ATTN_PAIR, cdiv(Sq, 128) == cdiv(Sk, 128)
+//   kk_attn_bwd_ws      2 | 4  both (small: no)      yes    all seven         q and kv     both            workspace, !causal || Sq == Sk
+//
+// All four: bf16 storage with bf16 math, g_attn_groups == 2.  "small" = attn_v2_small (33..64 rows: one tile, second wave group idle).
+// The dK/dV kernels address K, V and their outputs block by block through 64-bit pointers and loop over queries, which is why that
+// route alone has no Sk cap and bounds Q / dO instead.
+static bool dma_storage(int io_bf16, int math, int v2_bits) { return io_bf16 && math == KK_MATH_BF16 && (attn_v2_mask() & v2_bits) == v2_bits; }
+static bool dma_tiles(bool more_than_one, int Sq, int Sk) { return g_attn_groups == 2 && (more_than_one || attn_v2_small(Sq, Sk)); }
+static bool al16_all(std::initializer_list<const void *> ps) {              // (a null pointer counts as aligned: the optional O)
+    for (const void *p : ps)
+        if (!al16(p)) return false;
+    return true;
+}
+static bool dma_hn_q(const KkAttnHeadNorm *hn) { return !hn || (al16(hn->raw) && (!hn->rope || (al16(hn->cos_t) && al16(hn->sin_t)))); }
+static bool dma_hn_kv(const KkAttnHeadNorm *hn) { return !hn || (dma_hn_q(&hn[0]) && al16(hn[1].raw) && !hn[1].rope); }      // (no rope on V)
+static bool dma_bytes(int S, int64_t ld0, int64_t ld1) { return (int64_t)S * std::max(ld0, ld1) * 2 < (1ll << 31); }
+// (what the pair launch and the two passes share: both kernels' conditions apart from the tile gate)
+static bool dma_both(int io_bf16, int math, int Sq, int Sk, const void *Q, const void *K, const void *V, const void *dO, const void *dQ, const void *dK,
+                     const void *dV, int64_t ldq, int64_t ldk, int64_t ldv, int64_t lddo, const KkAttnHeadNorm *hn_q, const KkAttnHeadNorm *hn_kv) {
+    return dma_storage(io_bf16, math, 6) && Sk <= 4096 && al16_all({Q, K, V, dO, dQ, dK, dV}) && dma_hn_q(hn_q) && dma_hn_kv(hn_kv) &&
+           dma_bytes(Sk, ldk, ldv) && dma_bytes(Sq, ldq, lddo);
+}
+
+// Above 64 KB of dynamic LDS a kernel's attribute has to be raised, once per kernel and thread.
+// (one table: 64 slots for the ~20 kernels with more than 64 KB of dynamic LDS; a full table is an error, not a silent
+//  hipFuncSetAttribute per launch — ADVICE r4)
+int attn_raise_lds(const void *kernel, size_t lds, const char *who) {
+    if (lds <= 64 * 1024) return 0;
+    static thread_local const void *raised[64];
+    for (const void *p : raised)
+        if (p == kernel) return 0;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return kk_fail((int)e, "%s: cannot reserve %zu bytes of LDS: %s", who, lds, hipGetErrorString(e));
+    for (auto &p : raised)
+        if (!p) { p = kernel; return 0; }
+    return kk_fail(KK_EINVAL, "%s: the table of kernels with raised LDS limits is full", who);
+}
+
+// Launch KERNEL<BF16, ST16, G> with G*256 threads and its dynamic LDS (buffers x groups x NT tiles).
 template <typename K>
 int launch_attn(K kernel, dim3 grid, int G, size_t lds, hipStream_t s, const AttnArgs &a) {
-    if (lds > 64 * 1024) {
-        // (one table for every kernel of this signature: 64 slots for the ~20 kernels with more than 64 KB of dynamic LDS; a full table
-        //  is an error, not a silent hipFuncSetAttribute per launch — ADVICE r4)
-        static thread_local const void *raised[64];
-        bool done = false;
-        for (const void *p : raised) done = done || p == (const void *)kernel;
-        if (!done) {
-            hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return kk_fail((int)e, "attention: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-            bool noted = false;
-            for (auto &p : raised)
-                if (!p) { p = (const void *)kernel; noted = true; break; }
-            if (!noted) return kk_fail(KK_EINVAL, "attention: the table of kernels with raised LDS limits is full");
-        }
-    }
+    if (int rc = attn_raise_lds((const void *)kernel, lds, "attention")) return rc;
     hipLaunchKernelGGL(kernel, grid, dim3(256 * G), lds, s, a);
     return 0;
 }
@@ -2429,11 +2439,8 @@ static int attn_fwd_impl(const float *Q, const float *K, const float *V, float *
     KK_REQUIRE(!io_bf16 || math == KK_MATH_BF16, "kk_attn_fwd: bf16 storage needs KK_MATH_BF16");
     const int64_t lds[4] = {ldq, ldk, ldv, ldo};
     if (int rc = check_common("kk_attn_fwd", B, heads, Sq, Sk, math, lds, 4)) return rc;
-    AttnArgs a = {};
-    a.Q = Q; a.K = K; a.V = V; a.Out = O; a.LSEo = LSE; a.key_mask = key_mask;
-    a.B = B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.causal = causal;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldout = ldo; a.scale = scale;
-    a.seed = p_drop > 0.f ? seed : nullptr; a.site = site; a.p_drop = p_drop; a.xcd_map = attn_xcd_map(causal); a.dbg = attn_dbg(); a.wt = kk_write_through((int64_t)B * std::max(Sq, Sk));
+    AttnArgs a = attn_args(Q, K, V, B, heads, Sq, Sk, ldq, ldk, ldv, key_mask, causal, scale, seed, site, p_drop);
+    a.Out = O; a.LSEo = LSE; a.ldout = ldo;
     a.keep = keep;
     a.keep_rd = (keep_rd && keep != nullptr && a.seed != nullptr) ? 1 : 0;
     a.warm[0] = g_warm_ptr[0]; a.warm[1] = g_warm_ptr[1];
@@ -2579,26 +2586,23 @@ extern "C" int kk_attn_bwd_dq(const float *Q, const float *K, const float *V, co
     KK_REQUIRE(!io_bf16 || math == KK_MATH_BF16, "kk_attn_bwd_dq: bf16 storage needs KK_MATH_BF16");
     const int64_t lds[5] = {ldq, ldk, ldv, lddo, lddq};
     if (int rc = check_common("kk_attn_bwd_dq", B, heads, Sq, Sk, math, lds, 5)) return rc;
-    AttnArgs a = {};
-    a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.Out = dQ; a.key_mask = key_mask;
-    a.B = B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.causal = causal;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.lddo = lddo; a.ldout = lddq; a.scale = scale;
+    AttnArgs a = attn_args(Q, K, V, B, heads, Sq, Sk, ldq, ldk, ldv, key_mask, causal, scale, seed, site, p_drop);
+    a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.lddo = lddo; a.Out = dQ; a.ldout = lddq;
     if (O) {                                  // Delta is an OUTPUT of this call (and still the input of kk_attn_bwd_dkv)
         KK_REQUIRE(ldo % 8 == 0 && ldo >= 64 * heads, "kk_attn_bwd_dq: row stride of O unsupported");
         a.O = O; a.ldo = ldo; a.DeltaOut = Delta;
     }
-    a.seed = p_drop > 0.f ? seed : nullptr; a.site = site; a.p_drop = p_drop; a.xcd_map = attn_xcd_map(causal); a.dbg = attn_dbg(); a.wt = kk_write_through((int64_t)B * std::max(Sq, Sk));
     if (hn) {
         if (int rc = check_headnorm("kk_attn_bwd_dq", hn, 1)) return rc;
         a.hn[0] = hn[0];
     }
     dim3 grid(kk_cdiv(Sq, 128), B * heads);
     const int G = (Sk > 64 && g_attn_groups == 2) ? 2 : 1;
-    if (io_bf16 && (attn_v2_mask() & 2) && (G == 2 || attn_v2_small(Sq, Sk)) && g_attn_groups == 2 && Sk <= 4096 && al16(Q) && al16(K) && al16(V) && al16(dO) && al16(dQ) && (!O || al16(O)) &&
-        (!hn || (al16(hn->raw) && (!hn->rope || (al16(hn->cos_t) && al16(hn->sin_t))))) && (int64_t)Sk * std::max(ldk, ldv) * 2 < (1ll << 31)) {
-        kk_note_kernel((!O && (attn_gen3() & 1)) ? "attn_bwd_dq3" : "attn_bwd_dq2");
-        int rc2 = (!O && (attn_gen3() & 1)) ? launch_attn(attn_bwd_dq3_kernel, grid, 1, (size_t)3 * 16384 + 512 + 16384, (hipStream_t)stream, a)
-                                            : launch_attn(attn_bwd_dq2_kernel, grid, 2, (size_t)2 * 3 * 16384 + 512 + 3 * 16384, (hipStream_t)stream, a);
+    if (dma_storage(io_bf16, math, 2) && dma_tiles(Sk > 64, Sq, Sk) && Sk <= 4096 && al16_all({Q, K, V, dO, dQ, O}) && dma_hn_q(hn) &&
+        dma_bytes(Sk, ldk, ldv)) {
+        kk_note_kernel(!O ? "attn_bwd_dq3" : "attn_bwd_dq2");      // (the one-group kernel has no Delta output)
+        int rc2 = !O ? launch_attn(attn_bwd_dq3_kernel, grid, 1, (size_t)3 * 16384 + 512 + 16384, (hipStream_t)stream, a)
+                     : launch_attn(attn_bwd_dq2_kernel, grid, 2, (size_t)2 * 3 * 16384 + 512 + 3 * 16384, (hipStream_t)stream, a);
         if (rc2) return rc2;
         KK_LAUNCH_CHECK("kk_attn_bwd_dq");
         return 0;
@@ -2619,28 +2623,17 @@ extern "C" int kk_attn_bwd_dkv(const float *Q, const float *K, const float *V, c
     KK_REQUIRE(!io_bf16 || math == KK_MATH_BF16, "kk_attn_bwd_dkv: bf16 storage needs KK_MATH_BF16");
     const int64_t lds[6] = {ldq, ldk, ldv, lddo, lddk, lddv};
     if (int rc = check_common("kk_attn_bwd_dkv", B, heads, Sq, Sk, math, lds, 6)) return rc;
-    AttnArgs a = {};
-    a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.Out = dK; a.Out2 = dV; a.key_mask = key_mask;
-    a.B = B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.causal = causal;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.lddo = lddo; a.ldout = lddk; a.ldout2 = lddv; a.scale = scale;
-    a.seed = p_drop > 0.f ? seed : nullptr; a.site = site; a.p_drop = p_drop; a.xcd_map = attn_xcd_map(causal); a.dbg = attn_dbg(); a.wt = kk_write_through((int64_t)B * std::max(Sq, Sk));
+    AttnArgs a = attn_args(Q, K, V, B, heads, Sq, Sk, ldq, ldk, ldv, key_mask, causal, scale, seed, site, p_drop);
+    a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.lddo = lddo; a.Out = dK; a.Out2 = dV; a.ldout = lddk; a.ldout2 = lddv;
     if (hn) {
         if (int rc = check_headnorm("kk_attn_bwd_dkv", hn, 2)) return rc;
         a.hn[0] = hn[0]; a.hn[1] = hn[1];
     }
     dim3 grid(kk_cdiv(Sk, 128), B * heads);
     const int G = (Sq > 64 && g_attn_groups == 2) ? 2 : 1;          // one query tile: nothing to split
-    if (io_bf16 && (attn_v2_mask() & 4) && (G == 2 || attn_v2_small(Sq, Sk)) && g_attn_groups == 2 && al16(Q) && al16(K) && al16(V) && al16(dO) && al16(dK) && al16(dV) &&
-        (!hn || (al16(hn[0].raw) && al16(hn[1].raw) && !hn[1].rope && (!hn[0].rope || (al16(hn[0].cos_t) && al16(hn[0].sin_t))))) &&
-        (int64_t)Sq * std::max(ldq, lddo) * 2 < (1ll << 31)) {
-        kk_note_kernel((attn_gen3() & 1) ? "attn_bwd_dkv3" : "attn_bwd_dkv2");
-#ifdef KK_TUNING_HOOKS
-        int rc2 = (attn_gen3() & 1) ? launch_attn(attn_bwd_dkv3_kernel, grid, 1, (size_t)71680, (hipStream_t)stream, a)
-                                    : launch_attn(attn_bwd_dkv2_kernel, grid, 2, (size_t)2 * 3 * (16384 + 512) + 3 * 16384, (hipStream_t)stream, a);
-#else
-        int rc2 = launch_attn(attn_bwd_dkv3_kernel, grid, 1, (size_t)71680, (hipStream_t)stream, a);
-#endif
-        if (rc2) return rc2;
+    if (dma_storage(io_bf16, math, 4) && dma_tiles(Sq > 64, Sq, Sk) && al16_all({Q, K, V, dO, dK, dV}) && dma_hn_kv(hn) && dma_bytes(Sq, ldq, lddo)) {
+        kk_note_kernel("attn_bwd_dkv3");
+        if (int rc = launch_attn(attn_bwd_dkv3_kernel, grid, 1, (size_t)71680, (hipStream_t)stream, a)) return rc;
         KK_LAUNCH_CHECK("kk_attn_bwd_dkv");
         return 0;
     }
@@ -2652,9 +2645,9 @@ extern "C" int kk_attn_bwd_dkv(const float *Q, const float *K, const float *V, c
     return 0;
 }
 
-// dQ, dK and dV in one launch (attn_bwd_pair2_kernel) when both second-generation kernels apply; otherwise the two launches
-// above, in order.  Delta[b, head, q] = sum_d dO * O is an INPUT here (kk_gemm_dgrad_delta writes it with dO, or kk_attn_delta).
-// hn_q / hn_kv: the head-norm backward epilogues of kk_attn_bwd_dq / kk_attn_bwd_dkv (both or neither).
+// dQ, dK and dV in one launch (attn_bwd_pair3_kernel, or attn_bwd_pair3k_kernel reading keep bits) when both DMA-staged kernels
+// apply; otherwise the two launches above, in order.  Delta[b, head, q] = sum_d dO * O is an INPUT here (kk_gemm_dgrad_delta writes it
+// with dO, or kk_attn_delta).  hn_q / hn_kv: the head-norm backward epilogues of kk_attn_bwd_dq / kk_attn_bwd_dkv (both or neither).
 static int attn_bwd_impl(const float *Q, const float *K, const float *V, const float *dO, const float *LSE, const float *Delta,
                          float *dQ, float *dK, float *dV, int B, int heads, int Sq, int Sk, int64_t ldq, int64_t ldk,
                          int64_t ldv, int64_t lddo, int64_t lddq, int64_t lddk, int64_t lddv, const uint8_t *key_mask,
@@ -2662,14 +2655,8 @@ static int attn_bwd_impl(const float *Q, const float *K, const float *V, const f
                          const KkAttnHeadNorm *hn_q, const KkAttnHeadNorm *hn_kv, const void *keep, void *stream) {
     KK_REQUIRE(Delta != nullptr, "kk_attn_bwd: Delta is an input of this call");
     KK_REQUIRE((hn_q == nullptr) == (hn_kv == nullptr), "kk_attn_bwd: head-norm epilogues for both kernels or for neither");
-    const int G = (Sk > 64 && Sq > 64 && g_attn_groups == 2) ? 2 : 1;
-    const bool pair = io_bf16 && math == KK_MATH_BF16 && (attn_v2_mask() & 6) == 6 && attn_pair() && (G == 2 || attn_v2_small(Sq, Sk)) &&
-                      g_attn_groups == 2 && Sk <= 4096 &&
-                      kk_cdiv(Sq, 128) == kk_cdiv(Sk, 128) && al16(Q) && al16(K) && al16(V) && al16(dO) && al16(dQ) && al16(dK) && al16(dV) &&
-                      (!hn_q || (al16(hn_q->raw) && (!hn_q->rope || (al16(hn_q->cos_t) && al16(hn_q->sin_t))))) &&
-                      (!hn_kv || (al16(hn_kv[0].raw) && al16(hn_kv[1].raw) && !hn_kv[1].rope &&
-                                  (!hn_kv[0].rope || (al16(hn_kv[0].cos_t) && al16(hn_kv[0].sin_t))))) &&
-                      (int64_t)Sk * std::max(ldk, ldv) * 2 < (1ll << 31) && (int64_t)Sq * std::max(ldq, lddo) * 2 < (1ll << 31);
+    const bool pair = dma_both(io_bf16, math, Sq, Sk, Q, K, V, dO, dQ, dK, dV, ldq, ldk, ldv, lddo, hn_q, hn_kv) && attn_pair() &&
+                      dma_tiles(Sq > 64 && Sk > 64, Sq, Sk) && kk_cdiv(Sq, 128) == kk_cdiv(Sk, 128);
     if (!pair) {
         g_warm_bytes[0] = g_warm_bytes[1] = 0u;                 // (one-shot: a launch that cannot warm drops the request, it never waits for a later one)
         if (int rc = kk_attn_bwd_dq(Q, K, V, dO, LSE, const_cast<float *>(Delta), dQ, B, heads, Sq, Sk, ldq, ldk, ldv, lddo, lddq, key_mask,
@@ -2681,73 +2668,36 @@ static int attn_bwd_impl(const float *Q, const float *K, const float *V, const f
     KK_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "kk_attn_bwd: dropout probability must be in [0,1)");
     const int64_t lds[7] = {ldq, ldk, ldv, lddo, lddq, lddk, lddv};
     if (int rc = check_common("kk_attn_bwd", B, heads, Sq, Sk, math, lds, 7)) return rc;
-    struct { AttnArgs dq, dkv; } p = {};
-    AttnArgs &a = p.dq;
-    a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.Out = dQ; a.key_mask = key_mask;
-    a.B = B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.causal = causal;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.lddo = lddo; a.ldout = lddq; a.scale = scale;
-    a.seed = p_drop > 0.f ? seed : nullptr; a.site = site; a.p_drop = p_drop; a.xcd_map = attn_xcd_map(causal); a.dbg = attn_dbg(); a.wt = kk_write_through((int64_t)B * std::max(Sq, Sk));
+    AttnArgs a = attn_args(Q, K, V, B, heads, Sq, Sk, ldq, ldk, ldv, key_mask, causal, scale, seed, site, p_drop);
+    a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.lddo = lddo;
     if (a.xcd_map && causal) a.xcd_map = 2;                    // (the pair launch: always block-major when causal)
-    p.dkv = a;
-    if (attn_gen3() & 1) {                                     // the dQ half of the third-generation pair launch warms the next GEMMs' weights
-        p.dq.warm[0] = g_warm_ptr[0]; p.dq.warm[1] = g_warm_ptr[1];
-        p.dq.warm_bytes[0] = g_warm_bytes[0]; p.dq.warm_bytes[1] = g_warm_bytes[1];
-    }
+    AttnArgs a_dq = a, a_dkv = a;
+    a_dq.Out = dQ; a_dq.ldout = lddq;
+    a_dkv.Out = dK; a_dkv.Out2 = dV; a_dkv.ldout = lddk; a_dkv.ldout2 = lddv;
+    a_dq.warm[0] = g_warm_ptr[0]; a_dq.warm[1] = g_warm_ptr[1];          // the dQ half warms the next GEMMs' weights
+    a_dq.warm_bytes[0] = g_warm_bytes[0]; a_dq.warm_bytes[1] = g_warm_bytes[1];
     g_warm_bytes[0] = g_warm_bytes[1] = 0u;                     // (one-shot)
-    p.dkv.Out = dK; p.dkv.Out2 = dV; p.dkv.ldout = lddk; p.dkv.ldout2 = lddv;
     if (hn_q) {
         if (int rc = check_headnorm("kk_attn_bwd", hn_q, 1)) return rc;
         if (int rc = check_headnorm("kk_attn_bwd", hn_kv, 2)) return rc;
-        p.dq.hn[0] = hn_q[0];
-        p.dkv.hn[0] = hn_kv[0]; p.dkv.hn[1] = hn_kv[1];
+        a_dq.hn[0] = hn_q[0];
+        a_dkv.hn[0] = hn_kv[0]; a_dkv.hn[1] = hn_kv[1];
     }
-    if (attn_gen3() & 1) {                                     // one wave group per workgroup: two workgroups per CU
-        const size_t lds3 = 71680;
-        static thread_local bool raised3 = false;
-        if (!raised3) {
-            hipError_t e = hipFuncSetAttribute((const void *)attn_bwd_pair3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            if (e != hipSuccess) return kk_fail((int)e, "kk_attn_bwd: cannot reserve %zu bytes of LDS: %s", lds3, hipGetErrorString(e));
-            raised3 = true;
-        }
-        // (short blocks first only when both halves are resident at once — 2 workgroups per CU; with more rounds the longest-first
-        //  order of the second generation is the faster one: 8 x 8 x 1024^2 causal 79 against 96 us)
-        p.dkv.short_first = (causal && (attn_gen3() & 2) != 0 && (int64_t)kk_cdiv(Sq, 128) * B * heads <= g_attn_cus()) ? 1 : 0;
+    // (short blocks first only when both halves are resident at once — 2 workgroups per CU; with more rounds the longest-first
+    //  order is the faster one: 8 x 8 x 1024^2 causal 79 against 96 us)
+    a_dkv.short_first = (causal && attn_short_first() && (int64_t)kk_cdiv(Sq, 128) * B * heads <= g_attn_cus()) ? 1 : 0;
 #ifdef KK_TUNING_HOOKS
-        if (a.dbg & (256 | 4096)) { p.dq.DeltaOut = static_cast<float *>(g_attn_trace); p.dkv.DeltaOut = static_cast<float *>(g_attn_trace); }      // (stamp buffer: 8 rows x 64)
+    if (a.dbg & (256 | 4096)) { a_dq.DeltaOut = static_cast<float *>(g_attn_trace); a_dkv.DeltaOut = static_cast<float *>(g_attn_trace); }      // (stamp buffer: 8 rows x 64)
 #endif
-        if (keep != nullptr && p_drop > 0.f && Sk > 128 && kk_attn_keep_bytes(B, heads, Sq, Sk) > 0) {      // (exactly the launches whose forward stored the bits)
-            static thread_local bool raised3k = false;
-            if (!raised3k) {
-                hipError_t e = hipFuncSetAttribute((const void *)attn_bwd_pair3k_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-                if (e != hipSuccess) return kk_fail((int)e, "kk_attn_bwd: cannot reserve %zu bytes of LDS: %s", lds3, hipGetErrorString(e));
-                raised3k = true;
-            }
-            p.dq.keep = p.dkv.keep = const_cast<void *>(keep);
-            kk_note_kernel("attn_bwd_pair3k");
-            hipLaunchKernelGGL(attn_bwd_pair3k_kernel, dim3(kk_cdiv(Sq, 128), B * heads, 2), dim3(256), lds3, (hipStream_t)stream, p.dq, p.dkv);
-            KK_LAUNCH_CHECK("kk_attn_bwd");
-            return 0;
-        }
-        kk_note_kernel("attn_bwd_pair3");
-        hipLaunchKernelGGL(attn_bwd_pair3_kernel, dim3(kk_cdiv(Sq, 128), B * heads, 2), dim3(256), lds3, (hipStream_t)stream, p.dq, p.dkv);
-        KK_LAUNCH_CHECK("kk_attn_bwd");
-        return 0;
-    }
-#ifdef KK_TUNING_HOOKS
-    const size_t lds_bytes = std::max((size_t)2 * 3 * 16384 + 512 + 3 * 16384, (size_t)2 * 3 * (16384 + 512) + 3 * 16384);
-    static thread_local bool raised = false;
-    if (!raised) {
-        hipError_t e = hipFuncSetAttribute((const void *)attn_bwd_pair2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return kk_fail((int)e, "kk_attn_bwd: cannot reserve %zu bytes of LDS: %s", lds_bytes, hipGetErrorString(e));
-        raised = true;
-    }
-    kk_note_kernel("attn_bwd_pair2");
-    hipLaunchKernelGGL(attn_bwd_pair2_kernel, dim3(kk_cdiv(Sq, 128), B * heads, 2), dim3(512), lds_bytes, (hipStream_t)stream, p.dq, p.dkv);
+    const bool bits = keep != nullptr && p_drop > 0.f && Sk > 128 && kk_attn_keep_bytes(B, heads, Sq, Sk) > 0;      // (exactly the launches whose forward stored the bits)
+    if (bits) a_dq.keep = a_dkv.keep = const_cast<void *>(keep);
+    const auto kernel = bits ? attn_bwd_pair3k_kernel : attn_bwd_pair3_kernel;
+    const size_t lds3 = 71680;                                 // one wave group per workgroup: two workgroups per CU
+    if (int rc = attn_raise_lds((const void *)kernel, lds3, "kk_attn_bwd")) return rc;
+    kk_note_kernel(bits ? "attn_bwd_pair3k" : "attn_bwd_pair3");
+    hipLaunchKernelGGL(kernel, dim3(kk_cdiv(Sq, 128), B * heads, 2), dim3(256), lds3, (hipStream_t)stream, a_dq, a_dkv);
     KK_LAUNCH_CHECK("kk_attn_bwd");
     return 0;
-#else
-    return kk_fail(KK_EINVAL, "kk_attn_bwd: unreachable");
-#endif
 }
 
 extern "C" int kk_attn_bwd(const float *Q, const float *K, const float *V, const float *dO, const float *LSE, const float *Delta,
@@ -2770,8 +2720,8 @@ extern "C" int kk_attn_bwd_kb(const float *Q, const float *K, const float *V, co
                          scale, seed, site, p_drop, math, io_bf16, hn_q, hn_kv, keep, stream);
 }
 
-// Backward in two passes through a caller-owned workspace (see attn_bwd_dkv2s_kernel): the same contract and fall-backs as
-// kk_attn_bwd, which is what runs when ws is null / too small or the launch is not eligible for the pair launch either.
+// Backward in two passes through a caller-owned workspace (see attn_bwd_dkv3s_kernel): the same contract and fall-backs as
+// kk_attn_bwd, which is what runs when ws is null / too small or the launch is not eligible for the two passes.
 extern "C" int64_t kk_attn_bwd_ws_bytes(int B, int heads, int Sq, int Sk) {
     if (B <= 0 || heads <= 0 || Sq <= 0 || Sk <= 0) return 0;
     return (int64_t)B * heads * kk_cdiv(Sk, 32) * (kk_cdiv(Sq, 128) * 4) * 2048;
@@ -2779,19 +2729,16 @@ extern "C" int64_t kk_attn_bwd_ws_bytes(int B, int heads, int Sq, int Sk) {
 // Whether the two passes are the faster form for this shape (advice to the caller, who hands kk_attn_bwd_ws a workspace only then;
 // the entry point itself takes the two passes whenever it gets an adequate workspace and the kernels serve the launch).  The dQ
 // pass reads the dS tiles back from the Infinity Cache (~11 B/clk/CU with every CU streaming), 17 us of a 37-47 us launch at
-// 8 x 8 x 512^2 — so the two passes lose there and win where the pair launch is long and not lopsided: full attention from 1024^2 up
-// (146 -> 128 us; causal 92 -> 90: left to the pair launch, whose halves balance each other).  KK_ATTN_BWD_TWO_PASS=2: always, 0: never.
+// 8 x 8 x 512^2, so the two passes lose there; their best case is a long pair launch that is not lopsided, full attention at 1024^2,
+// which they run in 128 us and the pair launch in 118 us.  So the advice is "never" (causal launches were the pair launch's already: its halves
+// balance each other).  KK_ATTN_BWD_TWO_PASS=2 (tools): wherever the kernels serve the shape, 0: never.
 static int attn_two_pass_mode() {
     static const int v = kk_tune_env("KK_ATTN_BWD_TWO_PASS", 1);
     return v;
 }
 extern "C" int kk_attn_bwd_two_pass(int B, int heads, int Sq, int Sk, int causal) {
-    const int mode = attn_two_pass_mode();
-    if (mode == 0 || B <= 0 || heads <= 0 || Sq <= 64 || Sk <= 64 || Sk > 4096 || (causal && Sq != Sk)) return 0;
-    if (mode == 2) return 1;
-    // (against the second-generation pair launch the two passes won for full attention from 1024^2 up: 142 -> 125 us; the
-    //  third-generation pair launch runs that shape in 118 us, so with it the advice is "never")
-    return !(attn_gen3() & 1) && !causal && (int64_t)Sq * Sk >= (1ll << 20);
+    if (B <= 0 || heads <= 0 || Sq <= 64 || Sk <= 64 || Sk > 4096 || (causal && Sq != Sk)) return 0;
+    return attn_two_pass_mode() == 2;
 }
 
 extern "C" int kk_attn_bwd_ws(const float *Q, const float *K, const float *V, const float *dO, const float *LSE, const float *Delta,
@@ -2804,37 +2751,23 @@ extern "C" int kk_attn_bwd_ws(const float *Q, const float *K, const float *V, co
     const int two_pass = attn_two_pass_mode() != 0;             // (the shape policy is the caller's: kk_attn_bwd_two_pass)
     const int64_t per_head = (int64_t)kk_cdiv(Sk, 32) * (kk_cdiv(Sq, 128) * 4) * 2048;
     const bool ok = two_pass && ws && al16(ws) && ws_bytes >= kk_attn_bwd_ws_bytes(B, heads, Sq, Sk) && per_head < (1ll << 31) &&
-                    io_bf16 && math == KK_MATH_BF16 && (attn_v2_mask() & 6) == 6 && g_attn_groups == 2 && Sk > 64 && Sq > 64 && Sk <= 4096 &&
-                    (!causal || Sq == Sk) && al16(Q) && al16(K) && al16(V) && al16(dO) && al16(dQ) && al16(dK) && al16(dV) &&
-                    (!hn_q || (al16(hn_q->raw) && (!hn_q->rope || (al16(hn_q->cos_t) && al16(hn_q->sin_t))))) &&
-                    (!hn_kv || (al16(hn_kv[0].raw) && al16(hn_kv[1].raw) && !hn_kv[1].rope &&
-                                (!hn_kv[0].rope || (al16(hn_kv[0].cos_t) && al16(hn_kv[0].sin_t))))) &&
-                    (int64_t)Sk * std::max(ldk, ldv) * 2 < (1ll << 31) && (int64_t)Sq * std::max(ldq, lddo) * 2 < (1ll << 31);
+                    dma_both(io_bf16, math, Sq, Sk, Q, K, V, dO, dQ, dK, dV, ldq, ldk, ldv, lddo, hn_q, hn_kv) &&
+                    g_attn_groups == 2 && Sq > 64 && Sk > 64 && (!causal || Sq == Sk);
     if (!ok)
         return kk_attn_bwd(Q, K, V, dO, LSE, Delta, dQ, dK, dV, B, heads, Sq, Sk, ldq, ldk, ldv, lddo, lddq, lddk, lddv, key_mask, causal,
                            scale, seed, site, p_drop, math, io_bf16, hn_q, hn_kv, stream);
     KK_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "kk_attn_bwd_ws: dropout probability must be in [0,1)");
     const int64_t lds[7] = {ldq, ldk, ldv, lddo, lddq, lddk, lddv};
     if (int rc = check_common("kk_attn_bwd_ws", B, heads, Sq, Sk, math, lds, 7)) return rc;
-    AttnArgs a = {};
-    a.Q = Q; a.K = K; a.V = V; a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.Out = dK; a.Out2 = dV; a.key_mask = key_mask;
-    a.B = B; a.heads = heads; a.Sq = Sq; a.Sk = Sk; a.causal = causal;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.lddo = lddo; a.ldout = lddk; a.ldout2 = lddv; a.scale = scale;
-    a.seed = p_drop > 0.f ? seed : nullptr; a.site = site; a.p_drop = p_drop; a.xcd_map = attn_xcd_map(causal); a.dbg = attn_dbg();
-    a.wt = kk_write_through((int64_t)B * std::max(Sq, Sk));
+    AttnArgs a = attn_args(Q, K, V, B, heads, Sq, Sk, ldq, ldk, ldv, key_mask, causal, scale, seed, site, p_drop);
+    a.dO = dO; a.LSE = LSE; a.Delta = Delta; a.lddo = lddo; a.Out = dK; a.Out2 = dV; a.ldout = lddk; a.ldout2 = lddv;
     a.dS = ws;
     if (hn_q) {
         if (int rc = check_headnorm("kk_attn_bwd_ws", hn_q, 1)) return rc;
         if (int rc = check_headnorm("kk_attn_bwd_ws", hn_kv, 2)) return rc;
         a.hn[0] = hn_kv[0]; a.hn[1] = hn_kv[1];
     }
-#ifdef KK_TUNING_HOOKS
-    if (int rc = (attn_gen3() & 1) ? launch_attn(attn_bwd_dkv3s_kernel, dim3(kk_cdiv(Sk, 128), B * heads), 1, (size_t)71680, (hipStream_t)stream, a)
-                                   : launch_attn(attn_bwd_dkv2s_kernel, dim3(kk_cdiv(Sk, 128), B * heads), 2, (size_t)2 * 3 * (16384 + 512) + 3 * 16384, (hipStream_t)stream, a))
-        return rc;
-#else
     if (int rc = launch_attn(attn_bwd_dkv3s_kernel, dim3(kk_cdiv(Sk, 128), B * heads), 1, (size_t)71680, (hipStream_t)stream, a)) return rc;
-#endif
     KK_LAUNCH_CHECK("kk_attn_bwd_ws (dK, dV, dS)");
     a.Out = dQ; a.Out2 = nullptr; a.ldout = lddq; a.ldout2 = 0;
     a.hn[0] = KkAttnHeadNorm{}; a.hn[1] = KkAttnHeadNorm{};

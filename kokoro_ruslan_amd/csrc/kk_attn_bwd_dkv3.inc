@@ -106,7 +106,7 @@
     const float c2 = a.scale * 1.4426950408889634f;
     const bool anydead = __ballot(!kalive) != 0ull;
 #ifdef KK_DKV_STORE_DS
-    // (attn_bwd_dkv2s_kernel) dS = P o (dP - Delta), rounded to bf16 exactly as the dK MFMA below consumes it, leaves the workgroup as
+    // (attn_bwd_dkv3s_kernel) dS = P o (dP - Delta), rounded to bf16 exactly as the dK MFMA below consumes it, leaves the workgroup as
     // [32 keys][32 queries] tiles of 2 KB: tile (key unit, query unit) of this (batch, head) at ((ku * nqu4) + qu) * 2048 — the
     // operand of attn_bwd_dqpass_kernel, which then needs no scores, exponentials or masks of its own
     const int nqu4 = ((a.Sq + 127) >> 7) << 2;

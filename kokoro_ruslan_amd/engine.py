@@ -224,7 +224,7 @@ class KokoroEngine:
         # attention backward as ONE launch (kk_attn_bwd: the dQ and the dK/dV kernel as the two halves of a grid), Delta from the
         # epilogue of the w_o dgrad GEMM (kk_gemm_dgrad_delta) — bf16 storage, shapes that take the eight-wave GEMM tile
         self.attn_bwd_pair = True
-        # ... or, where the library prices it cheaper (kk_attn_bwd_two_pass: nowhere beside the present pair launch), as the dK/dV
+        # ... or, where the library prices it cheaper (kk_attn_bwd_two_pass: nowhere, 128 against the pair launch's 118 us at full 1024 x 1024), as the dK/dV
         # kernel that also stores dS + a dQ pass without softmax work (kk_attn_bwd_ws; workspace of 2 bytes per score per stream)
         self.attn_two_pass = True
         # the attention forward stores its dropout keep decisions as packed bits (kk_attn_fwd_kb) and the backward's pair launch reads
@@ -975,8 +975,8 @@ class KokoroEngine:
                                         w1.numel() * w1.element_size() if w1 is not None else 0)
 
         def bwd_one_call(*args):
-            """kk_attn_bwd, or — where the library says the shape pays (kk_attn_bwd_two_pass: full attention from 1024 x 1024 scores per
-            head up) — kk_attn_bwd_ws with this stream's dS workspace (2 bytes per score; "tmp.": private to the stream)."""
+            """kk_attn_bwd, or — where the library says the shape pays (kk_attn_bwd_two_pass: no shape at present, see there) —
+            kk_attn_bwd_ws with this stream's dS workspace (2 bytes per score; "tmp.": private to the stream)."""
             if self.attn_two_pass and kk.load().kk_attn_bwd_two_pass(B, h, Sq, Sk, cz):
                 need = kk.load().kk_attn_bwd_ws_bytes(B, h, Sq, Sk)
                 kk.call("kk_attn_bwd_ws", *args, self._buf("tmp.attn_dS", need, dtype=torch.uint8), need)
