@@ -442,6 +442,23 @@ int kk_feat_pitch(const float *wave, const int64_t *woff, const float *peak, con
 int kk_feat_finish(const int *moff, const int *poff, int B, const float *eraw, const float *cand, const float *acmax, const float *msq,
                    float *scratch_a, float *scratch_b, float *pitch, float *energy, int variance, void *stream);
 
+/* ---- band-limited resampling (kokoro_ruslan_amd/resample.py; kk_resample.hip): torchaudio's sinc_interp_hann, width 6, rolloff 0.99 ----
+ * Waveforms packed back to back, in by woff_in and out by woff_out (int64 [B + 1]; utterance b has ceil(n_b L_b / o_b) outputs).
+ * rate: int32 [B][8] = {o, n, width, bits of fp32(base / (o n)), bits of fp32(base / o), 0, 0, 0} with o : n the rates reduced by
+ * their gcd, base = 0.99 min(o, n), width = ceil(6 o / base); {1, 1, 0, 0, bits of 1.0f} copies the utterance.  tiles: int32
+ * [ntiles][2] = {utterance, first output sample (a multiple of kk_resample_tile())}.  peak (or null): x = wave / (peak[b] + 1e-9) on
+ * load.  y[q n + p] = sum_{m = c - width}^{c + width} x[q o + m] h(base (m n - p o) / (o n)), c = floor(p o / n), h(t) = (base / o)
+ * sinc(pi t) cos(pi t / 12)^2 with t clamped to [-6, 6], summed over ascending m in fp32.  An utterance's output does not depend on
+ * the batch. */
+/* outputs of one tile */
+int kk_resample_tile(void);
+/* 1 when the kernel takes this rate pair (the span 256 outputs read fits its LDS: o / n below ~14) */
+int kk_resample_supported(int o, int n, int width);
+int kk_resample(const float *wave, const int64_t *woff_in, const float *peak, const int *rate, const int *tiles, int ntiles,
+                const int64_t *woff_out, float *out, void *stream);
+/* wave[b] /= peak[b] + 1e-9 in place (max_samples: the longest utterance) */
+int kk_resample_normalise(float *wave, const int64_t *woff, int B, int64_t max_samples, const float *peak, void *stream);
+
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}
  * (transformers.py:16-40,482-487,569-581; the FFN has two dropouts in series, :111).  *seed is read on the device. */

@@ -1,11 +1,13 @@
 """kokoro-precompute: write the feature cache kokoro-train reads, with the acoustic features extracted on the device.
 
-    kokoro-precompute --wavs DIR --ids FILE.jsonl --cache-dir OUT [--force] [--no-variance] [--batch-size N] [--max-seq-length N]
+    kokoro-precompute --wavs DIR --ids FILE.jsonl --cache-dir OUT [--force] [--no-variance] [--resample] [--batch-size N]
+                      [--max-seq-length N]
 
 FILE.jsonl is kokoro-synth --ids's format, one utterance per line: {"name", "phoneme_indices"[, "stress_indices"]}, plus optional
 "phoneme_durations" (frames per phoneme, e.g. from an MFA alignment; absent: the reference's even fallback estimate) and "text".
-DIR/<name>.wav is the audio, 22050 Hz.  The phonemizer, MFA alignment and resampling are not part of this tool: it takes their
-results.  Entries of the current cache version are skipped unless --force, as the reference's kokoro-precompute does.
+DIR/<name>.wav is the audio, 22050 Hz; with --resample audio at another rate is resampled to 22050 Hz on the device first (the
+reference's torchaudio.transforms.Resample, data/dataset.py:662-665) instead of being refused.  The phonemizer and MFA alignment are
+not part of this tool: it takes their results.  Entries of the current cache version are skipped unless --force, as the reference's kokoro-precompute does.
 """
 from __future__ import annotations
 
@@ -23,6 +25,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--cache-dir", required=True, metavar="OUT")
     p.add_argument("--force", action="store_true", help="recompute entries that exist")
     p.add_argument("--no-variance", action="store_true", help="zero pitch and energy")
+    p.add_argument("--resample", action="store_true", help="resample audio at another rate to 22050 Hz on the device instead of refusing it")
     p.add_argument("--batch-size", type=int, default=32, help="utterances per device call")
     p.add_argument("--max-seq-length", type=int, default=1800, help="mel frames kept per utterance")
     p.add_argument("--n-mels", type=int, default=80)
@@ -72,17 +75,31 @@ def main(argv=None) -> int:
             todo.append(i)
     computed = failed = 0
     ext = FeatureExtractor() if todo else None
+    rs = None
     for s in range(0, len(todo), args.batch_size):
-        batch, waves = [], []
+        batch, waves, rates = [], [], []
         for i in todo[s:s + args.batch_size]:
             try:
-                waves.append(DF.load_wav(os.path.join(args.wavs, names[i] + ".wav")))
+                path = os.path.join(args.wavs, names[i] + ".wav")
+                sr, w = DF.load_wav_any(path) if args.resample else (args.sample_rate, DF.load_wav(path))
+                waves.append(w)
+                rates.append(sr)
                 batch.append(i)
             except Exception as e:
                 failed += 1
                 print(f"kokoro-precompute: {names[i]}: {e}", file=sys.stderr)
         if not batch:
             continue
+        if any(sr != args.sample_rate for sr in rates):
+            try:
+                if rs is None:
+                    from kokoro_ruslan_amd.resample import Resampler
+                    rs = Resampler()
+                waves = rs.resample(waves, rates, args.sample_rate)
+            except Exception as e:
+                failed += len(batch)
+                print(f"kokoro-precompute: resampling the batch of {names[batch[0]]}: {e}", file=sys.stderr)
+                continue
         feats = ext.extract(waves, max_seq_length=args.max_seq_length, variance=not args.no_variance)
         for i, ft in zip(batch, feats):
             try:

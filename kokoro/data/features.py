@@ -1,8 +1,9 @@
 """Writing the feature cache: what the reference's dataset does around the acoustic front-end when it builds a sample
 (data/dataset.py:581-606, :644-672, :737-784, :849-862).  `load_wav` reads a .wav by the reference's dtype rules, `stop_token_targets`
 and `fallback_durations` restate build_stop_token_targets and _build_fallback_durations, `cache_entry` assembles a schema-v7 entry from
-the device extractor's output and `write_cache_entry` saves it as <audio_file>.pt, the file kokoro.data.cached reads.  Resampling, the
-phonemizer and MFA alignment are out of scope: phoneme ids (and durations, when aligned) are given.
+the device extractor's output and `write_cache_entry` saves it as <audio_file>.pt, the file kokoro.data.cached reads.  `load_wav_any`
+reads a .wav at any rate for the callers that resample on the device (kokoro-precompute --resample).  The phonemizer and MFA
+alignment are out of scope: phoneme ids (and durations, when aligned) are given.
 """
 from __future__ import annotations
 
@@ -17,14 +18,11 @@ from kokoro.data.cached import FEATURE_CACHE_VERSION, reference_reconcile
 SAMPLE_RATE = 22050
 
 
-def load_wav(path: str) -> torch.Tensor:
-    """Mono fp32 samples of a .wav, un-normalised: int16 / 32768, int32 / 2^31, anything else cast to fp32; channels averaged
-    (dataset.py:644-669).  A sample rate other than 22050 Hz is an error: resampling is out of scope here."""
+def load_wav_any(path: str):
+    """(sample rate, mono fp32 samples) of a .wav at any rate, un-normalised: int16 / 32768, int32 / 2^31, anything else cast to fp32;
+    channels averaged (dataset.py:644-669)."""
     from scipy.io import wavfile
     sr, a = wavfile.read(str(path))
-    if sr != SAMPLE_RATE:
-        raise ValueError(f"{path}: sample rate {sr} Hz, expected {SAMPLE_RATE}; resampling is out of scope here, resample the corpus "
-                         f"first (the reference does it with torchaudio)")
     if a.dtype == np.int16:
         a = a.astype(np.float32) / 32768.0
     elif a.dtype == np.int32:
@@ -34,7 +32,17 @@ def load_wav(path: str) -> torch.Tensor:
     x = torch.from_numpy(a)
     if x.dim() == 2:
         x = x.T.mean(dim=0) if x.shape[1] > 1 else x[:, 0]
-    return x.contiguous()
+    return int(sr), x.contiguous()
+
+
+def load_wav(path: str) -> torch.Tensor:
+    """Mono fp32 samples of a .wav, un-normalised, by load_wav_any's rules.  A sample rate other than 22050 Hz is an error: resampling
+    is out of scope here (kokoro-precompute --resample does it on the device)."""
+    sr, x = load_wav_any(path)
+    if sr != SAMPLE_RATE:
+        raise ValueError(f"{path}: sample rate {sr} Hz, expected {SAMPLE_RATE}; resampling is out of scope here, resample the corpus "
+                         f"first (the reference does it with torchaudio)")
+    return x
 
 
 def stop_token_targets(T: int, tail: int = 4, decay: float = 0.5) -> torch.Tensor:

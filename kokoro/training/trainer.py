@@ -3,8 +3,10 @@ epoch loop → micro-batches with exact accumulation divisor (reference training
 boundary (all decisions on the device, see kokoro_ruslan_amd/csrc/kk_optim.hip) → validation on the EMA weights
 (trainer.py:1771-1985, forward + losses only) → checkpoints in the reference layout (kokoro.training.checkpoint).
 
-Input data are the reference's cached features (kokoro.data.cached); the audio front-end / MFA / phonemizer stay on
-the reference.  TensorBoard, profilers and MPS memory management of the reference trainer are out of scope.
+Input data are the reference's cached features (kokoro.data.cached).  With `use_speed_perturbation` and the corpus audio under
+{data_dir}/wavs/, the loader rebuilds the features of the perturbed samples from the raw audio on the device, as the reference's
+dataset does on the host (kokoro.data.augment).  MFA / phonemizer stay on the reference.  TensorBoard, profilers and MPS memory
+management of the reference trainer are out of scope.
 """
 from __future__ import annotations
 
@@ -68,11 +70,20 @@ class BatchPrefetcher:
     the GPU (an event recorded by the consumer), which is also what bounds the loader's run-ahead.
 
     Yields (batch of device views, expanded_len) where expanded_len = max_b sum(durations) is computed on the host
-    copy, and the consuming stream already waits for the transfer."""
+    copy, and the consuming stream already waits for the transfer.
+
+    `perturb` (kokoro.data.augment.SpeedPerturbation) turns on the reference's speed perturbation for `epoch`: a perturbed row gets
+    its host-side fields (ids, stress, rescaled durations, stop targets, mel_length) through the same collate and transfer; its audio
+    is copied up from a second pinned buffer and FeatureExtractor.extract_perturbed writes its mel, pitch and energy into the device
+    slab on the copy stream before `ready` is recorded.  Unperturbed rows, and every row without `perturb`, take the path above."""
 
     def __init__(self, dataset, batches: List[List[int]], device: torch.device, depth: int = 3, max_mel: int = 2000,
-                 max_ph: int = 2000, hip_lock=None):
+                 max_ph: int = 2000, hip_lock=None, perturb=None, epoch: int = 0):
         self.dataset, self.batches, self.device, self.depth = dataset, batches, device, max(2, depth)
+        self.perturb, self.epoch = perturb, int(epoch)
+        self.wave_host = [None] * self.depth             # pinned fp32 staging of the perturbed rows' audio, and its device copy
+        self.wave_dev = [None] * self.depth
+        self.perturbed_rows = 0
         self.max_mel, self.max_ph = max_mel, max_ph      # _cap_batch_sequence_dimensions (reference trainer.py:3364-3411)
         self.hip_lock = hip_lock if hip_lock is not None else threading.Lock()    # engine.capture_lock: no HIP calls from
         #                                                                           this thread while a graph is captured
@@ -103,6 +114,13 @@ class BatchPrefetcher:
                     break
                 t0 = time.perf_counter()
                 items = [self.dataset[i] for i in idxs]
+                todo = []                                # rows whose features are rebuilt from the perturbed audio
+                if self.perturb is not None:
+                    for r, i in enumerate(idxs):
+                        it = self.perturb.item(i, self.epoch, items[r])
+                        if it is not None:
+                            items[r] = it
+                            todo.append(r)
                 B, T, P, M, mel_len, ph_len, plan, total = batch_layout(items, self.max_mel, self.max_ph)
                 self.load_s += time.perf_counter() - t0
                 slot, done = self.free_q.get()
@@ -127,10 +145,14 @@ class BatchPrefetcher:
                     views[k] = dev[off:off + n].view(_TORCH_DT[dt]).view(shape)
                 collate_into(items, arrays, mel_len, ph_len)
                 expanded = int(np.clip(arrays["phoneme_durations"], 0, None).sum(axis=1).max()) if B and P else 0
+                if todo:
+                    wave_n = self._stage_waves(slot, [items[r]["_perturb"][0] for r in todo])
                 with self.hip_lock:
                     ready = torch.cuda.Event()
                     with torch.cuda.stream(self.copy_stream):
                         dev[:total].copy_(host[:total], non_blocking=True)
+                        if todo:
+                            self._perturbed_features(slot, wave_n, [items[r]["_perturb"][1] for r in todo], todo, views, mel_len)
                         ready.record(self.copy_stream)
                 self.load_s += time.perf_counter() - t0
                 self.q.put((slot, views, expanded, ready))
@@ -138,6 +160,41 @@ class BatchPrefetcher:
         except BaseException as e:                       # surfaced on the training thread
             self.error = e
             self.q.put(None)
+
+    def _stage_waves(self, slot: int, waves) -> List[int]:
+        """The perturbed rows' audio (int16 or fp32 arrays) as fp32 back to back in the slot's pinned buffer; their lengths."""
+        import numpy as np
+        n = [int(a.shape[0]) for a in waves]
+        total = sum(n)
+        if self.wave_host[slot] is None or self.wave_host[slot].numel() < total:
+            with self.hip_lock:
+                cap = total + total // 4
+                self.wave_host[slot] = torch.empty(cap, dtype=torch.float32).pin_memory()
+                self.wave_dev[slot] = torch.empty(cap, dtype=torch.float32, device=self.device)
+                torch.cuda.synchronize(self.device_index)
+        h = self.wave_host[slot].numpy()
+        off = 0
+        for a, v in zip(waves, n):
+            if a.dtype == np.int16:
+                np.multiply(a, np.float32(1.0 / 32768.0), out=h[off:off + v], casting="unsafe")     # = a / 32768: load_wav's rule
+            else:
+                h[off:off + v] = a
+            off += v
+        return n
+
+    def _perturbed_features(self, slot: int, n: List[int], factors: List[float], rows: List[int], views, mel_len: List[int]) -> None:
+        """On the copy stream, under hip_lock: audio up, extract_perturbed, the results into the device slab's views."""
+        total = sum(n)
+        wd = self.wave_dev[slot]
+        wd[:total].copy_(self.wave_host[slot][:total], non_blocking=True)
+        ext = self.perturb.extractor(self.device)
+        feats = ext.extract_perturbed(list(wd[:total].split(n)), factors, max_seq_length=self.perturb.max_seq_length)
+        for r, ft in zip(rows, feats):
+            t = mel_len[r]
+            views["mel_specs"][r, :t].copy_(ft["mel_spec"].T[:t])
+            views["pitches"][r, :t].copy_(ft["pitch"][:t])
+            views["energies"][r, :t].copy_(ft["energy"][:t])
+        self.perturbed_rows += len(rows)
 
     def __iter__(self):
         try:
@@ -204,6 +261,18 @@ class KokoroTrainer:
                 self.engine.dp_comm, self.engine.loss_sync, self.sync = comm, comm, None
             else:
                 self.engine.loss_sync = dp.LossSync(self.world)
+        # speed perturbation (reference data/dataset.py:613-627): on when the config asks for it AND the corpus audio is there
+        self.perturb = None
+        if getattr(config, "use_speed_perturbation", False):
+            wav_dir = os.path.join(str(config.data_dir), "wavs")
+            if os.path.isdir(wav_dir):
+                from kokoro.data.augment import SpeedPerturbation
+                self.perturb = SpeedPerturbation(self.dataset, wav_dir, config.speed_perturb_prob, config.speed_perturb_range, 0,
+                                                 config.max_seq_length, config.use_memory_cache)
+                logger.info("speed perturbation on: prob %.2f, range +-%.2f, audio from %s", config.speed_perturb_prob,
+                            config.speed_perturb_range, wav_dir)
+            else:
+                logger.info("speed perturbation off: use_speed_perturbation is set but %s does not exist; training from the cache", wav_dir)
         self.start_epoch, self.best_val, self.best_epoch, self.patience = 0, float("inf"), -1, 0
         self.use_graphs = os.environ.get("KK_TRAINER_GRAPHS", "1") != "0"
         # Per-micro-batch non-finite guard (reference trainer.py:2304-2314): by default the device flags the micro-batch
@@ -242,10 +311,13 @@ class KokoroTrainer:
         step = e.train_step_auto if self.use_graphs else e.train_step
         acc, losses, n = 0, torch.zeros(6, device=e.device), 0
         try:
-            self.last_prefetch = BatchPrefetcher(self.dataset, batches, e.device, self.prefetch_depth, 2000, 2000, e.capture_lock)
+            self.last_prefetch = BatchPrefetcher(self.dataset, batches, e.device, self.prefetch_depth, 2000, 2000, e.capture_lock,
+                                                 self.perturb, epoch)
             for bi, (batch, expanded) in enumerate(self.last_prefetch):
                 if groups is not None:      # longest (capped) mel length among this step's batches on all ranks
-                    e.global_mel_length = min(2000, max(self.dataset.samples[i]["audio_length"] for g in groups[bi] for i in g))
+                    frames = ((lambda i: self.perturb.perturbed_length(i, epoch)) if self.perturb is not None
+                              else (lambda i: self.dataset.samples[i]["audio_length"]))
+                    e.global_mel_length = min(2000, max(frames(i) for g in groups[bi] for i in g))
                 div = effective_accumulation_divisor(G, acc, bi, len(batches))
                 boundary = (acc + 1 >= G) or (bi == len(batches) - 1)
                 e.micro_in_cycle = acc

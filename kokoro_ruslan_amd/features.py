@@ -5,7 +5,8 @@ defaults: 22050 Hz, n_fft = win = 1024, hop 256, 80 HTK mels over 0-8000 Hz; Pit
 and EnergyExtractor (log1p of the mean linear mel, 5 % / 95 % quantile scaling).  The waveforms of one call are packed back to back
 with an offsets table and run through four launches: peak, mel, pitch, finish.  Every sum and every statistic of an utterance runs over
 its own samples in a fixed order, so row b of a batch is, bit for bit, the utterance extracted alone.  All arithmetic is fp32, as in
-the reference.  Resampling, the phonemizer and MFA alignment are not here.
+the reference.  `extract_perturbed` puts the resampler (kokoro_ruslan_amd/resample.py) in front of the same four launches: the
+reference's train-time speed perturbation.  The phonemizer and MFA alignment are not here.
 """
 from __future__ import annotations
 
@@ -56,6 +57,7 @@ class FeatureExtractor:
         self.pitch_window = torch.hann_window(PITCH_WIN, periodic=True, dtype=torch.float64).to(torch.float32).to(self.device)
         self.tw = torch.view_as_real(twiddles()).contiguous().to(self.device)
         self.tile_frames = int(kk.load().kk_feat_mel_tile_frames())
+        self._resampler = None
 
     def extract(self, waves: Sequence[torch.Tensor], max_seq_length: int = 1800, variance: bool = True,
                 max_samples: int = DEFAULT_MAX_SAMPLES, keep_linear: bool = False,
@@ -82,13 +84,51 @@ class FeatureExtractor:
             out += self._run(group, int(max_seq_length), variance, keep_linear, intermediates)
         return out
 
+    def extract_perturbed(self, waves: Sequence[torch.Tensor], factors: Sequence[float], max_seq_length: int = 1800,
+                          variance: bool = True, max_samples: int = DEFAULT_MAX_SAMPLES) -> List[Dict[str, object]]:
+        """extract() of Resampler.speed_perturb(waves, factors), bit for bit, without the waveforms leaving the device in between: the
+        reference's features of a speed-perturbed training sample (dataset.py:672-707).  Waveform b is peak-normalised, resampled
+        22050 -> int(22050 factors[b]) and peak-normalised again, then runs through the four feature launches.  All lengths are
+        computed on the host (ceil(n L / o) samples).  The waveforms run in groups of at most max_samples packed samples, counted
+        before and after resampling."""
+        from kokoro_ruslan_amd import resample as RS
+        if int(max_seq_length) != max_seq_length or max_seq_length < 1:
+            raise ValueError(f"max_seq_length must be an integer >= 1, not {max_seq_length!r}")
+        if int(max_samples) != max_samples or max_samples < 1:
+            raise ValueError(f"max_samples must be an integer >= 1, not {max_samples!r}")
+        if len(factors) != len(waves):
+            raise ValueError(f"{len(factors)} factors for {len(waves)} waveforms")
+        for i, w in enumerate(waves):
+            check_wave(i, w)
+        if self._resampler is None:
+            self._resampler = RS.Resampler(self.device)
+        rows = [RS.rate_row(SAMPLE_RATE, RS.perturbed_rate(f, SAMPLE_RATE)) for f in factors]
+        size = [max(int(w.shape[0]), RS.out_length(w.shape[0], r)) for w, r in zip(waves, rows)]
+        out: List[Dict[str, object]] = []
+        group, total = [], 0
+        for i in list(range(len(waves))) + [None]:
+            if group and (i is None or total + size[i] > max_samples):
+                n = [int(waves[k].shape[0]) for k in group]
+                pack = torch.cat([waves[k].to(self.device, torch.float32) for k in group]).contiguous()
+                wave, m = self._resampler.run_packed(pack, n, [rows[k] for k in group], True)
+                out += self._run_packed(wave, m, int(max_seq_length), variance, False, False)
+                group, total = [], 0
+            if i is not None:
+                group.append(i)
+                total += size[i]
+        return out
+
     def _run(self, waves: List[torch.Tensor], max_T: int, variance: bool, keep_linear: bool, intermediates: bool):
-        dev = self.device
-        B = len(waves)
         n = [int(w.shape[0]) for w in waves]
+        wave = torch.cat([w.to(self.device, torch.float32) for w in waves]).contiguous()
+        return self._run_packed(wave, n, max_T, variance, keep_linear, intermediates)
+
+    def _run_packed(self, wave: torch.Tensor, n: List[int], max_T: int, variance: bool, keep_linear: bool, intermediates: bool):
+        """wave: the fp32 waveforms of n[b] samples each, back to back on the device."""
+        dev = self.device
+        B = len(n)
         T = [min(1 + max(v, N_FFT) // HOP, max_T) for v in n]
         Tp = [1 + max(v, PITCH_WIN) // HOP for v in n]
-        wave = torch.cat([w.to(dev, torch.float32) for w in waves]).contiguous()
         cum = lambda v: torch.tensor([0] + v).cumsum(0)
         woff = cum(n).to(torch.int64).to(dev)
         moff, poff = cum(T).to(torch.int32).to(dev), cum(Tp).to(torch.int32).to(dev)

@@ -241,6 +241,10 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_feat_mel": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "kk_feat_pitch": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "kk_feat_finish": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "kk_resample_tile": [],
+    "kk_resample_supported": [_I, _I, _I],
+    "kk_resample": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "kk_resample_normalise": [_P, _P, _I, _L, _P, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
     "kk_losses_finalize": [_P, C.POINTER(KkLossCfg), _P, _I, _P, _P, _P, _I, _P],
     "kk_losses_bwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _P, _P],
