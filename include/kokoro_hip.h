@@ -376,6 +376,40 @@ int kk_decode_epilogue_rows(const float *frame_out, const float *stop, float *me
                             int *frames, int *live, const int *min_b, const int *expected_b, const int *max_b, int B, int L1, int M,
                             float stop_threshold, float post_expected_stop_threshold, void *stream);
 
+/* ---- continuous batching of the decode (KokoroEngine.generate_stream; kk_stream.hip): a pool of S slots of `cap` frames, every slot
+ * with its own frame index, so that a finished row's slot is refilled while the others go on.  All state is int32 [S]: t_rows (the
+ * slot's frame index), done, frames, klen (self-attention keys), clen (cross-attention keys), min_b / expected_b / max_b.  H = heads*64.
+ * attn_decode_rows: kk_attn_fwd's Sq = 1 kernel with a key count per row.  q, out [S, H]; K / V: key j of slot s at
+ *   s * k_slot + j * ldk (elements); lse [S, heads]; key_mask [S, Sk] or NULL (1 = masked).  Row s reads keys j < min(klen[s], Sk) only
+ *   — nothing at or past klen[s] is loaded — and gets the bits kk_attn_fwd gives at Sq = 1 over those keys; klen[s] == 0 gives a zero
+ *   output and lse = +inf.  Sk sizes the LDS score array (<= 8192).  No dropout.
+ * decode_prologue_rows: kk_decode_prologue with t_rows[s] in place of *t_dev: frame_in[s] = mel_all[s, t_s] (mel_all [S, L1, M]),
+ *   pe_rows [S, H] = pe[t_s], cos_rows / sin_rows [S, 64] = the RoPE tables' row t_s (tables of n_pos rows),
+ *   klen[s] = done[s] ? 0 : t_s + 1.  A row with done[s] set is fed position 0 and its mel row 0.
+ * decode_cache_append_rows: nrm [S, 3H] -> q [S, H] and row t_s of slot s of the slot-major caches [S][cap][H]; rows with done[s]
+ *   set write nothing.
+ * decode_epilogue_slots: kk_decode_epilogue_rows with each row filed under its own t_s: mel_all[s, t_s + 1] = frame_out[s],
+ *   stop_all[s, t_s] = stop[s] (stop_all [S, L1 - 1]), the stop rule with t_s against min_b / expected_b / max_b [s],
+ *   t_rows[s] += 1 for live rows; a row that stops gets frames[s] = t_s + 1, done[s] = 1 and *live -= 1 and is never written again.
+ * slot_admit: n rows into the slots slot_of[0..n): their cross-attention K|V rows (kv_src [n * T_adm] rows of row_bytes bytes) to rows
+ *   [slot * cap, slot * cap + T_adm) of kv_pool; fm_pool[slot, j] = j < T_adm ? fm_src[r, j] : 1 for j < cap; t = frames = done = 0,
+ *   clen = T_adm, the bounds from bounds [3, n] (min | expected | max), mel_all[slot, 0] = 0, *live += n.  The self-attention caches
+ *   are left as they are: klen keeps stale keys unread.  The entries of slot_of must be distinct and name free slots. */
+int kk_attn_decode_rows(const void *q, const void *K, const void *V, void *out, float *lse, const int *klen, const uint8_t *key_mask,
+                        int S, int heads, int Sk, int64_t k_slot, int64_t ldk, int64_t v_slot, int64_t ldv, float scale, int bf16,
+                        void *stream);
+int kk_decode_prologue_rows(const float *mel_all, float *frame_in, const float *pe, float *pe_rows, const float *cos_t,
+                            const float *sin_t, float *cos_rows, float *sin_rows, const int *t_rows, const int *done, int *klen, int S,
+                            int L1, int M, int H, int n_pos, void *stream);
+int kk_decode_cache_append_rows(const void *nrm, void *q, void *kcache, void *vcache, const int *t_rows, const int *done, int S, int cap,
+                                int H, int bf16, void *stream);
+int kk_decode_epilogue_slots(const float *frame_out, const float *stop, float *mel_all, float *stop_all, int *t_rows, int *done,
+                             int *frames, int *live, const int *min_b, const int *expected_b, const int *max_b, int S, int L1, int M,
+                             float stop_threshold, float post_expected_stop_threshold, void *stream);
+int kk_slot_admit(const void *kv_src, void *kv_pool, const uint8_t *fm_src, uint8_t *fm_pool, const int *slot_of, const int *bounds,
+                  int *t_rows, int *done, int *frames, int *clen, int *min_b, int *expected_b, int *max_b, float *mel_all, int *live,
+                  int n, int T_adm, int S, int cap, int64_t row_bytes, int L1, int M, void *stream);
+
 /* ---- HiFi-GAN vocoder (kokoro_ruslan_amd/vocoder.py; kk_vocoder.hip): mels -> waveforms for a packed batch ----
  * Activations are channels-last fp32 [rows, C]; the utterances are packed back to back along time and seg[0..nseg] holds their
  * start rows in the layer's INPUT row units (seg[0] = 0, seg[nseg] = rows).  A tap never reads outside its own utterance: each

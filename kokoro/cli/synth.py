@@ -2,13 +2,15 @@
 
     kokoro-synth --checkpoint CKPT (--features CACHE_DIR [--indices ...] | --ids FILE.jsonl) --output DIR
                  [--batch-size 32] [--weights auto|ema|model] [--stop-threshold X] [--max-len N] [--min-len-ratio R]
-                 [--min-len-floor N] [--trim] [--math bf16|f32]
+                 [--min-len-floor N] [--trim] [--math bf16|f32] [--stream [--slots 32]]
                  [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32]]
                  [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
 --features reads phoneme_indices / stress_indices from a precomputed feature cache (kokoro.data.cached); --ids reads JSON lines
 {"name", "phoneme_indices", "stress_indices"?}.  --trim applies the reference's clamp + trailing-silence trim (:588-619).
+--stream decodes all utterances in one pool of --slots rows whose finished rows are refilled with the next utterance (continuous
+batching, KokoroEngine.generate_stream) instead of in fixed batches of --batch-size; the mels are the same.
 --vocoder (a HiFi-GAN generator checkpoint: a directory with generator.pth + config.json, or a file) also writes <name>.wav: the
 saved mel, clamped to [-11.5, 2] (:590), vocoded on the device in batches, int16 PCM at the vocoder config's sampling_rate.
 --griffin-lim writes the same <name>.wav with the reference's Griffin-Lim vocoder instead (kokoro_ruslan_amd.griffinlim, 80 mels,
@@ -40,6 +42,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min-len-floor", type=int, default=None)
     p.add_argument("--trim", action="store_true")
     p.add_argument("--math", choices=("bf16", "f32"), default="bf16")
+    p.add_argument("--stream", action="store_true", help="continuous batching: refill finished rows instead of fixed batches")
+    p.add_argument("--slots", type=int, default=None, metavar="N", help="rows of the --stream pool (default 32)")
     p.add_argument("--vocoder", metavar="PATH", default=None, help="HiFi-GAN generator: directory or checkpoint file")
     p.add_argument("--vocoder-config", metavar="JSON", default=None, help="HiFi-GAN config (default: the checkpoint's config.json)")
     p.add_argument("--vocoder-math", choices=("bf16", "f32"), default="bf16")
@@ -56,6 +60,10 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--griffin-lim-iters / --griffin-lim-seed need --griffin-lim")
     if args.griffin_lim_iters < 0:
         p.error("--griffin-lim-iters must be >= 0")
+    if args.slots is not None and not args.stream:
+        p.error("--slots needs --stream")
+    if args.slots is not None and args.slots < 1:
+        p.error("--slots must be >= 1")
 
 
 def read_ids(path: str) -> Tuple[List[str], List[torch.Tensor], Optional[List[torch.Tensor]]]:
@@ -110,7 +118,10 @@ def main(argv=None) -> int:
                                                 min_len_floor=args.min_len_floor)
     if args.griffin_lim and engine.dims.mel != 80:
         parser.error(f"--griffin-lim needs an 80-mel model; this checkpoint makes {engine.dims.mel} mel channels")
-    mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **controls.kwargs())
+    if args.stream:
+        mels = synthesize(engine, ids, stress, stream=True, slots=32 if args.slots is None else args.slots, **controls.kwargs())
+    else:
+        mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **controls.kwargs())
     os.makedirs(args.output, exist_ok=True)
     saved = []
     for name, mel in zip(names, mels):

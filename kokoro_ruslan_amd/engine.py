@@ -552,6 +552,7 @@ class KokoroEngine:
                     raise RuntimeError("descriptor-table cache overflow inside a graph capture")
                 torch.cuda.synchronize(self.device)
                 self._graphs.clear()
+                self.ws_generation += 1                    # (a graph held outside _graphs checks this: generate_stream)
                 for _ in range(self.max_tables // 4):
                     self._tables.popitem(last=False)
             t = self._tables[key] = build()
@@ -591,12 +592,13 @@ class KokoroEngine:
         a = self.arena
         return a.fused(a.p16 if self.use_shadow else a.p, first, count)
 
-    def _linear(self, x, W, b, out, res=None, res_mod=0):
+    def _linear(self, x, W, b, out, res=None, res_mod=0, split_k=0):
         N, K = x.shape
         M = W.shape[0]
         # split_k = 0: kk_gemm splits K (fp32 atomics) by itself when the tile grid is too small to fill the chip
+        # (split_k = 1, _stream_step: one slice, no atomics, so that a replayed step repeats its bits)
         kk.call("kk_gemm", 0, 0, N, M, K, 1.0, x, x.stride(0), W, K, 0.0, out, out.stride(0), b, res,
-                res.stride(0) if res is not None else 0, res_mod, 0, self.math, _b16(x) | _b16(W) << 1 | _b16(out) << 2)
+                res.stride(0) if res is not None else 0, res_mod, split_k, self.math, _b16(x) | _b16(W) << 1 | _b16(out) << 2)
 
     def _dgrad(self, dy, W, dx, beta=0.0):
         N, M = dy.shape
@@ -815,6 +817,12 @@ class KokoroEngine:
         else:
             kk.call("kk_attn_fwd", q_n, k_n, v_n, ctx, lse, B, h, Sq, Sk, q_n.stride(0), k_n.stride(0), v_n.stride(0), H, key_mask,
                     1 if causal else 0, 0.125, self.rng, site + 3, p, self.math, i16)
+        return self._attn_out(key, prefix, ctx, Nq, Sq, x_res, x_out, site, p, dpr, next_ln)
+
+    def _attn_out(self, key, prefix, ctx, Nq, Sq, x_res, x_out, site, p, dpr, next_ln, split_k=0):
+        """The output projection and residual tail of an attention sub-layer: x_out = x_res + w_o(ctx) + b_o, and LayerNorm_next_ln."""
+        P, H = self.arena.P, self.dims.hidden
+        dt, i16 = ctx.dtype, _b16(ctx)
         # the projection output lives only until the tail two launches later: in the decoder's bf16 mode it is stored like every
         # other GEMM result there (what autocast gives the reference's nn.Linear); the text encoder keeps fp32 (its persistent
         # launch hands the tile over in fp32, and the per-kernel path must match it)
@@ -831,7 +839,7 @@ class KokoroEngine:
                     _b16(n), mean, rstd, Nq, H, Sq, self.rng, site, p, site + 1, 0.0, site + 2, dpr)
             return n
         proj = self._buf("tmp.attn_proj16" if p16 else "tmp.attn_proj", Nq, H, dtype=dt if p16 else torch.float32)
-        self._linear(ctx, Wo, P[prefix + ".w_o.bias"], proj)
+        self._linear(ctx, Wo, P[prefix + ".w_o.bias"], proj, split_k=split_k)
         return self._sublayer_tail(proj, x_res, x_out, Sq, site, p, dpr, 0.0, None, None, next_ln)   # (p = 0: masks are all ones)
 
     def _attn_keep(self, key, B, Sq, Sk, p, i16):
@@ -867,7 +875,7 @@ class KokoroEngine:
         nrm = self._buf(f"{ns}dec.ca.{which}kv_n_all", Nk, 2 * H * L, dtype=dt)
         return raw[:, 2 * H * layer:2 * H * (layer + 1)], nrm[:, 2 * H * layer:2 * H * (layer + 1)]
 
-    def _proj_headnorm(self, x, W, raw, nrm, S, gains, rope_mask, cos, sin):
+    def _proj_headnorm(self, x, W, raw, nrm, S, gains, rope_mask, cos, sin, split_k=0):
         """raw = x.W^T (an attention projection of len(gains) parts x heads x 64 columns, no bias: transformers.py:131-136)
         and nrm = its per-head RMSNorm (+ RoPE): in bf16 mode one GEMM whose epilogue normalises, else GEMM + norm launches."""
         H, h = self.dims.hidden, self.dims.heads
@@ -877,7 +885,7 @@ class KokoroEngine:
             kk.call("kk_gemm_qkv_headnorm", rows, parts, h, x.shape[1], x, x.stride(0), W, None, raw, raw.stride(0), nrm,
                     nrm.stride(0), S, table, rope_mask, cos, sin)
             return
-        self._linear(x, W, None, raw)
+        self._linear(x, W, None, raw, split_k=split_k)
         for p0 in range(0, parts, 3):                      # the norm kernel takes up to three parts per launch
             g = list(gains[p0:p0 + 3]) + [None] * 3
             n = min(3, parts - p0)
@@ -1088,7 +1096,7 @@ class KokoroEngine:
         return self._buf(f"enc{L - 1}.xo", Ne, H), self._buf("enc.norm.y", Ne, H)
 
     # ------------------------------------------------------------------ GLU feed-forward sub-layer
-    def _ffn_fwd(self, key, prefix, y, x_res, x_out, Fd, S=1, site=0, p=0.0, dpr=0.0, next_ln=None):
+    def _ffn_fwd(self, key, prefix, y, x_res, x_out, Fd, S=1, site=0, p=0.0, dpr=0.0, next_ln=None, split_k=0):
         P = self.arena.P
         N, H = y.shape
         dt, i16 = y.dtype, _b16(y)
@@ -1098,9 +1106,9 @@ class KokoroEngine:
         if i16 and _b16(W1) and H % 64 == 0 and self.fuse_glu_fwd:             # bf16 mode: the gate is the epilogue of the linear1 GEMM
             kk.call("kk_gemm_linear_glu", N, Fd, H, y, y.stride(0), W1, P[prefix + ".linear1.bias"], h1, g, Fd, self.rng, site + 4, p)
         else:
-            self._linear(y, W1, P[prefix + ".linear1.bias"], h1)
+            self._linear(y, W1, P[prefix + ".linear1.bias"], h1, split_k=split_k)
             kk.call("kk_glu_fwd", h1, g, N, Fd, self.rng, site + 4, p, i16)
-        self._linear(g, self._W(prefix + ".linear2.weight"), P[prefix + ".linear2.bias"], f2)
+        self._linear(g, self._W(prefix + ".linear2.weight"), P[prefix + ".linear2.bias"], f2, split_k=split_k)
         # rmsnorm -> FFN dropout (:111) -> drop_path -> residual dropout (+ the next LayerNorm), one launch
         return self._sublayer_tail(f2, x_res, x_out, S, site, p, dpr, p, P[prefix + ".output_norm.weight"],
                                    self._buf(key + ".rstd_f", N), next_ln)
@@ -1842,6 +1850,61 @@ class KokoroEngine:
         finally:
             self.train_dropout = saved_drop
 
+    def _check_utterances(self, utterances, stress):
+        """The argument checks of generate_batch / generate_stream; returns (stress or None, phonemes per utterance)."""
+        B = len(utterances)
+        if stress is not None and len(stress) != B:
+            raise ValueError(f"stress: {len(stress)} vectors for {B} utterances")
+        if stress is not None and any(s is None for s in stress):
+            if not all(s is None for s in stress):
+                raise ValueError("stress must be given for every utterance or for none")
+            stress = None
+        lens_p = [int(u.numel()) for u in utterances]
+        if min(lens_p) < 1:
+            raise ValueError("empty utterance")
+        if stress is not None and [int(s.numel()) for s in stress] != lens_p:
+            raise ValueError("stress and phoneme vectors differ in length")
+        if max(lens_p) > self.dims.max_len:
+            raise ValueError(f"utterance of {max(lens_p)} phonemes exceeds the positional table ({self.dims.max_len})")
+        return stress, lens_p
+
+    def _prefill_rows(self, ns, utterances, stress, lens_p, first=0, frame_limit=None):
+        """Everything of a ragged batch in front of the decode loop, on the workspace keys under `ns`: pad, encode, the duration
+        predictor over each row's own phonemes, the expansion with each row's own frame count (_expand_fwd(flens=...)).  Error
+        messages name utterance `first` + row; frame_limit: a row predicted longer raises before anything is expanded.
+        Returns (dur [B, Pn], T_b, T = max(T_b), memory, fm2)."""
+        d, H = self.dims, self.dims.hidden
+        B, Pn = len(utterances), max(lens_p)
+        ids_h = torch.zeros(B, Pn, dtype=torch.int64)
+        st_h = torch.zeros(B, Pn, dtype=torch.int64) if stress is not None else None
+        for b, u in enumerate(utterances):
+            ids_h[b, :lens_p[b]] = u.reshape(-1).to("cpu", torch.int64)
+            if st_h is not None:
+                st_h[b, :lens_p[b]] = stress[b].reshape(-1).to("cpu", torch.int64)
+        ids = ids_h.to(self.device)
+        st = st_h.to(self.device) if st_h is not None else None
+        text_mask = self._buf(ns + "text_mask", B, Pn, dtype=torch.uint8)
+        enc = self._encode_text_fwd(ns, ids, st, B, Pn, text_mask)
+        # ---- duration predictor, each row over its own P_b phonemes ----
+        plens = torch.tensor(lens_p, dtype=torch.int32).to(self.device)
+        log_dur = self._buf(ns + "out.log_dur", B, Pn)
+        col_e = self._buf(ns + "vp.col_enc", B * Pn, 3 * H, dtype=self.enc_dt)
+        kk.call("kk_im2col3_rows_fwd", enc, col_e, plens, B, Pn, H, CHUNK, _b16(col_e))
+        dmask = self._buf(ns + "vp.dur_mask", B, Pn, dtype=torch.uint8)
+        kk.call("kk_varpred_row_mask", text_mask, plens, dmask, B, Pn, CHUNK)
+        self._varpred_fwd(ns + "vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, dmask, log_dur, lens=plens)
+        dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
+        sums = dur.sum(dim=1).cpu().tolist()                   # (host sync: the row lengths size everything below)
+        Tb = [max(int(s_), 3) for s_ in sums]
+        for b, tb in enumerate(Tb):
+            if tb > d.max_len:
+                raise ValueError(f"utterance {first + b}: predicted length {tb} exceeds the positional table ({d.max_len})")
+            if frame_limit is not None and tb > frame_limit:
+                raise ValueError(f"utterance {first + b}: predicted length {tb} exceeds slot_frames ({frame_limit})")
+        T = max(Tb)
+        memory, fm2 = self._expand_fwd(ns, enc, dur, B, Pn, T, flens=torch.tensor(Tb, dtype=torch.int32).to(self.device))
+        return dur, Tb, T, memory, fm2
+
     @torch.no_grad()
     def generate_batch(self, utterances: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]] = None, *, max_len: int = 4000,
                        stop_threshold: float = 0.5, min_len_ratio: float = 0.7, min_len_floor: int = 12, max_len_ratio: float = 3.0,
@@ -1865,48 +1928,10 @@ class KokoroEngine:
         B = len(utterances)
         if B == 0:
             return ([], {"durations": [], "T": [], "bounds": []}) if want_info else []
-        if stress is not None and len(stress) != B:
-            raise ValueError(f"stress: {len(stress)} vectors for {B} utterances")
-        if stress is not None and any(s is None for s in stress):
-            if not all(s is None for s in stress):
-                raise ValueError("stress must be given for every utterance or for none")
-            stress = None
-        lens_p = [int(u.numel()) for u in utterances]
-        if min(lens_p) < 1:
-            raise ValueError("empty utterance")
-        if stress is not None and [int(s.numel()) for s in stress] != lens_p:
-            raise ValueError("stress and phoneme vectors differ in length")
-        Pn = max(lens_p)
-        if Pn > d.max_len:
-            raise ValueError(f"utterance of {Pn} phonemes exceeds the positional table ({d.max_len})")
-        ids_h = torch.zeros(B, Pn, dtype=torch.int64)
-        st_h = torch.zeros(B, Pn, dtype=torch.int64) if stress is not None else None
-        for b, u in enumerate(utterances):
-            ids_h[b, :lens_p[b]] = u.reshape(-1).to("cpu", torch.int64)
-            if st_h is not None:
-                st_h[b, :lens_p[b]] = stress[b].reshape(-1).to("cpu", torch.int64)
-        ids = ids_h.to(self.device)
-        st = st_h.to(self.device) if st_h is not None else None
+        stress, lens_p = self._check_utterances(utterances, stress)
         saved_drop, self.train_dropout = self.train_dropout, False
         try:
-            text_mask = self._buf("syn.text_mask", B, Pn, dtype=torch.uint8)
-            enc = self._encode_text_fwd("syn.", ids, st, B, Pn, text_mask)
-            # ---- duration predictor, each row over its own P_b phonemes ----
-            plens = torch.tensor(lens_p, dtype=torch.int32).to(self.device)
-            log_dur = self._buf("syn.out.log_dur", B, Pn)
-            col_e = self._buf("syn.vp.col_enc", B * Pn, 3 * H, dtype=self.enc_dt)
-            kk.call("kk_im2col3_rows_fwd", enc, col_e, plens, B, Pn, H, CHUNK, _b16(col_e))
-            dmask = self._buf("syn.vp.dur_mask", B, Pn, dtype=torch.uint8)
-            kk.call("kk_varpred_row_mask", text_mask, plens, dmask, B, Pn, CHUNK)
-            self._varpred_fwd("syn.vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, dmask, log_dur, lens=plens)
-            dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
-            sums = dur.sum(dim=1).cpu().tolist()                   # (host sync: the row lengths size everything below)
-            Tb = [max(int(s_), 3) for s_ in sums]
-            for b, tb in enumerate(Tb):
-                if tb > d.max_len:
-                    raise ValueError(f"utterance {b}: predicted length {tb} exceeds the positional table ({d.max_len})")
-            T = max(Tb)
-            memory, fm2 = self._expand_fwd("syn.", enc, dur, B, Pn, T, flens=torch.tensor(Tb, dtype=torch.int32).to(self.device))
+            dur, Tb, T, memory, fm2 = self._prefill_rows("syn.", utterances, stress, lens_p)
             bounds = []
             for b, expected in enumerate(Tb):
                 bounds.append(self._generation_bounds(expected, max_len, min_len_ratio, min_len_floor, max_len_ratio, max_len_cap,
@@ -1932,6 +1957,182 @@ class KokoroEngine:
             mels = [mel_out[b, 1:nf[b] + 1].clamp(min=-11.5, max=2.0).clone() for b in range(B)]
             if want_info:
                 return mels, {"durations": [dur[b, :lens_p[b]].clone() for b in range(B)], "T": Tb, "bounds": bounds}
+            return mels
+        finally:
+            self.train_dropout = saved_drop
+
+    # ------------------------------------------------------------------ continuous batching
+    def _stream_state(self, S, cap):
+        """The slot pool's int32 state, one buffer [8, S] (+ the live count): t | done | frames | klen | clen | min | expected | max."""
+        st = self._buf("str.state", 8, S, dtype=torch.int32)
+        return {"all": st, "t": st[0], "done": st[1], "frames": st[2], "klen": st[3], "clen": st[4], "min": st[5], "exp": st[6],
+                "max": st[7], "live": self._buf("str.live", 1, dtype=torch.int32)}
+
+    def _stream_step(self, S, cap, stop_threshold, post_expected_stop_threshold):
+        """_decode_step + kk_decode_epilogue_rows for a pool of S slots of `cap` frames, every slot at its own frame t_s: the row
+        kernels of kk_stream.hip around the same GEMM / norm launches.  Self-attention: kk_attn_decode_rows over the slot-major
+        caches [S][cap][H] with klen[s] = t_s + 1 keys (0 for a finished slot), no mask and no zero-filled cache.  Cross-attention:
+        the same kernel over the slot's rows of the K|V pool [S*cap, 2H*layers] with clen[s] = the admitted group's frame count
+        and the slot frame mask [S, cap].  The step's plain GEMMs are launched as one k-slice each (split_k = 1: no fp32 atomics),
+        so a replayed step repeats the bits of the eager one; at a few rows that gives up the k-split's extra workgroups."""
+        d, P, H, M, h = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dims.heads
+        ddt, L1, W = self.dec_dt, cap + 1, 2 * self.dims.hidden * self.dims.dec_layers
+        st = self._stream_state(S, cap)
+        pe = P["positional_encoding.pe"].view(d.max_len, H)
+        cos, sin = self._rope_tables(d.max_len)
+        mel_all, stop_all = self._buf("str.mel", S, L1, M), self._buf("str.stop", S, cap)
+        pool, fmask = self._buf("str.dec.ca.kv_n_pool", S * cap, W, dtype=ddt), self._buf("str.fmask", S, cap, dtype=torch.uint8)
+        y, frame_in, frame_out, stop_now = (self._buf("str.y", S, H), self._buf("str.frame_in", S, M), self._buf("str.frame_out", S, M),
+                                            self._buf("str.stop_now", S))
+        pe_rows, cos_rows, sin_rows = self._buf("str.pe_rows", S, H), self._buf("str.cos_rows", S, 64), self._buf("str.sin_rows", S, 64)
+        kk.call("kk_decode_prologue_rows", mel_all, frame_in, pe, pe_rows, cos, sin, cos_rows, sin_rows, st["t"], st["done"], st["klen"],
+                S, L1, M, H, d.max_len)
+        self._linear(frame_in, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], y, res=pe_rows, res_mod=0, split_k=1)
+        n1 = self._ln_fwd("str.dec0.ln1", y, "decoder.layers.0.norm1", ddt)
+        yl = y
+        for i in range(d.dec_layers):
+            pf, key = f"decoder.layers.{i}", f"str.dec{i}"
+            gq, gk, gv = P[pf + ".self_attn.q_norm.weight"], P[pf + ".self_attn.k_norm.weight"], P[pf + ".self_attn.v_norm.weight"]
+            raw, nrm = self._buf(key + ".qkv_raw", S, 3 * H, dtype=ddt), self._buf(key + ".qkv_n", S, 3 * H, dtype=ddt)
+            # S "positions" with a [S, 64] table: row s is rotated by cos_rows[s] = its own absolute position (K only, as _decode_step)
+            self._proj_headnorm(n1, self._Wf(pf + ".self_attn.w_q.weight", 3), raw, nrm, S, (gq, gk, gv), 2, cos_rows, sin_rows, split_k=1)
+            qb = self._buf(key + ".q", S, H, dtype=ddt)
+            Kc, Vc = self._buf(key + ".kcache", S, cap, H, dtype=ddt), self._buf(key + ".vcache", S, cap, H, dtype=ddt)
+            kk.call("kk_decode_cache_append_rows", nrm, qb, Kc, Vc, st["t"], st["done"], S, cap, H, _b16(nrm))
+            ctx, lse = self._buf(key + ".ctx", S, H, dtype=ddt), self._buf(key + ".lse", S, h)
+            kk.call("kk_attn_decode_rows", qb, Kc, Vc, ctx, lse, st["klen"], None, S, h, cap, cap * H, H, cap * H, H, 0.125, _b16(qb))
+            proj = self._buf("str.proj", S, H)
+            self._linear(ctx, self._W(pf + ".self_attn.w_o.weight"), P[pf + ".self_attn.w_o.bias"], proj, split_k=1)
+            ya = self._buf(key + ".xa", S, H)
+            n2 = self._sublayer_tail(proj, yl, ya, 1, 0, 0.0, 0.0, 0.0, None, None, (key + ".ln2", pf + ".norm2", ddt))
+            # cross-attention: _attn_fwd's launches with the row kernel in the place of kk_attn_fwd
+            cp = pf + ".cross_attn"
+            q_raw, q_n = self._buf(key + ".ca.q_raw", S, H, dtype=ddt), self._buf(key + ".ca.q_n", S, H, dtype=ddt)
+            self._proj_headnorm(n2, self._W(cp + ".w_q.weight"), q_raw, q_n, 1, (P[cp + ".q_norm.weight"],), 0, None, None, split_k=1)
+            k_n, v_n = pool[:, 2 * H * i:], pool[:, 2 * H * i + H:]
+            cctx, clse = self._buf(key + ".ca.ctx", S, H, dtype=ddt), self._buf(key + ".ca.lse", S, h)
+            kk.call("kk_attn_decode_rows", q_n, k_n, v_n, cctx, clse, st["clen"], fmask, S, h, cap, cap * W, W, cap * W, W, 0.125, _b16(q_n))
+            yc = self._buf(key + ".xc", S, H)
+            n3 = self._attn_out(key + ".ca", cp, cctx, S, 1, ya, yc, 0, 0.0, 0.0, (key + ".ln3", pf + ".norm3", ddt), split_k=1)
+            yo = self._buf(key + ".xo", S, H)
+            nxt = ((f"str.dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", ddt) if i + 1 < d.dec_layers
+                   else ("str.dec.norm", "decoder.norm", ddt))
+            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=nxt, split_k=1)
+            yl = yo
+        dec_out = n1
+        self._linear(dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out, split_k=1)
+        kk.call("kk_rowdot_fwd", dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now,
+                S, H, 1, 0, _b16(dec_out))
+        kk.call("kk_decode_epilogue_slots", frame_out, stop_now, mel_all, stop_all, st["t"], st["done"], st["frames"], st["live"],
+                st["min"], st["exp"], st["max"], S, L1, M, float(stop_threshold), float(post_expected_stop_threshold))
+
+    @torch.no_grad()
+    def generate_stream(self, utterances: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]] = None, *, slots: int = 32,
+                        slot_frames: Optional[int] = None, max_len: int = 4000, stop_threshold: float = 0.5, min_len_ratio: float = 0.7,
+                        min_len_floor: int = 12, max_len_ratio: float = 3.0, max_len_cap: int = 1600,
+                        post_expected_stop_threshold: float = 0.2, check_every: int = 16, decode_graph: bool = True,
+                        want_info: bool = False):
+        """generate_batch with continuous batching: the utterances are decoded in a pool of `slots` slots of `slot_frames` frames and
+        a finished row's slot is refilled with the next utterance, so the decode steps are spent on live rows instead of lasting as
+        long as the longest row of a fixed batch.  Arguments, results (in input order) and the want_info dict are generate_batch's.
+        Every mel is what generate_batch([u]) gives for that utterance alone (within 1e-4 in fp32) as long as slot_frames does not
+        cut the row's bound: slot_frames (default min(max_len_cap, the positional table)) bounds both T_b and the generation bound
+        of a row, which is computed with max_len_cap = min(max_len_cap, slot_frames).  An utterance predicted longer than
+        slot_frames raises ValueError naming its index before anything of it is decoded.
+
+        Admission: whenever slots are free and utterances remain, generate_batch's prefill stages (_prefill_rows, the same
+        launches) run on the next group on workspace keys "str.adm.", with their host sync for the row lengths; then kk_slot_admit
+        files the group's cross-attention K|V, frame mask and bounds under its slots.  A refill group is often one utterance.
+        Step: _stream_step; its buffers depend on (slots, slot_frames) alone, so one captured hipGraph serves the call unless an
+        admission regrows a workspace (which drops every graph of the engine, _invalidate): then the next step runs eagerly and
+        is captured again.  Workspaces only grow, so that dies out after the first few admissions of an engine's life.
+        Harvest: every `check_every` frames the host reads done | frames in one copy, clones the finished slots' mels and admits
+        into them; the steps of a block behind the last finished row run with every slot done.  Idle slots have done = 1 and
+        klen = 0."""
+        d, H, M = self.dims, self.dims.hidden, self.dims.mel
+        N = len(utterances)
+        if N == 0:
+            return ([], {"durations": [], "T": [], "bounds": []}) if want_info else []
+        S = int(slots)
+        cap = int(min(max_len_cap, d.max_len) if slot_frames is None else slot_frames)    # (no row outgrows the positional table)
+        if S < 1 or cap < 1 or check_every < 1:
+            raise ValueError("slots, slot_frames and check_every must be positive")
+        if cap > d.max_len:
+            raise ValueError(f"slot_frames {cap} exceeds the positional table ({d.max_len})")
+        if cap > 8192:
+            raise ValueError(f"slot_frames {cap} exceeds the decode attention's 8192 keys")
+        stress, lens_p = self._check_utterances(utterances, stress)
+        saved_drop, self.train_dropout = self.train_dropout, False
+        try:
+            ddt, L1, W = self.dec_dt, cap + 1, 2 * H * d.dec_layers
+            st = self._stream_state(S, cap)
+            mel_all = self._buf("str.mel", S, L1, M)
+            pool, fmask = self._buf("str.dec.ca.kv_n_pool", S * cap, W, dtype=ddt), self._buf("str.fmask", S, cap, dtype=torch.uint8)
+            st["all"].zero_()
+            st["done"].fill_(1)                            # every slot idle: klen = 0, nothing of it is read or written
+            st["live"].zero_()
+            mel_all[:, 0].zero_()
+            fmask.fill_(1)
+            mels, durs, Ts, bounds = [None] * N, [None] * N, [None] * N, [None] * N
+            owner = [-1] * S                               # utterance in each slot
+            nxt = 0
+
+            def admit():
+                nonlocal nxt
+                free = [s for s in range(S) if owner[s] < 0]
+                n = min(len(free), N - nxt)
+                if n == 0:
+                    return
+                grp = list(range(nxt, nxt + n))
+                dur, Tb, T, memory, fm2 = self._prefill_rows("str.adm.", [utterances[i] for i in grp],
+                                                             [stress[i] for i in grp] if stress is not None else None,
+                                                             [lens_p[i] for i in grp], first=nxt, frame_limit=cap)
+                rb = []
+                for r, i in enumerate(grp):
+                    b3 = self._generation_bounds(Tb[r], max_len, min_len_ratio, min_len_floor, max_len_ratio, min(max_len_cap, cap),
+                                                 who=f"utterance {i}: ")
+                    if b3[2] < 1:
+                        raise ValueError(f"utterance {i}: generation bound {b3[2]} leaves no frame")
+                    if b3[2] > cap:
+                        raise ValueError(f"utterance {i}: generation bound {b3[2]} exceeds slot_frames ({cap})")
+                    rb.append(b3)
+                    durs[i], Ts[i], bounds[i] = dur[r, :lens_p[i]].clone(), Tb[r], b3
+                kv_n = self._buf("str.adm.dec.ca.kv_n_all", n * T, W, dtype=ddt)      # (_expand_fwd -> _cross_kv_fwd_all wrote it)
+                dev = torch.tensor([free[:n]] + [[r[k] for r in rb] for k in range(3)], dtype=torch.int32).to(self.device)   # slots | bounds [3, n]
+                kk.call("kk_slot_admit", kv_n, pool, fm2, fmask, dev[0], dev[1:], st["t"], st["done"], st["frames"], st["clen"], st["min"],
+                        st["exp"], st["max"], mel_all, st["live"], n, T, S, cap, W * kv_n.element_size(), L1, M)
+                for r, i in enumerate(grp):
+                    owner[free[r]] = i
+                nxt += n
+
+            def step():
+                self._stream_step(S, cap, stop_threshold, post_expected_stop_threshold)
+
+            admit()
+            graph, graph_at = None, None
+            while any(o >= 0 for o in owner):
+                for _ in range(check_every):
+                    if graph is not None and self.ws_generation != graph_at:
+                        graph = None                       # an admission regrew a workspace or evicted tables: the addresses are stale
+                    if graph is not None:
+                        graph.replay()
+                        continue
+                    step()                                 # frame 0 eagerly: it sizes the workspaces a capture may not allocate
+                    if decode_graph:
+                        with self.capture_lock:
+                            torch.cuda.synchronize()
+                            g = torch.cuda.CUDAGraph()
+                            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                                step()
+                        graph, graph_at = g, self.ws_generation
+                host = st["all"][1:3].cpu().tolist()       # done | frames: the one copy of a harvest
+                for s in range(S):
+                    if owner[s] >= 0 and host[0][s]:
+                        mels[owner[s]] = mel_all[s, 1:host[1][s] + 1].clamp(min=-11.5, max=2.0).clone()
+                        owner[s] = -1
+                admit()
+            if want_info:
+                return mels, {"durations": durs, "T": Ts, "bounds": bounds}
             return mels
         finally:
             self.train_dropout = saved_drop

@@ -228,6 +228,11 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_groupnorm_relu_rows_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _U, _F, _P],
     "kk_varpred_row_mask": [_P, _P, _P, _I, _I, _I, _P],
     "kk_decode_epilogue_rows": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "kk_attn_decode_rows": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P],
+    "kk_decode_prologue_rows": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "kk_decode_cache_append_rows": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "kk_decode_epilogue_slots": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "kk_slot_admit": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _I, _P],
     "kk_voc_conv1d": [_P, _L, _I, _P, _I, _I, _P, _P, _I, _I, _I, _F, _P, _I, _P, _P, _I, _I, _P],
     "kk_voc_convt1d": [_P, _L, _I, _P, _I, _I, _P, _P, _I, _I, _I, _F, _P, _I, _I, _P],
     "kk_voc_convt_taps": [_I, _I, _P],
