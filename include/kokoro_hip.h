@@ -493,6 +493,33 @@ int kk_resample(const float *wave, const int64_t *woff_in, const float *peak, co
 /* wave[b] /= peak[b] + 1e-9 in place (max_samples: the longest utterance) */
 int kk_resample_normalise(float *wave, const int64_t *woff, int B, int64_t max_samples, const float *peak, void *stream);
 
+/* ---- dynamic time warping of mel pairs (kokoro_ruslan_amd/dtw.py; kk_dtw.hip): the alignment behind MCD-DTW ----
+ * A ragged batch of B pairs: side a (synthesized) and side b (ground truth) each packed back to back along time, aoff / boff: int32
+ * [B + 1].  1 <= Ta, Tb <= 4096 (the caller checks; a pair outside is skipped).  No output of a pair depends on the batch. */
+/* cells of an anti-diagonal one pass of kk_dtw covers (its workgroup size) */
+int kk_dtw_tile(void);
+/* cep[k - 1][t] = sum over ascending m of mel[t][m] table[k - 1][m] (an fp32 fmaf chain), k = 1..K <= 32, M <= 128: the orthonormal
+ * DCT-II without its 0th coefficient when table[k - 1][m] = sqrt(2 / M) cos(pi k (m + 0.5) / M).  The table comes from the HOST
+ * (evaluated in fp64, rounded once to fp32, the scale folded in); nothing is evaluated in the kernel.  mel: [T_total, M]; cep:
+ * [K][T_total].  A frame's cepstrum depends on that frame's values alone: identical frames give identical bits */
+int kk_mcep(const float *mel, int64_t T_total, int M, int K, const float *table, float *cep, void *stream);
+/* one workgroup per pair: D(0, 0) = d(0, 0), D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), d(i, j) = sqrt(sum_k
+ * (ca_k[i] - cb_k[j])^2), in fp32, no band; total[b] = D(Ta-1, Tb-1).  dir: the predecessor of every cell as 2 bits (0: (i-1, j-1),
+ * 1: (i-1, j), 2: (i, j-1); ties go to the earlier of that order), cell (i, j) of pair b in bits 2 (j % 16) .. + 1 of word doff[b] + i
+ * ceil(Tb / 16) + j / 16; doff: int64 [B + 1] */
+int kk_dtw(const float *ca, int64_t Ta_total, const float *cb, int64_t Tb_total, int K, const int *aoff, const int *boff,
+           const int64_t *doff, int B, float *total, uint32_t *dir, void *stream);
+/* one wave per pair walks dir from (Ta-1, Tb-1) to (0, 0): path: int32 [.][2] = (i, j) in forward order from entry poff[b] (int64
+ * [B + 1], room for Ta + Tb - 1 entries per pair), steps[b] = their count */
+int kk_dtw_backtrack(const uint32_t *dir, const int64_t *doff, const int *aoff, const int *boff, const int64_t *poff, int B, int *path,
+                     int *steps, void *stream);
+/* per pair, over its path: mcd_sum = sum (10 / ln 10) sqrt(2) d(i, j), l1_sum = sum mean_m |xa[i][m] - xb[j][m]| on the log-mels
+ * xa, xb: [T_total, M].  Each thread sums every 256th step, the workgroup adds the partial sums as a fixed tree; these sums are
+ * formed in fp64 from the fp32 inputs */
+int kk_dtw_path_stats(const float *ca, int64_t Ta_total, const float *cb, int64_t Tb_total, int K, const float *xa, const float *xb,
+                      int M, const int *aoff, const int *boff, const int *path, const int64_t *poff, const int *steps, int B,
+                      double *mcd_sum, double *l1_sum, void *stream);
+
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}
  * (transformers.py:16-40,482-487,569-581; the FFN has two dropouts in series, :111).  *seed is read on the device. */

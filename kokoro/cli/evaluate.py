@@ -1,0 +1,125 @@
+"""`kokoro-eval`: free-running evaluation of a kokoro-train checkpoint against the ground-truth mels of a feature cache.
+
+    kokoro-eval --checkpoint CKPT --features CACHE_DIR [--indices ...] [--split val|train|all] [--validation-split 0.1]
+                [--weights auto|ema|model] [--math bf16|f32] [--no-stream] [--slots N] [--batch-size N] [--mcep K]
+                [--stop-threshold X] [--max-len N] [--min-len-ratio R] [--min-len-floor N] [--output REPORT.json]
+
+Synthesizes every selected utterance with the stop rule deciding its length (continuous batching in a pool of --slots rows, or with
+--no-stream in batches of --batch-size), aligns each mel with the cached ground truth by dynamic time warping on K mel cepstra and
+prints, one line per metric, the mean, median and 95th percentile of: mcd_dtw (mel-cepstral distortion along the path, dB),
+mel_l1_dtw (mean |difference| of the aligned log-mels), len_ratio (synthesized / true frames), dur_abs_err (|sum of predicted
+durations - sum of true ones|, frames); plus the share of utterances that ran into their generation bound.  --split val takes the
+utterances `kokoro-train --validation-split` holds out (the same draw: kokoro.data.cached.split_indices), --indices names utterances
+of the cache's length-sorted order instead.  --output writes records, summary, controls and the weights used as JSON."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import List, Optional
+
+import torch
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Free-running evaluation of a Kokoro checkpoint: MCD-DTW against a feature cache")
+    p.add_argument("--checkpoint", required=True)
+    p.add_argument("--features", metavar="CACHE_DIR", required=True, help="precomputed feature cache (*.pt)")
+    p.add_argument("--indices", type=int, nargs="*", default=None, help="utterances of the feature cache (its length-sorted order)")
+    p.add_argument("--split", choices=("val", "train", "all"), default=None, help="default: val (all with --indices)")
+    p.add_argument("--validation-split", type=float, default=0.1)
+    p.add_argument("--weights", choices=("auto", "ema", "model"), default="auto")
+    p.add_argument("--math", choices=("bf16", "f32"), default="bf16")
+    p.add_argument("--no-stream", action="store_true", help="fixed batches of --batch-size instead of continuous batching")
+    p.add_argument("--slots", type=int, default=None, metavar="N", help="rows of the continuous-batching pool (default 32)")
+    p.add_argument("--batch-size", type=int, default=None, metavar="N", help="with --no-stream (default 32)")
+    p.add_argument("--mcep", type=int, default=13, metavar="K", help="cepstral coefficients c1..cK of the distance (default 13)")
+    p.add_argument("--stop-threshold", type=float, default=None)
+    p.add_argument("--max-len", type=int, default=None)
+    p.add_argument("--min-len-ratio", type=float, default=None)
+    p.add_argument("--min-len-floor", type=int, default=None)
+    p.add_argument("--output", metavar="REPORT.json", default=None)
+    return p
+
+
+def check_args(p: argparse.ArgumentParser, args) -> None:
+    if args.indices is not None and args.split is not None:
+        p.error("--indices and --split are alternatives: give one")
+    if args.indices is not None and (not args.indices or min(args.indices) < 0):
+        p.error("--indices needs non-negative utterance numbers")
+    if not (0.0 < args.validation_split < 1.0):
+        p.error("--validation-split must be in (0, 1)")
+    if args.slots is not None and args.no_stream:
+        p.error("--slots is for the continuous-batching pool: not with --no-stream")
+    if args.batch_size is not None and not args.no_stream:
+        p.error("--batch-size needs --no-stream")
+    if args.slots is not None and args.slots < 1:
+        p.error("--slots must be >= 1")
+    if args.batch_size is not None and args.batch_size < 1:
+        p.error("--batch-size must be >= 1")
+    if not (1 <= args.mcep <= 32):
+        p.error("--mcep must be in 1..32")
+
+
+def select_indices(n: int, split: Optional[str], validation_split: float, indices: Optional[List[int]]) -> List[int]:
+    """Utterances of an n-utterance cache (length-sorted order): --indices as given, else the trainer's split."""
+    if indices is not None:
+        return list(indices)
+    from kokoro.data.cached import split_indices
+    if split == "all":
+        return list(range(n))
+    train, val = split_indices(n, validation_split)
+    return train if split == "train" else val
+
+
+def read_features(cache_dir: str, split: Optional[str], validation_split: float, indices: Optional[List[int]]):
+    """(names, ids, stress, mels [T, M], durations) of the selected utterances."""
+    from kokoro.data.cached import CachedFeatureDataset, scan_cache
+    metas = scan_cache(cache_dir)
+    sel = select_indices(len(metas), split or "val", validation_split, indices)
+    ds = CachedFeatureDataset(cache_dir, indices=sel, memory_cache=False, metas=metas)
+    names, ids, stress, mels, durs = [], [], [], [], []
+    for i in range(len(ds)):
+        it = ds[i]
+        names.append(os.path.splitext(ds.samples[i]["file"].name)[0])
+        ids.append(it["phoneme_indices"].to(torch.int64))
+        stress.append(it["stress_indices"].to(torch.int64))
+        mels.append(it["mel_spec"].t().contiguous().float())
+        durs.append(it["phoneme_durations"].to(torch.int64))
+    return names, ids, stress, mels, durs
+
+
+def main(argv=None) -> int:
+    from kokoro.inference import evaluate as E
+    from kokoro.inference import synth as S
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_args(parser, args)
+    names, ids, stress, mels, durs = read_features(args.features, args.split, args.validation_split, args.indices)
+    if not names:
+        parser.error("the selection is empty: nothing to evaluate")
+    engine, controls, used = S.load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,
+                                                  stop_threshold=args.stop_threshold, min_len_ratio=args.min_len_ratio,
+                                                  min_len_floor=args.min_len_floor)
+    if engine.dims.mel != mels[0].shape[1]:
+        parser.error(f"the checkpoint makes {engine.dims.mel} mel channels, the cache holds {mels[0].shape[1]}")
+    records, summary = E.evaluate(engine, ids, stress, mels, stream=not args.no_stream, slots=32 if args.slots is None else args.slots,
+                                  batch_size=32 if args.batch_size is None else args.batch_size, durations=durs, names=names,
+                                  mcep=args.mcep, **controls.kwargs())
+    print(f"kokoro-eval: {summary['utterances']} utterances ({used} weights, {controls}), "
+          f"{100.0 * summary['hit_bound_share']:.1f} % ended at their generation bound")
+    for k in E.METRICS:
+        if k in summary:
+            s = summary[k]
+            print(f"{k:12s} mean {s['mean']:.4f}  median {s['median']:.4f}  p95 {s['p95']:.4f}")
+    if args.output:
+        with open(args.output, "w") as f:
+            json.dump({"records": records, "summary": summary, "controls": controls.kwargs(), "weights": used, "mcep": args.mcep,
+                       "split": "indices" if args.indices is not None else (args.split or "val"), "checkpoint": args.checkpoint}, f, indent=1)
+        print(f"kokoro-eval: report -> {args.output}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

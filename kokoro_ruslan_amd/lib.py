@@ -250,6 +250,11 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_resample_supported": [_I, _I, _I],
     "kk_resample": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
     "kk_resample_normalise": [_P, _P, _I, _L, _P, _P],
+    "kk_dtw_tile": [],
+    "kk_mcep": [_P, _L, _I, _I, _P, _P, _P],
+    "kk_dtw": [_P, _L, _P, _L, _I, _P, _P, _P, _I, _P, _P, _P],
+    "kk_dtw_backtrack": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "kk_dtw_path_stats": [_P, _L, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
     "kk_losses_finalize": [_P, C.POINTER(KkLossCfg), _P, _I, _P, _P, _P, _I, _P],
     "kk_losses_bwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _P, _P],
