@@ -1,4 +1,4 @@
-// Body of attn_bwd_dkv3_kernel (kk_attn.hip): the dK/dV kernel as ONE wave group — four waves (32 keys each, every query tile),
+// Body of attn_bwd_dkv3_kernel (kk_attn_bwd.hip): the dK/dV kernel as ONE wave group — four waves (32 keys each, every query tile),
 // 70 KB of LDS, two workgroups per CU; no merge of two groups' partial dK / dV.  `a` is the kernel's by-value AttnArgs parameter.
 // The K / V row images of the prologue lie in ring stage 2 and a 16 KB extra area (tile 2 is issued behind the loop's first barrier);
 // the head-norm epilogues' images are fetched after the loop: raw K | cos | sin over the ring, raw V behind the store tiles.

@@ -1,4 +1,4 @@
-// Body of attn_bwd_dq2_kernel (kk_attn.hip); `a` is the kernel's by-value AttnArgs parameter.
+// Body of attn_bwd_dq2_kernel (kk_attn_bwd.hip); `a` is the kernel's by-value AttnArgs parameter.
     typedef __bf16 T;
     constexpr int NS = 3, KIMG = 64 * 64 * 2, STAGE = 2 * KIMG, GSZ = NS * STAGE, STEP = 128;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];        // [group][stage][K | V], mask words, 3 x 16 KB images

@@ -1,4 +1,4 @@
-// Body of attn_bwd_dq3_kernel (kk_attn.hip): the dQ kernel as ONE wave group — four waves, 66 KB of LDS, two workgroups per CU.
+// Body of attn_bwd_dq3_kernel (kk_attn_bwd.hip): the dQ kernel as ONE wave group — four waves, 66 KB of LDS, two workgroups per CU.
 // `a` is the kernel's by-value AttnArgs parameter.  Differences from kk_attn_bwd_dq2.inc: every wave walks ALL key tiles (no merge of
 // two groups' partial dQ); the Q / dO row images of the prologue lie in ring stage 2 and a 16 KB extra area (tile 2 is issued behind
 // the first barrier of the loop, when every wave holds its row fragments); the head-norm epilogue's images are fetched after the

@@ -9,8 +9,9 @@
 // in the XCD's L2), sc1 loads on the reading side (L1 bypass, served by that L2) — no write-through round trip, no fence.
 //
 // How it is built.  The phases ARE the library's kernels: their bodies (g16x_body, attn_fwd3_body, gemm16_body, sublayer_out_row)
-// are compiled into this translation unit from the same sources (KK_BODIES_ONLY drops the host code, KK_A_AUX / KK_QKV_AUX set the
-// cache policy of the activation loads), and their ARGUMENT BLOCKS are the ones the library's own entry points build: between
+// are compiled into this translation unit from the same sources (KK_BODIES_ONLY drops the host code of the three .hip files, the
+// attention body comes from its own headers; KK_A_AUX / KK_QKV_AUX set the cache policy of the activation loads), and their
+// ARGUMENT BLOCKS are the ones the library's own entry points build: between
 // kk_chain_begin() and kk_chain_launch() the entry points record the launch they would have made instead of making it (kk_common.h:
 // kk_capture).  Same tile policy, same arguments, same arithmetic in the same order — the chained launch stores the bits the four
 // launches store (tests/test_chain_gpu.py), and anything it does not recognise is refused (the caller then launches as before).
@@ -40,7 +41,8 @@ namespace chain_g {
 #include "kk_gemm16.hip"
 }
 namespace chain_a {
-#include "kk_attn.hip"
+#include "kk_attn.h"
+#include "kk_attn_fwd3.h"
 }
 namespace chain_t {
 #include "kk_dropout.hip"

@@ -301,7 +301,7 @@ __device__ __forceinline__ void phase_qkv(const Ctx &c, const KkEncLayer &L) {
 }
 
 // ---- phase 2: attention of one head (all S <= 128 keys in one pass) ----------------------------------------------------
-// Same orientation and dropout function as kk_attn.hip (attn_fwd_kernel / ProbDrop): S^T = K.Q^T with a lane owning one
+// Same orientation and dropout function as attn_fwd_kernel (kk_attn_fwd.hip) / ProbDrop (kk_attn.h): S^T = K.Q^T with a lane owning one
 // query, so the softmax is in-lane + one xor-32 exchange and P feeds the second MFMA as it lies in the accumulators.
 struct ProbDropE {
     uint32_t thr, key, sk2;

@@ -14,7 +14,7 @@
 namespace {
 
 // ------------------------------------------------------------------ decode attention with a per-row key count
-// attn_decode_kernel (kk_attn.hip) with the key loops bounded by klen[s] instead of Sk and explicit slot strides: 1024 threads, key j in
+// attn_decode_kernel (kk_attn_fwd.hip) with the key loops bounded by klen[s] instead of Sk and explicit slot strides: 1024 threads, key j in
 // group j % 256, 4 lanes x 16 dims, scores in LDS between the max pass and the exp / P.V pass, the same shuffle and LDS reduction
 // order — so a row's bits are those of kk_attn_fwd at Sq = 1 over the same live keys.  Nothing at or past klen[s] is loaded.
 struct RowsArgs {

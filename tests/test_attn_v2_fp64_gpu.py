@@ -91,7 +91,7 @@ def test_v2_attention_forward_and_pair_backward_against_fp64(kk, S, causal, mask
         km = kmh.cuda()
     seed = torch.tensor([91], dtype=torch.int32, device="cuda")
     thr = int(p * 65536.0 + 0.5)
-    inv_keep = 65536.0 / (65536 - thr)                    # the kernels' quantised 1 / (1 - p) (kk_attn.hip ProbDrop)
+    inv_keep = 65536.0 / (65536 - thr)                    # the kernels' quantised 1 / (1 - p) (kk_attn.h ProbDrop)
 
     def fwd(v, pdrop, out, lse):
         kk.call("kk_attn_fwd", q_n, k_n, v, out, lse, B, h, S, S, H, 2 * H, v.stride(0), H, km, causal, 0.125, seed, site, pdrop, 1, 1)
