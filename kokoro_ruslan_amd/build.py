@@ -61,14 +61,17 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         if os.path.exists(stamp):
             os.remove(stamp)
     headers = [os.path.join(CSRC, "kk_common.h"), os.path.join(os.path.dirname(HERE), "include", "kokoro_hip.h")]
-    headers += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h") and not f.startswith(("kk_common", "kk_attn"))]      # included widely
+    headers += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h") and not f.startswith(("kk_common", "kk_attn", "kk_gemm16_", "kk_gemm16x_"))]      # included widely
     attn_h, incs = ["kk_attn.h", "kk_attn_host.h"], [f for f in sorted(os.listdir(CSRC)) if f.endswith(".inc")]
+    gemm_dev = ["kk_gemm16_dev.h"]      # device code shared by the two bf16 GEMM bodies
     extra_deps = {      # what single sources include besides the headers above
+        "kk_gemm16.hip": gemm_dev + ["kk_gemm16_body.h"],
+        "kk_gemm16x.hip": gemm_dev + ["kk_gemm16x_body.h"],
         "kk_attn.hip": attn_h,
         "kk_attn_fwd.hip": attn_h + ["kk_attn_fwd3.h"],
         "kk_attn_bwd.hip": attn_h + incs,      # the .inc files: bodies of the DMA-staged backward kernels
-        # bodies compiled into kk_chain.hip: three sources under KK_BODIES_ONLY, and the attention forward body from its two device headers
-        "kk_chain.hip": ["kk_gemm16x.hip", "kk_gemm16.hip", "kk_dropout.hip", "kk_attn.h", "kk_attn_fwd3.h"],
+        # bodies compiled into kk_chain.hip: the GEMM and attention forward bodies from their device headers, kk_dropout.hip under KK_BODIES_ONLY
+        "kk_chain.hip": gemm_dev + ["kk_gemm16x_body.h", "kk_gemm16_body.h", "kk_dropout.hip", "kk_attn.h", "kk_attn_fwd3.h"],
     }
 
     def compile_one(src: str) -> str:

@@ -9,8 +9,8 @@
 // in the XCD's L2), sc1 loads on the reading side (L1 bypass, served by that L2) — no write-through round trip, no fence.
 //
 // How it is built.  The phases ARE the library's kernels: their bodies (g16x_body, attn_fwd3_body, gemm16_body, sublayer_out_row)
-// are compiled into this translation unit from the same sources (KK_BODIES_ONLY drops the host code of the three .hip files, the
-// attention body comes from its own headers; KK_A_AUX / KK_QKV_AUX set the cache policy of the activation loads), and their
+// are compiled into this translation unit from the same sources (the GEMM and attention bodies from their device headers; KK_BODIES_ONLY
+// drops the host code of kk_dropout.hip; KK_A_AUX / KK_QKV_AUX set the cache policy of the activation loads), and their
 // ARGUMENT BLOCKS are the ones the library's own entry points build: between
 // kk_chain_begin() and kk_chain_launch() the entry points record the launch they would have made instead of making it (kk_common.h:
 // kk_capture).  Same tile policy, same arguments, same arithmetic in the same order — the chained launch stores the bits the four
@@ -34,11 +34,10 @@
 #include <stdlib.h>
 #include <type_traits>
 
-namespace chain_x {
-#include "kk_gemm16x.hip"
-}
 namespace chain_g {
-#include "kk_gemm16.hip"
+#include "kk_gemm16_dev.h"
+#include "kk_gemm16x_body.h"
+#include "kk_gemm16_body.h"
 }
 namespace chain_a {
 #include "kk_attn.h"
@@ -147,8 +146,8 @@ __global__ __launch_bounds__(512) void chain_sa_fwd_kernel(const ChainSA c) {
     sy.init(c.sync, item, members, c.local_sync != 0);
 
     // ---- phase 1: the item's q|k|v tiles (the XCD sweep of g16x_body IS the item: 256 tiles, 32 per XCD, n fastest)
-    if constexpr (FORM == 0) chain_x::g16x_body<false, false, 128, 192, 3, 3, 2, 2, 4>(c.qkv, wg, chain_smem);
-    else chain_x::g16x_body<false, false, 256, 192, 2, 3, 4, 2, 0>(c.qkv, wg, chain_smem);
+    if constexpr (FORM == 0) chain_g::g16x_body<false, false, 128, 192, 3, 3, 2, 2, 4>(c.qkv, wg, chain_smem);
+    else chain_g::g16x_body<false, false, 256, 192, 2, 3, 4, 2, 0>(c.qkv, wg, chain_smem);
     stamp(1);
     sy.barrier();
     stamp(2);

@@ -1,5 +1,6 @@
 // Argument block and shared constants of the bf16-storage GEMM cores (kk_gemm16.hip: 64x64 / 128x64 tiles, one 32x32
-// accumulator per wave; kk_gemm16x.hip: the large-tile family, several accumulators per wave).
+// accumulator per wave; kk_gemm16x.hip: the large-tile family, several accumulators per wave).  Device code: kk_gemm16_dev.h
+// (shared), kk_gemm16_body.h, kk_gemm16x_body.h (the two bodies, also compiled into kk_chain.hip).
 #pragma once
 #include "kk_common.h"
 
