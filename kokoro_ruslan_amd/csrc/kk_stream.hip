@@ -10,6 +10,7 @@
 //
 // State is int32 throughout (t_rows, done, frames, klen, the three bounds): the host reads done | frames in one copy.
 #include "kk_common.h"
+#include "kk_stop_rule.h"
 
 namespace {
 
@@ -154,6 +155,7 @@ __global__ __launch_bounds__(256) void decode_cache_append_rows_kernel(const T *
 }
 
 // ------------------------------------------------------------------ epilogue: one wave per slot
+// decode_epilogue_rows_kernel (kk_synth.hip) with a frame index per slot: the same decode_row_file_and_stop (kk_stop_rule.h) at t_s.
 __global__ __launch_bounds__(64) void decode_epilogue_slots_kernel(
     const float *__restrict__ frame_out, const float *__restrict__ stop, float *__restrict__ mel_all, float *__restrict__ stop_all,
     int *__restrict__ t_rows, int *__restrict__ done, int *__restrict__ frames, int *__restrict__ live,
@@ -166,29 +168,8 @@ __global__ __launch_bounds__(64) void decode_epilogue_slots_kernel(
         if (lane == 0) { done[b] = 1; frames[b] = t < 0 ? 0 : t; atomicSub(live, 1); }
         return;
     }
-    const float *fo = frame_out + (int64_t)b * M;
-    float *mrow = mel_all + (int64_t)b * L1 * M;
-    double s = 0.0;
-    for (int c = lane; c < M; c += 64) {
-        const float v = fo[c];
-        mrow[(int64_t)(t + 1) * M + c] = v;
-        s += (double)v;
-    }
-    const float logit = stop[b];
-    if (lane == 0) stop_all[(int64_t)b * (L1 - 1) + t] = logit;
-    bool fin = t + 1 >= max_b[b];
-    if (!fin && t >= min_b[b]) {
-        const float thr = t < expected_b[b] ? stop_threshold : fminf(stop_threshold, post_expected_stop_threshold);
-        const float prob = 1.f / (1.f + expf(-logit));
-        if (prob > thr) {
-            fin = true;
-        } else if (t + 1 >= 30) {
-            const float *tail = mrow + (int64_t)(t - 28) * M;             // 29 earlier frames, contiguous
-            for (int i = lane; i < 29 * M; i += 64) s += (double)tail[i];
-            s = wave_sum_d(s);
-            fin = s / (30.0 * M) < -9.5;
-        }
-    }
+    const bool fin = decode_row_file_and_stop(frame_out, stop, mel_all, stop_all + (int64_t)b * (L1 - 1) + t, min_b, expected_b, max_b,
+                                              b, t, lane, L1, M, stop_threshold, post_expected_stop_threshold);
     if (lane == 0) {
         t_rows[b] = t + 1;
         if (fin) {

@@ -9,6 +9,7 @@
 // The per-row length lens[b] plays the part of the sequence length L at B = 1: a chunk is [512k, min(512(k+1), lens[b])), and
 // everything at or past lens[b] is zero, as it would be outside the single-utterance tensor.
 #include "kk_common.h"
+#include "kk_stop_rule.h"
 
 namespace {
 
@@ -124,8 +125,7 @@ __global__ __launch_bounds__(256) void row_mask_kernel(const uint8_t *__restrict
 
 // ------------------------------------------------------------------ decode epilogue with the stop rule of each row
 // One workgroup of 16 waves; wave w owns rows w, w + 16, ...  Everything a wave branches on (done flag, t, the row's bounds, its stop
-// logit) is the same in all its lanes.  The last 30 frames of row b are mel_all rows t-28 .. t (earlier launches) and frame_out (this
-// step's frame), summed in fp64.
+// logit) is the same in all its lanes.  Filing the frame and the stop rule of a row: decode_row_file_and_stop (kk_stop_rule.h).
 constexpr int EPI_WAVES = 16;
 
 __global__ __launch_bounds__(64 * EPI_WAVES) void decode_epilogue_rows_kernel(
@@ -138,29 +138,8 @@ __global__ __launch_bounds__(64 * EPI_WAVES) void decode_epilogue_rows_kernel(
     if (t + 1 < L1) {
         for (int b = wave; b < B; b += EPI_WAVES) {
             if (done[b]) continue;
-            const float *fo = frame_out + (int64_t)b * M;
-            float *mrow = mel_all + (int64_t)b * L1 * M;
-            double s = 0.0;
-            for (int c = lane; c < M; c += 64) {
-                const float v = fo[c];
-                mrow[(int64_t)(t + 1) * M + c] = v;
-                s += (double)v;
-            }
-            const float logit = stop[b];
-            if (lane == 0) stop_all[(int64_t)t * B + b] = logit;
-            bool fin = t + 1 >= max_b[b];
-            if (!fin && t >= min_b[b]) {
-                const float thr = t < expected_b[b] ? stop_threshold : fminf(stop_threshold, post_expected_stop_threshold);
-                const float prob = 1.f / (1.f + expf(-logit));
-                if (prob > thr) {
-                    fin = true;
-                } else if (t + 1 >= 30) {
-                    const float *tail = mrow + (int64_t)(t - 28) * M;         // 29 earlier frames, contiguous
-                    for (int i = lane; i < 29 * M; i += 64) s += (double)tail[i];
-                    s = wave_sum_d(s);
-                    fin = s / (30.0 * M) < -9.5;
-                }
-            }
+            const bool fin = decode_row_file_and_stop(frame_out, stop, mel_all, stop_all + (int64_t)t * B + b, min_b, expected_b, max_b,
+                                                      b, t, lane, L1, M, stop_threshold, post_expected_stop_threshold);
             if (fin && lane == 0) {
                 done[b] = 1;
                 frames[b] = t + 1;

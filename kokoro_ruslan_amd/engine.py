@@ -376,6 +376,15 @@ class KokoroEngine:
             self.math, self.enc_dt, self.dec_dt, self.use_shadow = saved
 
     @contextlib.contextmanager
+    def _no_dropout(self):
+        """Run the enclosed launches with every dropout and stochastic-depth rate at 0 (_p, _dpr): the generate* methods."""
+        saved, self.train_dropout = self.train_dropout, False
+        try:
+            yield self
+        finally:
+            self.train_dropout = saved
+
+    @contextlib.contextmanager
     def ema_weights(self):
         """Run the enclosed forward passes on the EMA replica (reference validation, trainer.py:1771-1790) by pointing the
         parameter views at the EMA slab — no copy, and nothing but two references to restore if the block raises.  Only
@@ -779,10 +788,9 @@ class KokoroEngine:
 
     # ------------------------------------------------------------------ attention sub-layer
     def _attn_fwd(self, key, prefix, xq, xkv, B, Sq, Sk, rope, causal, key_mask, x_res, x_out, site=0, p=0.0, dpr=0.0, next_ln=None,
-                  layer=0, kv_ns=""):
+                  layer=0):
         """x_out = x_res + w_o(attention(...)) + b_o.  xq [B*Sq,H] (post-LN), xkv [B*Sk,H] (None = self-attention).
-        Returns LayerNorm_next_ln(x_out) when the fused dropout tail computed it, else None.  kv_ns: key prefix of the cross-attention
-        K|V buffers (_cross_kv)."""
+        Returns LayerNorm_next_ln(x_out) when the fused dropout tail computed it, else None."""
         P, H, h = self.arena.P, self.dims.hidden, self.dims.heads
         Nq, Nk = B * Sq, B * Sk
         dt = xq.dtype                                   # storage of every activation of the sub-layer
@@ -795,7 +803,7 @@ class KokoroEngine:
             q_raw, k_raw, v_raw, q_n, k_n, v_n = raw, raw[:, H:], raw[:, 2 * H:], nrm, nrm[:, H:], nrm[:, 2 * H:]
         else:
             q_raw, q_n = self._buf(key + ".q_raw", Nq, H, dtype=dt), self._buf(key + ".q_n", Nq, H, dtype=dt)
-            kv_raw, kv_n = self._cross_kv(layer, Nk, dt, ns=kv_ns)                    # filled by _cross_kv_fwd_all
+            kv_raw, kv_n = self._cross_kv(layer, Nk, dt)                              # filled by _cross_kv_fwd_all
             self._proj_headnorm(xq, self._W(prefix + ".w_q.weight"), q_raw, q_n, Sq, (gq,), 0, None, None)
             k_raw, v_raw, k_n, v_n = kv_raw, kv_raw[:, H:], kv_n, kv_n[:, H:]
         ctx, lse = self._buf(key + ".ctx", Nq, H, dtype=dt), self._buf(key + ".lse", B, h, Sq)
@@ -1629,55 +1637,78 @@ class KokoroEngine:
         return out
 
     # ------------------------------------------------------------------ inference
-    def _decode_step(self, ns, B, T, max_expected, memory, fm2):
-        """The launches of one decoder step at Sq = 1 up to the stop logits; returns (frame_out [B, mel], stop_now [B]), which the
-        epilogue of generate / generate_batch files under frame t.  The step's state is the workspace entries under the key prefix
-        `ns` ("gen" / "syn") that _decode_state_init reset; the cross-attention K|V are those of _expand_fwd ("" for "gen", else
-        `ns` + ".")."""
-        d, P, H, M, h = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dims.heads
-        ddt = self.dec_dt
-        BH, L1 = B * H, max_expected + 1
-        kv_ns = "" if ns == "gen" else ns + "."
-        pe = P["positional_encoding.pe"].view(d.max_len, H)
-        cos, sin = self._rope_tables(d.max_len)
-        Kc = [self._buf(f"{ns}.dec{i}.kcache", max_expected, BH, dtype=ddt) for i in range(d.dec_layers)]
-        Vc = [self._buf(f"{ns}.dec{i}.vcache", max_expected, BH, dtype=ddt) for i in range(d.dec_layers)]
-        mel_out, y = self._buf(f"{ns}.mel", B, L1, M), self._buf(f"{ns}.y", B, H)
-        t_dev, kmask = self._buf(f"{ns}.t", 1, dtype=torch.int32), self._buf(f"{ns}.kmask", 1, max_expected, dtype=torch.uint8)
-        frame_in, frame_out, stop_now = self._buf(f"{ns}.frame_in", B, M), self._buf(f"{ns}.frame_out", B, M), self._buf(f"{ns}.stop_now", B)
-        pe_row, cos_row, sin_row = self._buf(f"{ns}.pe_row", 1, H), self._buf(f"{ns}.cos_row", 1, 64), self._buf(f"{ns}.sin_row", 1, 64)
-        kk.call("kk_decode_prologue", mel_out, frame_in, pe, pe_row, cos, sin, cos_row, sin_row, kmask, t_dev, B, L1, M, H)
-        # mel_projection_in + positional encoding at offset t (model.py:541-545)
-        self._linear(frame_in, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], y, res=pe_row, res_mod=1)
+    def _decoder_step(self, ns, rows, pe_res, res_mod, cos, sin, S, split_k, self_attn, cross_attn):
+        """The decoder at Sq = 1 for `rows` rows on the workspace keys `ns`.*, from the mel input projection of frame_in (written, like
+        the positional operands, by the caller's prologue kernel) to (frame_out [rows, mel], stop_now [rows]) for its epilogue kernel.
+        The callers (_decode_step: every row at one frame; _stream_step: each at its own) differ in the positional rows pe_res /
+        cos / sin (one for all: res_mod = 1, S = 1; one per row: res_mod = 0, S = rows), in split_k of the step's GEMMs, and in
+        self_attn(i, key, nrm [rows, 3H]) (append q|k|v to layer i's cache, attend over it) and cross_attn(i, key, q_n [rows, H])
+        (attend over layer i's K|V of the expanded memory), which return ctx [rows, H]."""
+        d, P, H, M, ddt = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dec_dt
+        frame_in, y = self._buf(f"{ns}.frame_in", rows, M), self._buf(f"{ns}.y", rows, H)
+        frame_out, stop_now = self._buf(f"{ns}.frame_out", rows, M), self._buf(f"{ns}.stop_now", rows)
+        # mel_projection_in + positional encoding at the row's frame (model.py:541-545)
+        self._linear(frame_in, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], y, res=pe_res, res_mod=res_mod, split_k=split_k)
         n1 = self._ln_fwd(f"{ns}.dec0.ln1", y, "decoder.layers.0.norm1", ddt)
         yl = y
         for i in range(d.dec_layers):
             pf, key = f"decoder.layers.{i}", f"{ns}.dec{i}"
-            gq, gk, gv = P[pf + ".self_attn.q_norm.weight"], P[pf + ".self_attn.k_norm.weight"], P[pf + ".self_attn.v_norm.weight"]
-            raw, nrm = self._buf(key + ".qkv_raw", B, 3 * H, dtype=ddt), self._buf(key + ".qkv_n", B, 3 * H, dtype=ddt)
-            self._proj_headnorm(n1, self._Wf(pf + ".self_attn.w_q.weight", 3), raw, nrm, 1, (gq, gk, gv), 2, cos_row, sin_row)
-            qb = self._buf(key + ".q", 1, BH, dtype=ddt)
-            kk.call("kk_decode_cache_append", nrm, qb, Kc[i], Vc[i], t_dev, B, H, _b16(nrm))
-            ctx, lse = self._buf(key + ".ctx", 1, BH, dtype=ddt), self._buf(key + ".lse", 1, B * h, 1)
-            kk.call("kk_attn_fwd", qb, Kc[i], Vc[i], ctx, lse, 1, B * h, 1, max_expected, BH, BH, BH, BH, kmask, 0, 0.125, self.rng,
-                    0, 0.0, self.math, _b16(qb))
-            proj = self._buf(f"tmp.{ns}_proj", B, H)
-            self._linear(ctx.view(B, H), self._W(pf + ".self_attn.w_o.weight"), P[pf + ".self_attn.w_o.bias"], proj)
-            ya = self._buf(key + ".xa", B, H)
+            sp, cp = pf + ".self_attn", pf + ".cross_attn"
+            raw, nrm = self._buf(key + ".qkv_raw", rows, 3 * H, dtype=ddt), self._buf(key + ".qkv_n", rows, 3 * H, dtype=ddt)
+            # K alone is rotated, by the row's absolute position; the single query by position 0, i.e. not at all (generate)
+            self._proj_headnorm(n1, self._Wf(sp + ".w_q.weight", 3), raw, nrm, S,
+                                (P[sp + ".q_norm.weight"], P[sp + ".k_norm.weight"], P[sp + ".v_norm.weight"]), 2, cos, sin, split_k=split_k)
+            ctx = self_attn(i, key, nrm)
+            proj = self._buf("str.proj" if ns == "str" else f"tmp.{ns}_proj", rows, H)
+            self._linear(ctx, self._W(sp + ".w_o.weight"), P[sp + ".w_o.bias"], proj, split_k=split_k)
+            ya = self._buf(key + ".xa", rows, H)
             n2 = self._sublayer_tail(proj, yl, ya, 1, 0, 0.0, 0.0, 0.0, None, None, (key + ".ln2", pf + ".norm2", ddt))
-            yc = self._buf(key + ".xc", B, H)
-            n3 = self._attn_fwd(key + ".ca", pf + ".cross_attn", n2, memory, B, 1, T, False, False, fm2, ya, yc,
-                                next_ln=(key + ".ln3", pf + ".norm3", ddt), layer=i, kv_ns=kv_ns)
-            yo = self._buf(key + ".xo", B, H)
+            # cross-attention: _attn_fwd's launches without dropout, with the caller's attention kernel
+            q_raw, q_n = self._buf(key + ".ca.q_raw", rows, H, dtype=ddt), self._buf(key + ".ca.q_n", rows, H, dtype=ddt)
+            self._proj_headnorm(n2, self._W(cp + ".w_q.weight"), q_raw, q_n, 1, (P[cp + ".q_norm.weight"],), 0, None, None, split_k=split_k)
+            ctx = cross_attn(i, key, q_n)
+            yc = self._buf(key + ".xc", rows, H)
+            n3 = self._attn_out(key + ".ca", cp, ctx, rows, 1, ya, yc, 0, 0.0, 0.0, (key + ".ln3", pf + ".norm3", ddt), split_k=split_k)
+            yo = self._buf(key + ".xo", rows, H)
             nxt = ((f"{ns}.dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", ddt) if i + 1 < d.dec_layers
                    else (f"{ns}.dec.norm", "decoder.norm", ddt))
-            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=nxt)
+            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=nxt, split_k=split_k)
             yl = yo
-        dec_out = n1
-        self._linear(dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out)
-        kk.call("kk_rowdot_fwd", dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now,
-                B, H, 1, 0, _b16(dec_out))
+        self._linear(n1, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out, split_k=split_k)
+        kk.call("kk_rowdot_fwd", n1, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now, rows, H, 1, 0, _b16(n1))
         return frame_out, stop_now
+
+    def _decode_step(self, ns, B, T, max_expected, fm2):
+        """One decoder step of generate / generate_batch, all B rows at the frame of one device counter: kk_decode_prologue, then
+        _decoder_step; returns its (frame_out [B, mel], stop_now [B]), which the caller's epilogue files under frame t.  The state is
+        the workspace entries under `ns` ("gen" / "syn") that _decode_state_init reset.  Self-attention: one kk_attn_fwd with B*heads
+        "heads" over the time-major caches [t][B*H]; cross-attention over the K|V of _expand_fwd ("" for "gen", else `ns` + ".")."""
+        d, P, H, M, h, ddt = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dims.heads, self.dec_dt
+        BH, L1, kv_ns = B * H, max_expected + 1, "" if ns == "gen" else ns + "."
+        pe, (cos, sin) = P["positional_encoding.pe"].view(d.max_len, H), self._rope_tables(d.max_len)
+        mel_out, frame_in = self._buf(f"{ns}.mel", B, L1, M), self._buf(f"{ns}.frame_in", B, M)
+        t_dev, kmask = self._buf(f"{ns}.t", 1, dtype=torch.int32), self._buf(f"{ns}.kmask", 1, max_expected, dtype=torch.uint8)
+        pe_row, cos_row, sin_row = self._buf(f"{ns}.pe_row", 1, H), self._buf(f"{ns}.cos_row", 1, 64), self._buf(f"{ns}.sin_row", 1, 64)
+        kk.call("kk_decode_prologue", mel_out, frame_in, pe, pe_row, cos, sin, cos_row, sin_row, kmask, t_dev, B, L1, M, H)
+
+        def self_attn(i, key, nrm):
+            Kc, Vc = self._buf(key + ".kcache", max_expected, BH, dtype=ddt), self._buf(key + ".vcache", max_expected, BH, dtype=ddt)
+            qb = self._buf(key + ".q", 1, BH, dtype=ddt)
+            kk.call("kk_decode_cache_append", nrm, qb, Kc, Vc, t_dev, B, H, _b16(nrm))
+            ctx, lse = self._buf(key + ".ctx", 1, BH, dtype=ddt), self._buf(key + ".lse", 1, B * h, 1)
+            kk.call("kk_attn_fwd", qb, Kc, Vc, ctx, lse, 1, B * h, 1, max_expected, BH, BH, BH, BH, kmask, 0, 0.125, self.rng,
+                    0, 0.0, self.math, _b16(qb))
+            return ctx.view(B, H)
+
+        def cross_attn(i, key, q_n):
+            _, kv_n = self._cross_kv(i, B * T, ddt, ns=kv_ns)              # filled by _cross_kv_fwd_all
+            k_n, v_n = kv_n, kv_n[:, H:]
+            ctx, lse = self._buf(key + ".ca.ctx", B, H, dtype=ddt), self._buf(key + ".ca.lse", B, h, 1)
+            kk.call("kk_attn_fwd", q_n, k_n, v_n, ctx, lse, B, h, 1, T, q_n.stride(0), k_n.stride(0), v_n.stride(0), H, fm2, 0, 0.125,
+                    self.rng, 3, 0.0, self.math, _b16(q_n))
+            return ctx
+
+        return self._decoder_step(ns, B, pe_row, 1, cos_row, sin_row, 1, 0, self_attn, cross_attn)
 
     def _encode_text_fwd(self, ns, ids, stress, B, Pn, text_mask):
         """encode_text (model.py:375-388) with dropout off: embedding, the encoder layers under the key mask `text_mask`
@@ -1760,6 +1791,15 @@ class KokoroEngine:
         self._buf(f"{ns}.kmask", 1, max_expected, dtype=torch.uint8).fill_(1)
         return mel_out, self._buf(f"{ns}.stop", max_expected, B), t_dev
 
+    def _capture_step(self, step) -> "torch.cuda.CUDAGraph":
+        """One hipGraph of step(), a decode step that has run eagerly once with the same buffers."""
+        with self.capture_lock:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                step()
+        return g
+
     def _decode_loop(self, step, stop, max_expected, check_every, decode_graph):
         """Run step() for up to max_expected frames; every `check_every` frames and after the last the host asks stop(t), t = the
         frame just decoded (a host sync), and leaves when it says so.  The step's launches take the frame index from device
@@ -1772,11 +1812,7 @@ class KokoroEngine:
             else:
                 step()                                     # frame 0 eagerly: it sizes the workspaces a capture may not allocate
                 if decode_graph and max_expected > 1:
-                    with self.capture_lock:
-                        torch.cuda.synchronize()
-                        step_graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(step_graph, capture_error_mode="thread_local"):
-                            step()
+                    step_graph = self._capture_step(step)
             if ((t + 1) % check_every == 0 or t + 1 == max_expected) and stop(t):
                 break
 
@@ -1807,8 +1843,7 @@ class KokoroEngine:
         ids = ids.to(self.device, torch.int64).contiguous()
         stress = stress.to(self.device, torch.int64).contiguous() if stress is not None else None
         B, Pn = ids.shape
-        saved_drop, self.train_dropout = self.train_dropout, False
-        try:
+        with self._no_dropout():
             text_mask = self._buf("gen.text_mask", B, Pn, dtype=torch.uint8)
             enc = self._encode_text_fwd("", ids, stress, B, Pn, text_mask)
             # ---- duration predictor ----
@@ -1826,7 +1861,7 @@ class KokoroEngine:
             mel_out, stop_logit, t_dev = self._decode_state_init("gen", B, max_expected)
 
             def step():
-                frame_out, stop_now = self._decode_step("gen", B, T, max_expected, memory, fm2)
+                frame_out, stop_now = self._decode_step("gen", B, T, max_expected, fm2)
                 kk.call("kk_decode_epilogue", frame_out, stop_now, mel_out, stop_logit, t_dev, B, max_expected + 1, M)
 
             frames, done = max_expected, 0
@@ -1847,8 +1882,6 @@ class KokoroEngine:
 
             self._decode_loop(step, stop, max_expected, check_every, decode_graph)
             return mel_out[:, 1:frames + 1].clamp(min=-11.5, max=2.0).clone()
-        finally:
-            self.train_dropout = saved_drop
 
     def _check_utterances(self, utterances, stress):
         """The argument checks of generate_batch / generate_stream; returns (stress or None, phonemes per utterance)."""
@@ -1929,8 +1962,7 @@ class KokoroEngine:
         if B == 0:
             return ([], {"durations": [], "T": [], "bounds": []}) if want_info else []
         stress, lens_p = self._check_utterances(utterances, stress)
-        saved_drop, self.train_dropout = self.train_dropout, False
-        try:
+        with self._no_dropout():
             dur, Tb, T, memory, fm2 = self._prefill_rows("syn.", utterances, stress, lens_p)
             bounds = []
             for b, expected in enumerate(Tb):
@@ -1948,7 +1980,7 @@ class KokoroEngine:
             live.fill_(B)
 
             def step():
-                frame_out, stop_now = self._decode_step("syn", B, T, max_expected, memory, fm2)
+                frame_out, stop_now = self._decode_step("syn", B, T, max_expected, fm2)
                 kk.call("kk_decode_epilogue_rows", frame_out, stop_now, mel_out, stop_logit, t_dev, done, frames_d, live, rb[0], rb[1],
                         rb[2], B, max_expected + 1, M, float(stop_threshold), float(post_expected_stop_threshold))
 
@@ -1958,8 +1990,6 @@ class KokoroEngine:
             if want_info:
                 return mels, {"durations": [dur[b, :lens_p[b]].clone() for b in range(B)], "T": Tb, "bounds": bounds}
             return mels
-        finally:
-            self.train_dropout = saved_drop
 
     # ------------------------------------------------------------------ continuous batching
     def _stream_state(self, S, cap):
@@ -1969,60 +1999,37 @@ class KokoroEngine:
                 "max": st[7], "live": self._buf("str.live", 1, dtype=torch.int32)}
 
     def _stream_step(self, S, cap, stop_threshold, post_expected_stop_threshold):
-        """_decode_step + kk_decode_epilogue_rows for a pool of S slots of `cap` frames, every slot at its own frame t_s: the row
-        kernels of kk_stream.hip around the same GEMM / norm launches.  Self-attention: kk_attn_decode_rows over the slot-major
+        """One decoder step of a pool of S slots of `cap` frames, slot s at its own frame t_s: kk_decode_prologue_rows, _decoder_step
+        with the row kernels of kk_stream.hip, kk_decode_epilogue_slots.  Self-attention: kk_attn_decode_rows over the slot-major
         caches [S][cap][H] with klen[s] = t_s + 1 keys (0 for a finished slot), no mask and no zero-filled cache.  Cross-attention:
-        the same kernel over the slot's rows of the K|V pool [S*cap, 2H*layers] with clen[s] = the admitted group's frame count
-        and the slot frame mask [S, cap].  The step's plain GEMMs are launched as one k-slice each (split_k = 1: no fp32 atomics),
-        so a replayed step repeats the bits of the eager one; at a few rows that gives up the k-split's extra workgroups."""
+        the same kernel over the slot's rows of the K|V pool [S*cap, 2H*layers] with clen[s] = the admitted group's frame count and
+        the slot frame mask [S, cap].  The plain GEMMs are one k-slice each (split_k = 1: no fp32 atomics), so a replayed step
+        repeats the bits of the eager one; at a few rows that gives up the k-split's extra workgroups."""
         d, P, H, M, h = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, self.dims.heads
         ddt, L1, W = self.dec_dt, cap + 1, 2 * self.dims.hidden * self.dims.dec_layers
         st = self._stream_state(S, cap)
-        pe = P["positional_encoding.pe"].view(d.max_len, H)
-        cos, sin = self._rope_tables(d.max_len)
-        mel_all, stop_all = self._buf("str.mel", S, L1, M), self._buf("str.stop", S, cap)
+        pe, (cos, sin) = P["positional_encoding.pe"].view(d.max_len, H), self._rope_tables(d.max_len)
+        mel_all, stop_all, frame_in = self._buf("str.mel", S, L1, M), self._buf("str.stop", S, cap), self._buf("str.frame_in", S, M)
         pool, fmask = self._buf("str.dec.ca.kv_n_pool", S * cap, W, dtype=ddt), self._buf("str.fmask", S, cap, dtype=torch.uint8)
-        y, frame_in, frame_out, stop_now = (self._buf("str.y", S, H), self._buf("str.frame_in", S, M), self._buf("str.frame_out", S, M),
-                                            self._buf("str.stop_now", S))
         pe_rows, cos_rows, sin_rows = self._buf("str.pe_rows", S, H), self._buf("str.cos_rows", S, 64), self._buf("str.sin_rows", S, 64)
         kk.call("kk_decode_prologue_rows", mel_all, frame_in, pe, pe_rows, cos, sin, cos_rows, sin_rows, st["t"], st["done"], st["klen"],
                 S, L1, M, H, d.max_len)
-        self._linear(frame_in, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], y, res=pe_rows, res_mod=0, split_k=1)
-        n1 = self._ln_fwd("str.dec0.ln1", y, "decoder.layers.0.norm1", ddt)
-        yl = y
-        for i in range(d.dec_layers):
-            pf, key = f"decoder.layers.{i}", f"str.dec{i}"
-            gq, gk, gv = P[pf + ".self_attn.q_norm.weight"], P[pf + ".self_attn.k_norm.weight"], P[pf + ".self_attn.v_norm.weight"]
-            raw, nrm = self._buf(key + ".qkv_raw", S, 3 * H, dtype=ddt), self._buf(key + ".qkv_n", S, 3 * H, dtype=ddt)
-            # S "positions" with a [S, 64] table: row s is rotated by cos_rows[s] = its own absolute position (K only, as _decode_step)
-            self._proj_headnorm(n1, self._Wf(pf + ".self_attn.w_q.weight", 3), raw, nrm, S, (gq, gk, gv), 2, cos_rows, sin_rows, split_k=1)
+
+        def self_attn(i, key, nrm):
             qb = self._buf(key + ".q", S, H, dtype=ddt)
             Kc, Vc = self._buf(key + ".kcache", S, cap, H, dtype=ddt), self._buf(key + ".vcache", S, cap, H, dtype=ddt)
             kk.call("kk_decode_cache_append_rows", nrm, qb, Kc, Vc, st["t"], st["done"], S, cap, H, _b16(nrm))
             ctx, lse = self._buf(key + ".ctx", S, H, dtype=ddt), self._buf(key + ".lse", S, h)
             kk.call("kk_attn_decode_rows", qb, Kc, Vc, ctx, lse, st["klen"], None, S, h, cap, cap * H, H, cap * H, H, 0.125, _b16(qb))
-            proj = self._buf("str.proj", S, H)
-            self._linear(ctx, self._W(pf + ".self_attn.w_o.weight"), P[pf + ".self_attn.w_o.bias"], proj, split_k=1)
-            ya = self._buf(key + ".xa", S, H)
-            n2 = self._sublayer_tail(proj, yl, ya, 1, 0, 0.0, 0.0, 0.0, None, None, (key + ".ln2", pf + ".norm2", ddt))
-            # cross-attention: _attn_fwd's launches with the row kernel in the place of kk_attn_fwd
-            cp = pf + ".cross_attn"
-            q_raw, q_n = self._buf(key + ".ca.q_raw", S, H, dtype=ddt), self._buf(key + ".ca.q_n", S, H, dtype=ddt)
-            self._proj_headnorm(n2, self._W(cp + ".w_q.weight"), q_raw, q_n, 1, (P[cp + ".q_norm.weight"],), 0, None, None, split_k=1)
+            return ctx
+
+        def cross_attn(i, key, q_n):
             k_n, v_n = pool[:, 2 * H * i:], pool[:, 2 * H * i + H:]
-            cctx, clse = self._buf(key + ".ca.ctx", S, H, dtype=ddt), self._buf(key + ".ca.lse", S, h)
-            kk.call("kk_attn_decode_rows", q_n, k_n, v_n, cctx, clse, st["clen"], fmask, S, h, cap, cap * W, W, cap * W, W, 0.125, _b16(q_n))
-            yc = self._buf(key + ".xc", S, H)
-            n3 = self._attn_out(key + ".ca", cp, cctx, S, 1, ya, yc, 0, 0.0, 0.0, (key + ".ln3", pf + ".norm3", ddt), split_k=1)
-            yo = self._buf(key + ".xo", S, H)
-            nxt = ((f"str.dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", ddt) if i + 1 < d.dec_layers
-                   else ("str.dec.norm", "decoder.norm", ddt))
-            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=nxt, split_k=1)
-            yl = yo
-        dec_out = n1
-        self._linear(dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out, split_k=1)
-        kk.call("kk_rowdot_fwd", dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now,
-                S, H, 1, 0, _b16(dec_out))
+            ctx, lse = self._buf(key + ".ca.ctx", S, H, dtype=ddt), self._buf(key + ".ca.lse", S, h)
+            kk.call("kk_attn_decode_rows", q_n, k_n, v_n, ctx, lse, st["clen"], fmask, S, h, cap, cap * W, W, cap * W, W, 0.125, _b16(q_n))
+            return ctx
+
+        frame_out, stop_now = self._decoder_step("str", S, pe_rows, 0, cos_rows, sin_rows, S, 1, self_attn, cross_attn)
         kk.call("kk_decode_epilogue_slots", frame_out, stop_now, mel_all, stop_all, st["t"], st["done"], st["frames"], st["live"],
                 st["min"], st["exp"], st["max"], S, L1, M, float(stop_threshold), float(post_expected_stop_threshold))
 
@@ -2062,8 +2069,7 @@ class KokoroEngine:
         if cap > 8192:
             raise ValueError(f"slot_frames {cap} exceeds the decode attention's 8192 keys")
         stress, lens_p = self._check_utterances(utterances, stress)
-        saved_drop, self.train_dropout = self.train_dropout, False
-        try:
+        with self._no_dropout():
             ddt, L1, W = self.dec_dt, cap + 1, 2 * H * d.dec_layers
             st = self._stream_state(S, cap)
             mel_all = self._buf("str.mel", S, L1, M)
@@ -2105,26 +2111,18 @@ class KokoroEngine:
                     owner[free[r]] = i
                 nxt += n
 
-            def step():
-                self._stream_step(S, cap, stop_threshold, post_expected_stop_threshold)
-
+            step = lambda: self._stream_step(S, cap, stop_threshold, post_expected_stop_threshold)
             admit()
             graph, graph_at = None, None
             while any(o >= 0 for o in owner):
                 for _ in range(check_every):
-                    if graph is not None and self.ws_generation != graph_at:
-                        graph = None                       # an admission regrew a workspace or evicted tables: the addresses are stale
-                    if graph is not None:
+                    if graph is not None and self.ws_generation == graph_at:
                         graph.replay()
                         continue
-                    step()                                 # frame 0 eagerly: it sizes the workspaces a capture may not allocate
+                    # no graph yet, or an admission regrew a workspace or evicted tables and its addresses are stale: this step
+                    step()                                 # eagerly (it sizes the workspaces a capture may not allocate)
                     if decode_graph:
-                        with self.capture_lock:
-                            torch.cuda.synchronize()
-                            g = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                                step()
-                        graph, graph_at = g, self.ws_generation
+                        graph, graph_at = self._capture_step(step), self.ws_generation
                 host = st["all"][1:3].cpu().tolist()       # done | frames: the one copy of a harvest
                 for s in range(S):
                     if owner[s] >= 0 and host[0][s]:
@@ -2134,8 +2132,6 @@ class KokoroEngine:
             if want_info:
                 return mels, {"durations": durs, "T": Ts, "bounds": bounds}
             return mels
-        finally:
-            self.train_dropout = saved_drop
 
     # ------------------------------------------------------------------ optimizer boundary
     def _opt_cfg(self, mel_length: int) -> kk.KkOptCfg:

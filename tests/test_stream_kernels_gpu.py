@@ -156,14 +156,15 @@ def test_decode_cache_append_rows(kk, bf16):
 
 def test_decode_epilogue_slots(kk):
     """Row 0 stops by the threshold, row 2 by the quiet output, row 3 by max_b, row 5 by the post-expected threshold; rows 1 and 6
-    go on (6 past frame 30 with a loud output); row 4 is finished and must stay byte-identical."""
+    go on (1 with the stop head firing below its min, 6 past frame 30 with a loud output); row 4 is finished and must stay
+    byte-identical."""
     g = torch.Generator().manual_seed(6)
     mel0 = torch.randn(S2, L1, M, generator=g)
     mel0[2, 5:34] = -10.0                                      # rows t - 28 .. t of slot 2 (t = 33)
     frame_out = torch.randn(S2, M, generator=g)
     frame_out[2] = -10.0
-    stop = torch.tensor([5.0, -5.0, -5.0, -5.0, 5.0, 0.0, -5.0])
-    min_b = [0, 0, 0, 100, 0, 0, 0]
+    stop = torch.tensor([5.0, 5.0, -5.0, -5.0, 5.0, 0.0, -5.0])
+    min_b = [0, 8, 0, 100, 0, 0, 0]
     exp_b = [10, 10, 40, 40, 10, 20, 40]
     max_b = [40, 40, 40, 40, 40, 40, 40]
     stop_all0 = torch.randn(S2, CAP2, generator=g)
