@@ -520,6 +520,38 @@ int kk_dtw_path_stats(const float *ca, int64_t Ta_total, const float *cb, int64_
                       int M, const int *aoff, const int *boff, const int *path, const int64_t *poff, const int *steps, int B,
                       double *mcd_sum, double *l1_sum, void *stream);
 
+/* ---- flat-start forced alignment of phoneme tokens to mel frames (kokoro_ruslan_amd/align.py; kk_align.hip) ----
+ * A ragged batch of B utterances: frames packed back to back, foff: int32 [B + 1]; tokens packed back to back, poff: int32 [B + 1].
+ * 1 <= P <= kk_align_max_tokens(), 1 <= T <= 4096 (the caller checks; an utterance outside is skipped).  feats, viterbi and backtrack
+ * compute nothing of an utterance that depends on the batch; a frame's L depends on that frame alone. */
+/* tokens of an utterance kk_align_viterbi takes (the size of its workgroup) */
+int kk_align_max_tokens(void);
+/* feat [D][T_total], D = 2 (K + 1), from cep = kk_mcep's [K][T_total] (NULL when K = 0) and the log-mel [T_total, M]: rows 0..K-1
+ * c_1..c_K, row K the frame's mean over the mel channels, each minus the utterance's mean over time (a fixed-order sum); rows
+ * K+1..2K+1 their first differences (x(t+1) - x(t-1)) / 2, the edge frames replicated */
+int kk_align_feats(const float *cep, const float *mel, int64_t T_total, int M, int K, const int *foff, int B, float *feat,
+                   void *stream);
+/* L[v][t] = sum over ascending d of a[v][d] (feat[d][t] - mu[v][d])^2 (one fp32 fmaf chain) + c[v]; a = -1/2 / var, mu, c = -1/2
+ * sum_d ln(2 pi var): [V][D], [V][D], [V] from the HOST (fp64, rounded once).  D <= 64, V <= 256; L: [V][T_total] */
+int kk_align_loglik(const float *feat, int64_t T_total, int D, int V, const float *a, const float *mu, const float *c, float *L,
+                    void *stream);
+/* one workgroup of `threads` (a multiple of 64 >= every P) per utterance: S(p, t) = L[ids[p]][t] + max(S(p, t-1), S(p-1, t-1),
+ * S(p-2, t-1) if opt[p-1]), a later candidate only when strictly greater; S(0, 0) = L[ids[0]][0] and, if opt[0], S(1, 0) =
+ * L[ids[1]][0]; the end state is P-1, or P-2 when opt[P-1] and that cell is strictly greater.  score[b] = S(end, T-1) and end[b],
+ * or -inf and -1 when no path exists.  codes: the candidate of every cell as 2 bits (0 stay, 1 advance, 2 skip), token p at frame t
+ * of utterance b in word coff[b] + t ceil(P / 16) + p / 16: its low bit at bit p % 16, its high bit at bit 16 + p % 16; coff: int64
+ * [B + 1] */
+int kk_align_viterbi(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff, const int *poff,
+                     const int64_t *coff, int B, int threads, float *score, int *end, uint32_t *codes, void *stream);
+/* one wave per utterance walks codes from end[b] back to frame 0: durations [P_total] (frames per token, 0 for a skipped one) and
+ * label [T_total] (the phoneme id of every frame); an infeasible utterance gets durations 0 and labels -1 */
+int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids, const int *end,
+                       int B, int *durations, int *label, void *stream);
+/* per class v < V over the frames with label[t] == v: count [V], sum [V][D] and sumsq [V][D] of feat [D][T_total] in fp64, by
+ * fixed-order partial sums and a fixed tree (no atomics: two runs give the same bits) */
+int kk_align_accumulate(const float *feat, const int *label, int64_t T_total, int D, int V, int64_t *count, double *sum,
+                        double *sumsq, void *stream);
+
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}
  * (transformers.py:16-40,482-487,569-581; the FFN has two dropouts in series, :111).  *seed is read on the device. */

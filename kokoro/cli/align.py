@@ -1,0 +1,139 @@
+"""`kokoro-align`: phoneme durations for a feature cache by flat-start forced alignment on the device (no external aligner).
+
+    kokoro-align --cache-dir DIR [--iters N] [--optional-id ID ...] [--batch-size N] [--var-floor F] [--mcep K] [--n-classes V]
+                 [--model-in FILE | --model-out FILE] [--output FILE.jsonl] [--write-cache]
+
+Reads the schema-v7 entries of a feature cache (mel_spec, phoneme_indices), fits one diagonal Gaussian per phoneme id by Viterbi
+training from the even split (kokoro_ruslan_amd.align.PhoneAligner.fit) -- or, with --model-in, loads a fitted model and only aligns --
+and gives every utterance the durations of its best path: frames per phoneme, summing to mel_length.  --optional-id names phoneme ids
+whose tokens may get no frame (a silence the speaker did not make; there is no default: the id of <sil> is the vocabulary's business).
+--output writes one {"name", "phoneme_durations"} line per utterance, the field kokoro-precompute --ids accepts; --write-cache replaces
+phoneme_durations in every entry, atomically.  An utterance that cannot be aligned (more mandatory tokens than frames, or longer than
+the kernels take) keeps the durations it has, is reported on stderr and makes the exit status 1.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import Dict, List
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="kokoro-align", description=__doc__.split("\n\n")[0])
+    p.add_argument("--cache-dir", required=True, metavar="DIR", help="feature cache (*.pt)")
+    p.add_argument("--iters", type=int, default=6, help="passes of Viterbi training (default 6)")
+    p.add_argument("--optional-id", type=int, action="append", default=[], metavar="ID", help="a phoneme id whose tokens may be skipped")
+    p.add_argument("--batch-size", type=int, default=64, help="utterances per device call")
+    p.add_argument("--var-floor", type=float, default=0.01, help="variance floor as a share of the global variance")
+    p.add_argument("--mcep", type=int, default=13, metavar="K", help="cepstral coefficients c1..cK of the features (default 13)")
+    p.add_argument("--n-classes", type=int, default=59, metavar="V", help="phoneme ids (default 59)")
+    m = p.add_mutually_exclusive_group()
+    m.add_argument("--model-in", metavar="FILE", help="align with this model instead of fitting one")
+    m.add_argument("--model-out", metavar="FILE", help="save the fitted model")
+    p.add_argument("--output", metavar="FILE.jsonl", default=None)
+    p.add_argument("--write-cache", action="store_true", help="replace phoneme_durations in the cache entries")
+    return p
+
+
+def check_args(p: argparse.ArgumentParser, args) -> None:
+    if args.iters < 1:
+        p.error("--iters must be >= 1")
+    if args.batch_size < 1:
+        p.error("--batch-size must be >= 1")
+    if not (0.0 <= args.var_floor < 1.0):
+        p.error("--var-floor must be in [0, 1)")
+    if not (0 <= args.mcep <= 31):
+        p.error("--mcep must be in 0..31")
+    if not (1 <= args.n_classes <= 256):
+        p.error("--n-classes must be in 1..256")
+    if any(not (0 <= o < args.n_classes) for o in args.optional_id):
+        p.error("--optional-id must be a phoneme id below --n-classes")
+
+
+def read_cache(cache_dir: str) -> List[Dict]:
+    """[{"path", "name", "mel" [T, M], "ids" [P], "durations" [P]}] of the cache's entries, in its length-sorted order."""
+    import torch
+    from kokoro.data.cached import scan_cache
+    out = []
+    for meta in scan_cache(cache_dir):
+        it = torch.load(meta["file"], map_location="cpu", weights_only=False)
+        T = int(it["mel_length"])
+        out.append({"path": str(meta["file"]), "name": os.path.splitext(meta["file"].name)[0],
+                    "mel": it["mel_spec"][:, :T].t().contiguous().float(), "ids": it["phoneme_indices"].to(torch.int64),
+                    "durations": it["phoneme_durations"].to(torch.int64)})
+    return out
+
+
+def replace_durations(path: str, durations) -> None:
+    """Rewrite one cache entry with other phoneme_durations, atomically (as kokoro.data.features.write_cache_entry writes it)."""
+    import torch
+    it = torch.load(path, map_location="cpu", weights_only=False)
+    it["phoneme_durations"] = durations.to(torch.long).contiguous()
+    tmp = f"{path}.tmp{os.getpid()}"
+    torch.save(it, tmp)
+    os.replace(tmp, path)
+
+
+def main(argv=None) -> int:
+    p = build_parser()
+    args = p.parse_args(argv)
+    check_args(p, args)
+    import torch
+    from kokoro_ruslan_amd import align as A
+
+    entries = read_cache(args.cache_dir)
+    al = A.PhoneAligner(K=args.mcep, n_classes=args.n_classes, var_floor=args.var_floor)
+    limit = A.max_tokens()
+    failed = 0
+    todo = []
+    for n, e in enumerate(entries):
+        P, T = int(e["ids"].shape[0]), int(e["mel"].shape[0])
+        why = (f"{T} frames; at most {A.MAX_FRAMES}" if T > A.MAX_FRAMES else f"{P} tokens; at most {limit}" if P > limit else
+               "no tokens" if P < 1 else "no frames" if T < 1 else
+               f"a phoneme id outside 0..{args.n_classes - 1}" if int(e["ids"].min()) < 0 or int(e["ids"].max()) >= args.n_classes else None)
+        if why:
+            failed += 1
+            print(f"kokoro-align: {e['name']}: {why}; its durations stay", file=sys.stderr)
+        else:
+            todo.append(n)
+    if not todo:
+        p.error("no utterance of the cache can be aligned")
+    mels, ids = [entries[n]["mel"] for n in todo], [entries[n]["ids"] for n in todo]
+    if args.model_in:
+        model = al.load(args.model_in)
+        recs = []
+        for s in range(0, len(todo), args.batch_size):
+            recs += al.align(mels[s:s + args.batch_size], ids[s:s + args.batch_size], args.optional_id, model)
+        durs, how = [r["durations"] for r in recs], f"model {args.model_in}"
+        score = sum(r["score"] for r in recs if r["feasible"])
+    else:
+        model, durs, scores = al.fit(mels, ids, args.optional_id, iters=args.iters, batch_size=args.batch_size)
+        how, score = f"{len(scores)} passes", scores[-1]
+        if args.model_out:
+            al.save(model, args.model_out)
+    aligned = 0
+    for n, d in zip(todo, durs):
+        e = entries[n]
+        if d is None:
+            failed += 1
+            print(f"kokoro-align: {e['name']}: {e['ids'].shape[0]} tokens cannot be laid on {e['mel'].shape[0]} frames; its durations stay",
+                  file=sys.stderr)
+            continue
+        aligned += 1
+        e["durations"] = d
+        if args.write_cache:
+            replace_durations(e["path"], d)
+    if args.output:
+        with open(args.output, "w") as f:
+            for e in entries:
+                f.write(json.dumps({"name": e["name"], "phoneme_durations": [int(v) for v in e["durations"]]}) + "\n")
+    frames = sum(int(entries[n]["mel"].shape[0]) for n, d in zip(todo, durs) if d is not None)
+    print(f"kokoro-align: {aligned} aligned, {failed} infeasible ({len(entries)} utterances), {how}, "
+          f"log-likelihood per frame {score / max(frames, 1):.4f}" + (" -> " + args.cache_dir if args.write_cache else ""))
+    return 0 if failed == 0 else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

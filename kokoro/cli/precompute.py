@@ -4,7 +4,7 @@
                       [--max-seq-length N]
 
 FILE.jsonl is kokoro-synth --ids's format, one utterance per line: {"name", "phoneme_indices"[, "stress_indices"]}, plus optional
-"phoneme_durations" (frames per phoneme, e.g. from an MFA alignment; absent: the reference's even fallback estimate) and "text".
+"phoneme_durations" (frames per phoneme, from kokoro-align or an MFA alignment; absent: the reference's even fallback estimate) and "text".
 DIR/<name>.wav is the audio, 22050 Hz; with --resample audio at another rate is resampled to 22050 Hz on the device first (the
 reference's torchaudio.transforms.Resample, data/dataset.py:662-665) instead of being refused.  The phonemizer and MFA alignment are
 not part of this tool: it takes their results.  Entries of the current cache version are skipped unless --force, as the reference's kokoro-precompute does.

@@ -1,0 +1,261 @@
+"""Flat-start forced alignment on the device, on the kernels of csrc/kk_align.hip: phoneme durations without an external aligner.
+
+What a monophone first stage does, reduced to essentials: one diagonal Gaussian per phoneme id over cepstral features of the log-mel
+(c_1..c_K and c_0, mean-normalised per utterance, plus their first differences), a flat start from the even split, and a few passes of
+Viterbi training: align every utterance with the current Gaussians, re-estimate the Gaussians from the alignment.  `PhoneAligner.fit`
+does that over a corpus held as lists, `align` aligns with a given model; an utterance's result is, bit for bit, what it gives alone.
+align_torch is the fp64 oracle of every step.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Iterable, List, Optional, Sequence
+
+import torch
+
+from kokoro_ruslan_amd import lib as kk
+from kokoro_ruslan_amd.align_torch import VAR_MIN, even_split
+from kokoro_ruslan_amd.dtw_torch import dct_table
+
+MAX_FRAMES = 4096                        # the longest utterance the kernels take (the positional table's order)
+MAX_MEL = 128                            # kk_mcep stages 64 frames of at most this many channels
+MAX_CLASSES = 256                        # kk_align_loglik
+MAX_DIM = 64
+
+
+def max_tokens() -> int:
+    """Tokens of an utterance the Viterbi kernel takes: the size of its workgroup."""
+    return int(kk.load().kk_align_max_tokens())
+
+
+def code_words(P: int, T: int) -> int:
+    """32-bit code words of a P-token, T-frame utterance: 16 tokens of a frame per word."""
+    return T * ((P + 15) // 16)
+
+
+class PhoneAligner:
+    """Batched Viterbi alignment and Viterbi training on the MI355X."""
+
+    def __init__(self, device: str = "cuda", K: int = 13, n_classes: int = 59, var_floor: float = 0.01):
+        if int(K) != K or not (0 <= K <= MAX_DIM // 2 - 1):
+            raise ValueError(f"K must be an integer in 0..{MAX_DIM // 2 - 1}, not {K!r}")
+        if int(n_classes) != n_classes or not (1 <= n_classes <= MAX_CLASSES):
+            raise ValueError(f"n_classes must be an integer in 1..{MAX_CLASSES}, not {n_classes!r}")
+        if not (0.0 <= var_floor < 1.0):
+            raise ValueError(f"var_floor must be in [0, 1), not {var_floor!r}")
+        self.device, self.K, self.n_classes, self.var_floor = torch.device(device), int(K), int(n_classes), float(var_floor)
+        self._tables: Dict[int, torch.Tensor] = {}
+
+    @property
+    def dim(self) -> int:
+        return 2 * (self.K + 1)
+
+    # ---- guards: everything is checked before anything is launched --------------------------------------------------------------
+    def _check(self, mels, ids, feats) -> None:
+        x, what = (mels, "mel") if feats is None else (feats, "features")
+        if x is None or len(x) != len(ids):
+            raise ValueError(f"{0 if x is None else len(x)} {what} tensors for {len(ids)} token sequences")
+        if not len(ids):
+            raise ValueError("nothing to align")
+        limit = max_tokens()
+        for i, (m, t) in enumerate(zip(x, ids)):
+            if not isinstance(m, torch.Tensor) or m.dim() != 2 or not m.is_floating_point():
+                raise ValueError(f"utterance {i}: the {what} must be a float tensor [frames, {'mels' if feats is None else 'dims'}]")
+            if m.shape[0] < 1:
+                raise ValueError(f"utterance {i}: the {what} is empty")
+            if m.shape[0] > MAX_FRAMES:
+                raise ValueError(f"utterance {i}: {m.shape[0]} frames; at most {MAX_FRAMES}")
+            if feats is None and m.shape[1] > MAX_MEL:
+                raise ValueError(f"utterance {i}: {m.shape[1]} mel channels; at most {MAX_MEL}")
+            if m.shape[1] != x[0].shape[1] or m.shape[1] < 1:
+                raise ValueError(f"utterance {i}: {m.shape[1]} channels against {x[0].shape[1]}")
+            if feats is not None and m.shape[1] > MAX_DIM:
+                raise ValueError(f"utterance {i}: {m.shape[1]} feature dimensions; at most {MAX_DIM}")
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.is_floating_point():
+                raise ValueError(f"utterance {i}: the tokens must be an integer tensor [P]")
+            if t.shape[0] < 1:
+                raise ValueError(f"utterance {i}: no tokens")
+            if t.shape[0] > limit:
+                raise ValueError(f"utterance {i}: {t.shape[0]} tokens; at most {limit}")
+            if int(t.min()) < 0 or int(t.max()) >= self.n_classes:
+                raise ValueError(f"utterance {i}: phoneme ids must lie in 0..{self.n_classes - 1}")
+
+    def _check_model(self, model: Dict, D: int) -> None:
+        for k in ("mean", "var"):
+            if tuple(model[k].shape) != (self.n_classes, D):
+                raise ValueError(f"the model's {k} is {tuple(model[k].shape)}; this aligner and these features need ({self.n_classes}, {D})")
+
+    # ---- pieces ------------------------------------------------------------------------------------------------------------------
+    def table(self, M: int) -> torch.Tensor:
+        if M not in self._tables:
+            self._tables[M] = torch.from_numpy(dct_table(M, self.K)).to(torch.float32).to(self.device).contiguous()
+        return self._tables[M]
+
+    def _features_packed(self, x: torch.Tensor, foff: torch.Tensor, B: int) -> torch.Tensor:
+        T, M = x.shape
+        cep = None
+        if self.K:
+            cep = torch.empty(self.K, T, dtype=torch.float32, device=self.device)
+            kk.call("kk_mcep", x, T, M, self.K, self.table(M), cep)
+        feat = torch.empty(self.dim, T, dtype=torch.float32, device=self.device)
+        kk.call("kk_align_feats", cep, x, T, M, self.K, foff, B, feat)
+        return feat
+
+    def features(self, mels: Sequence[torch.Tensor]) -> torch.Tensor:
+        """The packed features [D, T_total] (fp32, on the device) of log-mels [T, M]: utterance after utterance along time."""
+        self._check(mels, [torch.zeros(1, dtype=torch.long)] * len(mels), None)
+        x = torch.cat([m.to(self.device, torch.float32) for m in mels]).contiguous()
+        foff = torch.tensor([0] + [int(m.shape[0]) for m in mels], dtype=torch.int64).cumsum(0).to(torch.int32).to(self.device)
+        return self._features_packed(x, foff, len(mels))
+
+    def params(self, model: Dict):
+        """(a = -1/2 / var, mu, c = -1/2 sum ln(2 pi var)) as the device takes them: evaluated in fp64, rounded once."""
+        mean, var = model["mean"].to(torch.float64), model["var"].to(torch.float64)
+        a, c = -0.5 / var, -0.5 * (math.log(2.0 * math.pi) + var.log()).sum(1)
+        return tuple(t.to(torch.float32).to(self.device).contiguous() for t in (a, mean, c))
+
+    def loglik(self, feat: torch.Tensor, model: Dict) -> torch.Tensor:
+        """L [V, T_total] (fp32) of packed features [D, T_total] on the device."""
+        D, T = feat.shape
+        self._check_model(model, D)
+        a, mu, c = self.params(model)
+        L = torch.empty(self.n_classes, T, dtype=torch.float32, device=self.device)
+        kk.call("kk_align_loglik", feat, T, D, self.n_classes, a, mu, c, L)
+        return L
+
+    def accumulate(self, feat: torch.Tensor, label: torch.Tensor):
+        """(count int64 [V], sum x fp64 [V, D], sum x^2 fp64 [V, D]) of packed features [D, T_total] under frame labels int32 [T_total]."""
+        D, T = feat.shape
+        V = self.n_classes
+        count = torch.empty(V, dtype=torch.int64, device=self.device)
+        sums = torch.empty(2, V, D, dtype=torch.float64, device=self.device)
+        kk.call("kk_align_accumulate", feat, label, T, D, V, count, sums[0], sums[1])
+        return count, sums[0], sums[1]
+
+    def estimate(self, count: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor) -> Dict:
+        """The model of class statistics (align_torch.model_from_stats, in fp64 torch): [V, D] is tiny."""
+        n = count.to(torch.float64)
+        N = n.sum().clamp(min=1.0)
+        gmean = s1.sum(0) / N
+        gvar = (s2.sum(0) / N - gmean ** 2).clamp(min=0.0)
+        safe = n.clamp(min=1.0)[:, None]
+        mean = s1 / safe
+        var = s2 / safe - mean ** 2
+        few = (n < 2)[:, None]
+        mean, var = torch.where(few, gmean, mean), torch.where(few, gvar, var)
+        var = torch.maximum(torch.maximum(var, self.var_floor * gvar), torch.full_like(var, VAR_MIN))
+        return {"mean": mean, "var": var, "K": self.K, "n_classes": self.n_classes}
+
+    # ---- one batch on the device -------------------------------------------------------------------------------------------------
+    def _pack(self, mels, ids, optional_ids: Iterable[int], feats) -> Dict:
+        dev = self.device
+        x = mels if feats is None else feats
+        nt, np_ = [int(m.shape[0]) for m in x], [int(t.shape[0]) for t in ids]
+        cum = lambda v, dt: torch.tensor([0] + v, dtype=torch.int64).cumsum(0).to(dt)
+        coff_h = cum([code_words(p, t) for p, t in zip(np_, nt)], torch.int64)
+        tok_h = torch.cat([t.to("cpu", torch.int64) for t in ids])
+        opt_h = torch.isin(tok_h, torch.tensor(sorted(set(int(o) for o in optional_ids)), dtype=torch.int64))
+        pk = {"B": len(ids), "frames": nt, "tokens": np_, "foff": cum(nt, torch.int32).to(dev), "poff": cum(np_, torch.int32).to(dev),
+              "coff": coff_h.to(dev), "coff_host": coff_h.tolist(), "foff_host": cum(nt, torch.int64).tolist(),
+              "poff_host": cum(np_, torch.int64).tolist(), "ids_host": tok_h, "ids": tok_h.to(torch.int32).to(dev),
+              "opt": opt_h.to(torch.uint8).to(dev), "threads": (max(np_) + 63) // 64 * 64}
+        packed = torch.cat([m.to(dev, torch.float32) for m in x]).contiguous()
+        pk["feat"] = self._features_packed(packed, pk["foff"], pk["B"]) if feats is None else packed.t().contiguous()
+        return pk
+
+    def _align_packed(self, pk: Dict, model: Dict) -> Dict:
+        dev, B = self.device, pk["B"]
+        L = self.loglik(pk["feat"], model)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        end = torch.empty(B, dtype=torch.int32, device=dev)
+        codes = torch.empty(pk["coff_host"][-1], dtype=torch.int32, device=dev)
+        durations = torch.empty(pk["poff_host"][-1], dtype=torch.int32, device=dev)
+        label = torch.empty(pk["foff_host"][-1], dtype=torch.int32, device=dev)
+        kk.call("kk_align_viterbi", L, L.shape[1], pk["ids"], pk["opt"], pk["foff"], pk["poff"], pk["coff"], B, pk["threads"], score, end,
+                codes)
+        kk.call("kk_align_backtrack", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, durations, label)
+        return {"feat": pk["feat"], "L": L, "score": score, "end": end, "codes": codes, "durations": durations, "label": label,
+                "foff_host": pk["foff_host"], "poff_host": pk["poff_host"], "coff_host": pk["coff_host"]}
+
+    def run_packed(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (),
+                   model: Optional[Dict] = None, feats: Optional[Sequence[torch.Tensor]] = None) -> Dict:
+        """One batch on the device, nothing read back: the features [D, T_total], L [V, T_total], score fp32 [B], end int32 [B] (the
+        end state, -1 when infeasible), the code words, durations int32 [P_total], label int32 [T_total] and the host lists foff_host /
+        poff_host / coff_host (first frame / token / code word of each utterance).  feats: features [T, D] per utterance instead of
+        mels (then mels is None)."""
+        if model is None:
+            raise ValueError("run_packed needs a model: fit one, or load one")
+        self._check(mels, ids, feats)
+        self._check_model(model, self.dim if feats is None else int(feats[0].shape[1]))
+        return self._align_packed(self._pack(mels, ids, optional_ids, feats), model)
+
+    @staticmethod
+    def _records(run: Dict) -> List[Dict]:
+        score, dur, poff = run["score"].cpu().tolist(), run["durations"].cpu().to(torch.int64), run["poff_host"]
+        out = []
+        for n, s in enumerate(score):
+            ok = s > -math.inf
+            out.append({"durations": dur[poff[n]:poff[n + 1]].clone() if ok else None, "score": s, "feasible": ok})
+        return out
+
+    def align(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (),
+              model: Optional[Dict] = None, feats: Optional[Sequence[torch.Tensor]] = None) -> List[Dict]:
+        """mels: log-mels [T, M], ids: integer tokens [P], utterance i = (mels[i], ids[i]); optional_ids: the phoneme ids whose tokens
+        may get no frame.  Returns per utterance {"durations": LongTensor [P] summing to T (0 for a skipped token) | None, "score":
+        the log-likelihood of the best path, "feasible": whether a path exists}.  One read by the host."""
+        return self._records(self.run_packed(mels, ids, optional_ids, model, feats))
+
+    def fit(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (), iters: int = 6,
+            batch_size: int = 64, feats: Optional[Sequence[torch.Tensor]] = None):
+        """Viterbi training from the even split: `iters` passes of estimate -> align over the corpus in batches of batch_size, the
+        class statistics accumulated batch by batch in that order; stops once no duration changes.  Returns (model, durations: list of
+        LongTensor [P] | None, scores: the corpus score of each pass)."""
+        if int(iters) != iters or iters < 1:
+            raise ValueError(f"iters must be an integer >= 1, not {iters!r}")
+        if int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError(f"batch_size must be an integer >= 1, not {batch_size!r}")
+        self._check(mels, ids, feats)
+        x = mels if feats is None else feats
+        packs = []
+        for s in range(0, len(ids), batch_size):
+            e = s + batch_size
+            packs.append(self._pack(None if feats is not None else x[s:e], ids[s:e], optional_ids, None if feats is None else x[s:e]))
+        flat = [torch.from_numpy(even_split(int(t.shape[0]), int(m.shape[0]))) for m, t in zip(x, ids)]
+        labels, n = [], 0
+        for pk in packs:
+            d = torch.cat(flat[n:n + pk["B"]])
+            labels.append(torch.repeat_interleave(pk["ids_host"], d).to(torch.int32).to(self.device))
+            n += pk["B"]
+        durs: List[Optional[torch.Tensor]] = list(flat)
+        model, scores = None, []
+        for _ in range(int(iters)):
+            stats = None
+            for pk, lab in zip(packs, labels):
+                part = self.accumulate(pk["feat"], lab)
+                stats = part if stats is None else tuple(a + b for a, b in zip(stats, part))
+            model = self.estimate(*stats)
+            new, labels, total = [], [], 0.0
+            for pk in packs:
+                run = self._align_packed(pk, model)
+                labels.append(run["label"])
+                for r in self._records(run):
+                    new.append(r["durations"])
+                    total += r["score"] if r["feasible"] else 0.0
+            scores.append(total)
+            same = all((d is None and e is None) or (d is not None and e is not None and torch.equal(d, e)) for d, e in zip(durs, new))
+            durs = new
+            if same:
+                break
+        return model, durs, scores
+
+    # ---- the model on disk -------------------------------------------------------------------------------------------------------
+    def save(self, model: Dict, path: str) -> None:
+        torch.save({"mean": model["mean"].detach().to("cpu", torch.float64), "var": model["var"].detach().to("cpu", torch.float64),
+                    "K": self.K, "n_classes": self.n_classes}, path)
+
+    def load(self, path: str) -> Dict:
+        m = torch.load(path, map_location="cpu", weights_only=True)
+        if int(m["K"]) != self.K or int(m["n_classes"]) != self.n_classes:
+            raise ValueError(f"{path}: a model of K = {int(m['K'])}, {int(m['n_classes'])} classes; this aligner has K = {self.K}, "
+                             f"{self.n_classes} classes")
+        return {"mean": m["mean"].to(self.device), "var": m["var"].to(self.device), "K": self.K, "n_classes": self.n_classes}

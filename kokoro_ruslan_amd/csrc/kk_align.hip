@@ -1,0 +1,300 @@
+// Flat-start forced alignment of phoneme tokens to mel frames (kokoro_ruslan_amd/align.py): the phoneme durations the length regulator
+// and the duration loss train on, from one diagonal Gaussian per phoneme id and a few passes of Viterbi training.
+//
+// A ragged batch of B utterances packed as kk_dtw.hip packs pairs: frames back to back with foff (int32, B + 1), tokens back to back
+// with poff (int32, B + 1).  Five launches:
+//   feats       from kk_mcep's cepstra [K][T_total] and the packed log-mel: rows 0..K-1 c_1..c_K, row K c_0 (the frame's mean over
+//               the mel channels), each minus the utterance's own mean over time, then rows K+1..2K+1 their first differences
+//               (x(t+1) - x(t-1)) / 2 with the edge frames replicated.  One workgroup per (utterance, row); the mean is a fixed-order
+//               sum (thread i takes the frames i, i + 256, ..., then a fixed tree), in fp64 from the fp32 values.
+//   loglik      L[v][t] = sum over ascending d of a[v][d] (x[d][t] - mu[v][d])^2 (one fmaf chain), plus c[v]: a = -1/2 / var, mu and
+//               c = -1/2 sum_d ln(2 pi var) come from the HOST (fp64, rounded once).  A workgroup takes 256 frames and 16 classes,
+//               whose parameters it stages in LDS (read wave-uniformly); a thread holds its frame's features in registers.
+//   viterbi     one workgroup per utterance, thread p = token p: S(p, t) = L[ids[p]][t] + max(S(p, t-1), S(p-1, t-1), S(p-2, t-1) if
+//               token p-1 is optional), a later candidate only when strictly greater.  Only column t-1 is needed: two columns of S
+//               in LDS, two cells of -inf in front of each so that p-1 and p-2 need no branch, one barrier per frame.  A thread
+//               loads its row of L eight frames ahead.  The candidate chosen (0 stay, 1 advance, 2 skip) goes out as 2 bits, 16
+//               tokens per 32-bit word, straight from two wave ballots: bits 0..15 of a word are the low bits of the 16 codes, bits
+//               16..31 their high bits.
+//   backtrack   one wave per utterance: lane 0 walks the code words from the end state back to frame 0, counting durations in LDS
+//               and writing every frame's class id; the wave writes the durations out.  An infeasible utterance (no finite path)
+//               gets durations 0 and labels -1.
+//   accumulate  per class the count and, in fp64, sum x and sum x^2 over the frames labelled with it: one workgroup per (class, four
+//               dimensions), thread i sums the frames i, i + 256, ... in order, then a fixed tree.  No atomics: two runs give the
+//               same bits.
+// Nothing an utterance computes in feats, viterbi or backtrack depends on the other utterances, and a frame's L on that frame alone.
+#include "kk_common.h"
+
+namespace {
+
+constexpr int AL_MAXP = 1024;                 // tokens of an utterance = threads of its workgroup
+constexpr int AL_MAXT = 4096;                 // frames of an utterance (the positional table's order, as kk_dtw)
+constexpr int AL_PRE = 8;                     // frames of L a state loads ahead
+constexpr int AL_THREADS = 256;
+constexpr int LL_VC = 16;                     // classes per workgroup of loglik_kernel
+constexpr int ACC_DG = 4;                     // dimensions per workgroup of accumulate_kernel
+
+__global__ __launch_bounds__(AL_THREADS) void align_feats_kernel(const float *__restrict__ cep, const float *__restrict__ mel,
+                                                                 int64_t T_total, int M, int K, const int *__restrict__ foff,
+                                                                 float *__restrict__ feat) {
+    __shared__ float row[AL_MAXT];
+    __shared__ double red[AL_THREADS];
+    const int b = blockIdx.x / (K + 1), r = blockIdx.x % (K + 1), tid = threadIdx.x;
+    const int f0 = foff[b], T = foff[b + 1] - f0;
+    if (T < 1 || T > AL_MAXT) return;                                 // (the host checks; nothing is written past the LDS row)
+    double part = 0.0;
+    for (int t = tid; t < T; t += AL_THREADS) {
+        float v;
+        if (r < K) v = cep[(int64_t)r * T_total + f0 + t];
+        else {
+            const float *x = mel + (int64_t)(f0 + t) * M;
+            float acc = 0.f;
+            for (int m = 0; m < M; ++m) acc += x[m];
+            v = acc / (float)M;
+        }
+        row[t] = v;
+        part += (double)v;
+    }
+    red[tid] = part;
+    __syncthreads();
+    for (int h = AL_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) red[tid] += red[tid + h];
+        __syncthreads();
+    }
+    const float mean = (float)(red[0] / (double)T);
+    float *stat = feat + (int64_t)r * T_total + f0, *delta = feat + (int64_t)(K + 1 + r) * T_total + f0;
+    for (int t = tid; t < T; t += AL_THREADS) {
+        stat[t] = row[t] - mean;
+        delta[t] = 0.5f * ((row[min(t + 1, T - 1)] - mean) - (row[max(t - 1, 0)] - mean));
+    }
+}
+
+template <int DM>
+__global__ __launch_bounds__(AL_THREADS) void align_loglik_kernel(const float *__restrict__ feat, int64_t T_total, int D, int V,
+                                                                  const float *__restrict__ a, const float *__restrict__ mu,
+                                                                  const float *__restrict__ c, float *__restrict__ L) {
+    __shared__ float as[LL_VC * DM], ms[LL_VC * DM], cs[LL_VC];
+    const int tid = threadIdx.x, v0 = blockIdx.y * LL_VC, nv = min(LL_VC, V - v0);
+    for (int e = tid; e < nv * D; e += AL_THREADS) {
+        const int vv = e / D, d = e % D;
+        as[vv * DM + d] = a[(int64_t)(v0 + vv) * D + d];
+        ms[vv * DM + d] = mu[(int64_t)(v0 + vv) * D + d];
+    }
+    if (tid < nv) cs[tid] = c[v0 + tid];
+    __syncthreads();
+    const int64_t t = (int64_t)blockIdx.x * AL_THREADS + tid;
+    if (t >= T_total) return;
+    float x[DM];
+#pragma unroll
+    for (int d = 0; d < DM; ++d) x[d] = feat[(int64_t)min(d, D - 1) * T_total + t];
+    for (int vv = 0; vv < nv; ++vv) {
+        float acc = 0.f;
+#pragma unroll
+        for (int d = 0; d < DM; ++d)
+            if (d < D) {
+                const float diff = x[d] - ms[vv * DM + d];
+                acc = fmaf(diff * diff, as[vv * DM + d], acc);
+            }
+        L[(int64_t)(v0 + vv) * T_total + t] = acc + cs[vv];
+    }
+}
+
+struct VitArgs {
+    const float *L;                           // [V][T_total]
+    int64_t T_total;
+    const int *ids;                           // [P_total]
+    const unsigned char *opt;                 // [P_total]: 1 where the token may be skipped
+    const int *foff, *poff;
+    const int64_t *coff;                      // first code word of each utterance
+    float *score;
+    int *end;                                 // the end state, -1 when infeasible
+    uint32_t *codes;
+};
+
+__global__ __launch_bounds__(AL_MAXP) void align_viterbi_kernel(const VitArgs a) {
+    __shared__ float S[2][AL_MAXP + 2];                               // state p at [p + 2]; [0] and [1] stay -inf
+    const int b = blockIdx.x, p = threadIdx.x;
+    const int f0 = a.foff[b], T = a.foff[b + 1] - f0, p0 = a.poff[b], P = a.poff[b + 1] - p0;
+    if (P < 1 || P > (int)blockDim.x || T < 1 || T > AL_MAXT) return;  // (the host checks)
+    const bool live = p < P, wave_live = (p & ~63) < P;               // a wave past the last token only keeps the barriers
+    const int W = (P + 15) >> 4;                                      // code words per frame
+    uint32_t *codes = a.codes + a.coff[b];
+    const float ninf = -__builtin_inff();
+    const float *Lr = a.L + (int64_t)(live ? a.ids[p0 + p] : 0) * a.T_total + f0;
+    const bool may_skip = live && p >= 2 && a.opt[p0 + p - 1];
+    const bool starts = p == 0 || (p == 1 && a.opt[p0]);
+    if (p < 2) S[0][p] = S[1][p] = ninf;
+    __syncthreads();
+    for (int t0 = 0; t0 < T; t0 += AL_PRE) {
+        float l[AL_PRE];
+        if (wave_live) {
+#pragma unroll
+            for (int u = 0; u < AL_PRE; ++u) l[u] = Lr[min(t0 + u, T - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < AL_PRE; ++u) {
+            const int t = t0 + u;
+            if (t >= T) break;
+            if (wave_live) {
+                const float *prev = S[(t & 1) ^ 1];
+                float s;
+                uint32_t code = 0;
+                if (t == 0) s = starts ? l[u] : ninf;
+                else {
+                    float best = prev[p + 2];
+                    const float adv = prev[p + 1], skip = may_skip ? prev[p] : ninf;
+                    if (adv > best) best = adv, code = 1;
+                    if (skip > best) best = skip, code = 2;
+                    s = l[u] + best;
+                }
+                if (live) S[t & 1][p + 2] = s;
+                else code = 0;
+                const unsigned long long lo = __ballot(code & 1u), hi = __ballot(code & 2u);
+                if (live && (p & 15) == 0) {
+                    const int sh = p & 48;
+                    codes[(int64_t)t * W + (p >> 4)] = (uint32_t)((lo >> sh) & 0xffffull) | ((uint32_t)((hi >> sh) & 0xffffull) << 16);
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (p == 0) {
+        const float *last = S[(T - 1) & 1];
+        int e = P - 1;
+        float s = last[P + 1];
+        if (P > 1 && a.opt[p0 + P - 1] && last[P] > s) e = P - 2, s = last[P];
+        const bool ok = s > ninf;                                     // (false for a NaN too)
+        a.score[b] = ok ? s : ninf;
+        a.end[b] = ok ? e : -1;
+    }
+}
+
+__global__ __launch_bounds__(64) void align_backtrack_kernel(const uint32_t *__restrict__ codes, const int64_t *__restrict__ coff,
+                                                             const int *__restrict__ foff, const int *__restrict__ poff,
+                                                             const int *__restrict__ ids, const int *__restrict__ end,
+                                                             int *__restrict__ durations, int *__restrict__ label) {
+    __shared__ int dur[AL_MAXP];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int f0 = foff[b], T = foff[b + 1] - f0, p0 = poff[b], P = poff[b + 1] - p0;
+    if (P < 1 || P > AL_MAXP || T < 1 || T > AL_MAXT) return;
+    for (int p = lane; p < P; p += 64) dur[p] = 0;
+    __syncthreads();
+    const int e = end[b];
+    if (e < 0 || e >= P) {
+        for (int t = lane; t < T; t += 64) label[f0 + t] = -1;
+    } else if (lane == 0) {
+        const uint32_t *cod = codes + coff[b];
+        const int W = (P + 15) >> 4;
+        int p = e;
+        for (int t = T - 1; t >= 0; --t) {
+            ++dur[p];
+            label[f0 + t] = ids[p0 + p];
+            if (t) {
+                const uint32_t w = cod[(int64_t)t * W + (p >> 4)] >> (p & 15);
+                p = max(p - (int)min((w & 1u) | ((w >> 15) & 2u), 2u), 0);
+            }
+        }
+    }
+    __syncthreads();
+    for (int p = lane; p < P; p += 64) durations[p0 + p] = dur[p];
+}
+
+__global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const float *__restrict__ feat, const int *__restrict__ label,
+                                                                      int64_t T_total, int D, long long *__restrict__ count,
+                                                                      double *__restrict__ sum, double *__restrict__ sumsq) {
+    __shared__ double red[2 * ACC_DG][AL_THREADS];
+    __shared__ int cnt[AL_THREADS];
+    const int v = blockIdx.x, d0 = blockIdx.y * ACC_DG, tid = threadIdx.x;
+    double s1[ACC_DG] = {}, s2[ACC_DG] = {};
+    int n = 0;
+    for (int64_t t = tid; t < T_total; t += AL_THREADS)
+        if (label[t] == v) {
+            ++n;
+#pragma unroll
+            for (int u = 0; u < ACC_DG; ++u)
+                if (d0 + u < D) {
+                    const double x = (double)feat[(int64_t)(d0 + u) * T_total + t];
+                    s1[u] += x;
+                    s2[u] += x * x;
+                }
+        }
+#pragma unroll
+    for (int u = 0; u < ACC_DG; ++u) red[u][tid] = s1[u], red[ACC_DG + u][tid] = s2[u];
+    cnt[tid] = n;
+    __syncthreads();
+    for (int h = AL_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int u = 0; u < 2 * ACC_DG; ++u) red[u][tid] += red[u][tid + h];
+            cnt[tid] += cnt[tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid < ACC_DG && d0 + tid < D) {
+        sum[(int64_t)v * D + d0 + tid] = red[tid][0];
+        sumsq[(int64_t)v * D + d0 + tid] = red[ACC_DG + tid][0];
+    }
+    if (tid == 0 && blockIdx.y == 0) count[v] = cnt[0];
+}
+
+}  // namespace
+
+extern "C" int kk_align_max_tokens(void) { return AL_MAXP; }
+
+extern "C" int kk_align_feats(const float *cep, const float *mel, int64_t T_total, int M, int K, const int *foff, int B, float *feat,
+                              void *stream) {
+    KK_REQUIRE(mel && foff && feat && B > 0 && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_feats: bad args");
+    KK_REQUIRE(M >= 1 && K >= 0 && K <= 31 && (cep || K == 0), "kk_align_feats: M = %d, K = %d; needs M >= 1 and 0 <= K <= 31", M, K);
+    kk_note_kernel("align_feats");
+    hipLaunchKernelGGL(align_feats_kernel, dim3((unsigned)B * (K + 1)), dim3(AL_THREADS), 0, (hipStream_t)stream, cep, mel, T_total, M, K,
+                       foff, feat);
+    KK_LAUNCH_CHECK("kk_align_feats");
+    return 0;
+}
+
+extern "C" int kk_align_loglik(const float *feat, int64_t T_total, int D, int V, const float *a, const float *mu, const float *c,
+                               float *L, void *stream) {
+    KK_REQUIRE(feat && a && mu && c && L && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_loglik: bad args");
+    KK_REQUIRE(D >= 1 && D <= 64 && V >= 1 && V <= 256, "kk_align_loglik: D = %d, V = %d; needs 1 <= D <= 64 and 1 <= V <= 256", D, V);
+    const dim3 grid(kk_cdiv(T_total, AL_THREADS), kk_cdiv(V, LL_VC));
+    kk_note_kernel("align_loglik");
+    if (D <= 8) hipLaunchKernelGGL(align_loglik_kernel<8>, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, V, a, mu, c, L);
+    else if (D <= 32) hipLaunchKernelGGL(align_loglik_kernel<32>, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, V, a, mu, c, L);
+    else hipLaunchKernelGGL(align_loglik_kernel<64>, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, V, a, mu, c, L);
+    KK_LAUNCH_CHECK("kk_align_loglik");
+    return 0;
+}
+
+extern "C" int kk_align_viterbi(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff,
+                                const int *poff, const int64_t *coff, int B, int threads, float *score, int *end, uint32_t *codes,
+                                void *stream) {
+    KK_REQUIRE(L && ids && opt && foff && poff && coff && score && end && codes && B > 0 && T_total > 0, "kk_align_viterbi: bad args");
+    KK_REQUIRE(threads >= 64 && threads <= AL_MAXP && threads % 64 == 0, "kk_align_viterbi: %d threads; needs a multiple of 64 in 64..%d",
+               threads, AL_MAXP);
+    VitArgs r{L, T_total, ids, opt, foff, poff, coff, score, end, codes};
+    kk_note_kernel("align_viterbi");
+    hipLaunchKernelGGL(align_viterbi_kernel, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
+    KK_LAUNCH_CHECK("kk_align_viterbi");
+    return 0;
+}
+
+extern "C" int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids,
+                                  const int *end, int B, int *durations, int *label, void *stream) {
+    KK_REQUIRE(codes && coff && foff && poff && ids && end && durations && label && B > 0, "kk_align_backtrack: bad args");
+    kk_note_kernel("align_backtrack");
+    hipLaunchKernelGGL(align_backtrack_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, codes, coff, foff, poff, ids, end, durations,
+                       label);
+    KK_LAUNCH_CHECK("kk_align_backtrack");
+    return 0;
+}
+
+extern "C" int kk_align_accumulate(const float *feat, const int *label, int64_t T_total, int D, int V, int64_t *count, double *sum,
+                                   double *sumsq, void *stream) {
+    KK_REQUIRE(feat && label && count && sum && sumsq && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_accumulate: bad args");
+    KK_REQUIRE(D >= 1 && D <= 64 && V >= 1 && V <= 256, "kk_align_accumulate: D = %d, V = %d; needs 1 <= D <= 64 and 1 <= V <= 256", D, V);
+    kk_note_kernel("align_accumulate");
+    hipLaunchKernelGGL(align_accumulate_kernel, dim3(V, kk_cdiv(D, ACC_DG)), dim3(AL_THREADS), 0, (hipStream_t)stream, feat, label, T_total,
+                       D, (long long *)count, sum, sumsq);
+    KK_LAUNCH_CHECK("kk_align_accumulate");
+    return 0;
+}

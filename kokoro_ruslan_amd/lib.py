@@ -255,6 +255,12 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_dtw": [_P, _L, _P, _L, _I, _P, _P, _P, _I, _P, _P, _P],
     "kk_dtw_backtrack": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
     "kk_dtw_path_stats": [_P, _L, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "kk_align_max_tokens": [],
+    "kk_align_feats": [_P, _P, _L, _I, _I, _P, _I, _P, _P],
+    "kk_align_loglik": [_P, _L, _I, _I, _P, _P, _P, _P, _P],
+    "kk_align_viterbi": [_P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "kk_align_backtrack": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "kk_align_accumulate": [_P, _P, _L, _I, _I, _P, _P, _P, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
     "kk_losses_finalize": [_P, C.POINTER(KkLossCfg), _P, _I, _P, _P, _P, _I, _P],
     "kk_losses_bwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _P, _P],

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Throughput of the forced-alignment kernels.
+
+PhoneAligner.align (features, log-likelihoods, Viterbi, backtrack and the read of the durations: everything an alignment costs) on 64
+utterances of 100 tokens x 600 frames and of 300 x 1800, and one PhoneAligner.fit pass (accumulate, estimate, align) over 256 utterances
+of 100 x 600, against two baselines: the same recurrence written with torch ops on the same GPU (all utterances of the batch per op,
+one frame at a time, the recurrence alone: L given, no codes, no path), and the fp64 oracle (kokoro_ruslan_amd.align_torch) on the host
+in 16 threads.  Five repeats with the device paths interleaved inside every repeat; medians, with the spread.  The host oracle runs
+once per size on 16 utterances.  One JSON line at the end.
+
+    python tools/align_bench.py [repeats=5]"""
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from kokoro_ruslan_amd import align_torch as R
+from kokoro_ruslan_amd.align import PhoneAligner
+
+REPEATS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+SIZES, B, FIT_B, M, V = ((100, 600), (300, 1800)), 64, 256, 80, 59
+al = PhoneAligner(n_classes=V)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def corpus(n, P, T, seed):
+    """n utterances whose frames follow their tokens' class templates in an uneven split: an alignment worth finding."""
+    g = torch.Generator().manual_seed(seed)
+    templates = torch.randn(V, M, generator=g) * 2.0 - 5.0
+    mels, ids = [], []
+    for _ in range(n):
+        i = torch.randint(0, V, (P,), generator=g)
+        d = torch.ones(P, dtype=torch.long) + torch.bincount(torch.randint(0, P, (T - P,), generator=g), minlength=P)
+        mels.append((templates[torch.repeat_interleave(i, d)] + 0.5 * torch.randn(T, M, generator=g)).cuda())
+        ids.append(i)
+    return mels, ids
+
+
+def torch_viterbi(L, ids):
+    """The scores [B] of the best paths with torch ops: L [V, B, T], ids [B, P]; no optional tokens."""
+    Bn, P = ids.shape
+    Lp = L.permute(1, 0, 2).gather(1, ids[:, :, None].expand(Bn, P, L.shape[2]))      # [B, P, T]
+    S = torch.full((Bn, P + 1), float("-inf"), device=L.device)
+    S[:, 1] = Lp[:, 0, 0]
+    for t in range(1, L.shape[2]):
+        S = torch.cat([S[:, :1], Lp[:, :, t] + torch.maximum(S[:, 1:], S[:, :-1])], 1)
+    return S[:, P]
+
+
+result = {"repeats": REPEATS, "align": {}, "fit": {}}
+cases = {}
+for P, T in SIZES:
+    mels, ids = corpus(B, P, T, 1000 + P)
+    model, _, _ = al.fit(mels, ids, iters=2)                    # warm-up, and a model worth aligning with
+    run = al.run_packed(mels, ids, (), model)
+    L = run["L"].reshape(V, B, T).contiguous()
+    idt = torch.stack(ids).cuda()
+    ours, base = run["score"].cpu(), torch_viterbi(L, idt).cpu()
+    gap = float(((ours - base).abs() / base.abs()).max())      # both sum T fp32 terms along a best path
+    print(f"{P} x {T}: kernels against torch ops, largest relative difference of the scores {gap:.2e}"
+          + ("" if gap <= T * 2.0 ** -22 else "  <-- MORE than two fp32 sums of T terms explain"))
+    cases[(P, T)] = (mels, ids, model, L, idt, {"kernel_s": [], "torch_s": [], "scores_rel_gap": gap})
+fit_mels, fit_ids = corpus(FIT_B, *SIZES[0], 7)
+al.fit(fit_mels, fit_ids, iters=1)
+fit_s = []
+for _ in range(REPEATS):
+    for key, (mels, ids, model, L, idt, r) in cases.items():
+        r["kernel_s"].append(timed(lambda: al.align(mels, ids, (), model))[1])
+        r["torch_s"].append(timed(lambda: torch_viterbi(L, idt))[1])
+    fit_s.append(timed(lambda: al.fit(fit_mels, fit_ids, iters=1))[1])
+torch.set_num_threads(1)                                        # 16 utterances side by side, one thread each
+for P, T in SIZES:
+    mels, ids, model, L, idt, r = cases[(P, T)]
+    Lh, ih = L[:, :16].double().cpu().numpy(), [i.numpy() for i in ids[:16]]
+    with ThreadPoolExecutor(16) as ex:
+        t0 = time.perf_counter()
+        list(ex.map(lambda n: R.align(Lh[:, n], ih[n])[1], range(16)))
+        host = time.perf_counter() - t0
+    tk, tt = statistics.median(r["kernel_s"]), statistics.median(r["torch_s"])
+    r.update(kernel_median_s=tk, torch_median_s=tt, utterances_per_s=B / tk, cells_per_s=B * P * T / tk, host_oracle_16_threads_utterances_per_s=16 / host)
+    result["align"][f"{P}x{T}"] = r
+    print(f"{P} x {T}, B = {B}: align {tk * 1e3:8.2f} ms [{min(r['kernel_s']) * 1e3:.2f}, {max(r['kernel_s']) * 1e3:.2f}] = {B / tk:8.0f} utterances/s = "
+          f"{B * P * T / tk / 1e9:6.2f} G cells/s | torch ops (recurrence only) {tt * 1e3:8.1f} ms [{min(r['torch_s']) * 1e3:.1f}, {max(r['torch_s']) * 1e3:.1f}] | x{tt / tk:.1f} "
+          f"| fp64 oracle on the host (recurrence and path, L given), 16 utterances in 16 threads: {host:.2f} s = {16 / host:.1f} utterances/s")
+tf = statistics.median(fit_s)
+P, T = SIZES[0]
+result["fit"] = {"utterances": FIT_B, "tokens": P, "frames": T, "pass_s": fit_s, "pass_median_s": tf, "frames_per_s": FIT_B * T / tf}
+print(f"fit, one pass over {FIT_B} utterances of {P} x {T} (features, accumulate, estimate, align): {tf * 1e3:.1f} ms "
+      f"[{min(fit_s) * 1e3:.1f}, {max(fit_s) * 1e3:.1f}] = {FIT_B * T / tf / 1e6:.2f} M frames/s")
+print(json.dumps(result))
