@@ -451,6 +451,21 @@ int kk_gl_iter(const void *y_in, void *y_out, void *rebuilt, const float *S, con
 /* wave = istft(y): 256 (frames - 1) samples per utterance at its offset */
 int kk_gl_istft(const void *y, const int *tiles, int ntiles, const void *tw, const float *win, float *wave, void *stream);
 
+/* ---- spectral denoising of vocoded audio (kokoro_ruslan_amd/denoise.py; kk_denoise.hip): y = istft(G . stft(x)) for a packed batch ----
+ * G = max(1 - strength . bias[k] / |X|, 0) per bin and frame (0 where |X| = 0): the magnitude less a multiple of the vocoder's bias
+ * spectrum, the phase kept.  n_fft = win = 1024, hop = 256, periodic Hann, center = True, reflect padding, onesided, torch.istft's
+ * window-square envelope; fp32.  Waveforms packed back to back: woff int64 [B + 1] sample offsets, every utterance >= 1024 samples.
+ * tiles: int32 [ntiles][2] = {utterance, first hop (a multiple of kk_denoise_tile_frames(), below ceil(n / 256))}: a tile writes samples
+ * [256 hop, 256 (hop + tile)) of its utterance, and the tiles of an utterance cover it.  bias: [513] >= 0; tw: exp(-2 pi i j / 1024),
+ * j < 1024; win: the window, 1024.  out has wave's layout and is another buffer.  An utterance's output does not depend on the batch. */
+/* hops of one tile */
+int kk_denoise_tile_frames(void);
+int kk_denoise(const float *wave, const int64_t *woff, const int *tiles, int ntiles, const float *bias, float strength, const void *tw,
+               const float *win, float *out, void *stream);
+/* out[513] = mean over frames [f_lo, f_hi) of |stft(wave)| of one waveform of n >= 1024 samples (1 + n / 256 frames), summed in a fixed
+ * order: the bias of a vocoder from what it makes of a silent mel */
+int kk_stft_mag_mean(const float *wave, int64_t n, int f_lo, int f_hi, const void *tw, const float *win, float *out, void *stream);
+
 /* ---- audio feature extraction (kokoro_ruslan_amd/features.py; kk_features.hip): waveforms -> log-mel, pitch, energy ----
  * The reference's per-utterance front-end (22050 Hz, n_fft = win = 1024, hop 256, 80 HTK mels; pitch window 2048, lags 27..441), fp32.
  * The waveforms of a batch are packed back to back: woff int64 [B + 1] sample offsets.  moff int32 [B + 1]: offsets of the mel frames

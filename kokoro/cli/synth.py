@@ -3,7 +3,7 @@
     kokoro-synth --checkpoint CKPT (--features CACHE_DIR [--indices ...] | --ids FILE.jsonl) --output DIR
                  [--batch-size 32] [--weights auto|ema|model] [--stop-threshold X] [--max-len N] [--min-len-ratio R]
                  [--min-len-floor N] [--trim] [--math bf16|f32] [--stream [--slots 32]]
-                 [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32]]
+                 [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
                  [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
@@ -13,12 +13,16 @@ Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout 
 batching, KokoroEngine.generate_stream) instead of in fixed batches of --batch-size; the mels are the same.
 --vocoder (a HiFi-GAN generator checkpoint: a directory with generator.pth + config.json, or a file) also writes <name>.wav: the
 saved mel, clamped to [-11.5, 2] (:590), vocoded on the device in batches, int16 PCM at the vocoder config's sampling_rate.
+--denoise (with --vocoder) takes the generator's stationary noise floor out of every waveform before it is written: S (default 0.005)
+times the magnitude spectrum of what the generator makes of a silent mel is subtracted from the magnitude of every STFT frame, the
+phase kept (kokoro_ruslan_amd.denoise).
 --griffin-lim writes the same <name>.wav with the reference's Griffin-Lim vocoder instead (kokoro_ruslan_amd.griffinlim, 80 mels,
 22050 Hz; :684-739), no checkpoint needed: N iterations (default 60) from random phases drawn under seed S (default: unseeded)."""
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 from typing import List, Optional, Tuple
@@ -47,6 +51,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--vocoder", metavar="PATH", default=None, help="HiFi-GAN generator: directory or checkpoint file")
     p.add_argument("--vocoder-config", metavar="JSON", default=None, help="HiFi-GAN config (default: the checkpoint's config.json)")
     p.add_argument("--vocoder-math", choices=("bf16", "f32"), default="bf16")
+    p.add_argument("--denoise", type=float, nargs="?", const=0.005, default=None, metavar="S",
+                   help="subtract S (default 0.005) times the vocoder's bias spectrum from every waveform (needs --vocoder)")
     p.add_argument("--griffin-lim", action="store_true", help="vocode with Griffin-Lim (no checkpoint; not with --vocoder)")
     p.add_argument("--griffin-lim-iters", type=int, default=60, metavar="N")
     p.add_argument("--griffin-lim-seed", type=int, default=None, metavar="S", help="seed of the initial random phases")
@@ -60,6 +66,11 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--griffin-lim-iters / --griffin-lim-seed need --griffin-lim")
     if args.griffin_lim_iters < 0:
         p.error("--griffin-lim-iters must be >= 0")
+    if args.denoise is not None:
+        if args.griffin_lim or not args.vocoder:
+            p.error("--denoise needs --vocoder: the bias it subtracts is a HiFi-GAN generator's (not with --griffin-lim)")
+        if not math.isfinite(args.denoise) or args.denoise < 0:
+            p.error("--denoise must be >= 0")
     if args.slots is not None and not args.stream:
         p.error("--slots needs --stream")
     if args.slots is not None and args.slots < 1:
@@ -136,9 +147,17 @@ def main(argv=None) -> int:
         from kokoro_ruslan_amd.vocoder import HifiganVocoder
         voc = HifiganVocoder.from_checkpoint(args.vocoder, args.vocoder_config, device=engine.device, math_mode=args.vocoder_math)
         audio = vocode(voc, saved)
+        how = f"{args.vocoder_math} vocoder"
+        if args.denoise is not None:
+            from kokoro.inference.audio import denoise
+            from kokoro_ruslan_amd.denoise import SpectralDenoiser
+            den = SpectralDenoiser(device=engine.device)
+            den.bias_from_vocoder(voc)
+            audio = denoise(den, audio, args.denoise)
+            how += f", denoised at strength {args.denoise:g}"
         for name, a in zip(names, audio):
             write_wav(os.path.join(args.output, f"{name}.wav"), a, voc.sampling_rate)
-        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({args.vocoder_math} vocoder) -> {args.output}")
+        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({how}) -> {args.output}")
     if args.griffin_lim:
         from kokoro.inference.audio import vocode, write_wav
         from kokoro_ruslan_amd.griffinlim import GriffinLimVocoder

@@ -1,6 +1,7 @@
 """Mels to audio: the engine-side counterpart of the reference's vocoder step (inference/inference.py:588-634, 684-739) and of
 AudioUtils.save_audio.  `vocode` runs a batch of mels through a kokoro_ruslan_amd.vocoder.HifiganVocoder or a
-kokoro_ruslan_amd.griffinlim.GriffinLimVocoder; `write_wav` writes one waveform as 16-bit PCM."""
+kokoro_ruslan_amd.griffinlim.GriffinLimVocoder; `denoise` takes the vocoder's stationary noise floor out of a batch of waveforms with a
+kokoro_ruslan_amd.denoise.SpectralDenoiser; `write_wav` writes one waveform as 16-bit PCM."""
 from __future__ import annotations
 
 from typing import List, Sequence
@@ -15,6 +16,12 @@ def vocode(vocoder, mels: Sequence[torch.Tensor], clamp: bool = True, **kwargs) 
     if clamp:
         mels = [torch.clamp(m, min=-11.5, max=2.0) for m in mels]
     return vocoder.vocode(list(mels), **kwargs)
+
+
+def denoise(denoiser, waves: Sequence[torch.Tensor], strength: float = 0.005) -> List[torch.Tensor]:
+    """The waveforms less `strength` times the denoiser's bias spectrum in every STFT frame (phase kept), in input order and of the same
+    lengths.  The denoiser's bias must be set (SpectralDenoiser.bias_from_vocoder, once per vocoder)."""
+    return denoiser.denoise(list(waves), strength=strength)
 
 
 def write_wav(path: str, audio, sample_rate: int) -> None:

@@ -241,6 +241,9 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_gl_init": [_P, _L, _P, _P, _P, _P, _P, _P],
     "kk_gl_iter": [_P, _P, _P, _P, _P, _I, _P, _P, _F, _P],
     "kk_gl_istft": [_P, _P, _I, _P, _P, _P, _P],
+    "kk_denoise_tile_frames": [],
+    "kk_denoise": [_P, _P, _P, _I, _P, _F, _P, _P, _P, _P],
+    "kk_stft_mag_mean": [_P, _L, _I, _I, _P, _P, _P, _P],
     "kk_feat_mel_tile_frames": [],
     "kk_feat_peak": [_P, _P, _I, _L, _P, _P],
     "kk_feat_mel": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
