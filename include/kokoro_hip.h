@@ -466,6 +466,33 @@ int kk_denoise(const float *wave, const int64_t *woff, const int *tiles, int nti
  * order: the bias of a vocoder from what it makes of a silent mel */
 int kk_stft_mag_mean(const float *wave, int64_t n, int f_lo, int f_hi, const void *tw, const float *win, float *out, void *stream);
 
+/* ---- edge trimming, integrated loudness and gain (kokoro_ruslan_amd/loudness.py; kk_loudness.hip) for a packed batch ----
+ * Mono fp32 waveforms packed back to back: woff int64 [B + 1] sample offsets, every utterance >= 1 sample, fewer than 2^31 samples in
+ * all.  The definitions (frames of 1024 at hop 256 for the trim; ITU-R BS.1770-4 K-weighting, 400 ms blocks at 100 ms steps and both
+ * gates for the loudness) are restated in fp64 in kokoro_ruslan_amd/loudness_torch.py.  The five calls run back to back on one stream
+ * with no host read between them; all sums are fp64 in an order fixed by the sample's position in its own utterance (from `start`),
+ * so an utterance's results do not depend on the batch.  fs in [8000, 48000]: S = round(0.1 fs), N = round(0.4 fs). */
+/* hopsq[hoff[b] + h] = sum of squares of samples [256 h, 256 h + 256) of utterance b; hoff int32 [B + 1]: offsets of the
+ * ceil(n_b / 256) hops per utterance, nhops = hoff[B] */
+int kk_loud_hop_energy(const float *wave, const int64_t *woff, const int *hoff, int B, int nhops, double *hopsq, void *stream);
+/* se int32 [B][2] = {start, end}: frame t = samples [256 t - 512, 256 t + 512), 1 + n / 256 frames; loud = energy above the loudest
+ * frame's less top_db (> 0) dB; start = max(0, 256 first - margin), end = min(n, 256 (last + 1) + margin); all zeros: {0, n} */
+int kk_loud_edges(const double *hopsq, const int64_t *woff, const int *hoff, int B, double top_db, int margin, int *se, void *stream);
+/* per step k of S samples of [start, end) counted from start (soff int32 [B + 1]: offsets of ceil(n_b / S) slots per utterance,
+ * nsteps = soff[B]): stepsq = sum of squares of the K-weighted samples (filters at zero state at start), stepex = the part of it on
+ * the step's first N - 4 S (> 0) or last 4 S - N (> 0) sample positions, steppk = max |x|.  coef: double [10] = b0 b1 b2 a1 a2 of the
+ * shelving stage, then of the high-pass stage.  Slots past the trimmed range are left unwritten. */
+int kk_loud_kweight(const float *wave, const int64_t *woff, const int *se, const int *soff, int B, int nsteps, int S, int N,
+                    const double *coef, double *stepsq, double *stepex, float *steppk, void *stream);
+/* stats double [B][4] = {L in LUFS or -inf, gain (an fp32 value), limited 0 / 1, max |x[start:end]|}: gain = 10^((target - L) / 20),
+ * lowered to ceiling / peak where it would exceed that (ceiling in (0, 1], linear); L = -inf: gain 1 */
+int kk_loud_gate(const double *stepsq, const double *stepex, const float *steppk, const int *se, const int *soff, int B, int S, int N,
+                 double target, double ceiling, double *stats, void *stream);
+/* out[woff[b] + i] = wave[woff[b] + start_b + i] * gain_b for i < end_b - start_b; the rest of out is left unwritten.  out != wave;
+ * total = woff[B] */
+int kk_loud_apply(const float *wave, const int64_t *woff, const int *se, const double *stats, int B, int64_t total, float *out,
+                  void *stream);
+
 /* ---- audio feature extraction (kokoro_ruslan_amd/features.py; kk_features.hip): waveforms -> log-mel, pitch, energy ----
  * The reference's per-utterance front-end (22050 Hz, n_fft = win = 1024, hop 256, 80 HTK mels; pitch window 2048, lags 27..441), fp32.
  * The waveforms of a batch are packed back to back: woff int64 [B + 1] sample offsets.  moff int32 [B + 1]: offsets of the mel frames

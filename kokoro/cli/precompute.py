@@ -1,18 +1,26 @@
 """kokoro-precompute: write the feature cache kokoro-train reads, with the acoustic features extracted on the device.
 
     kokoro-precompute --wavs DIR --ids FILE.jsonl --cache-dir OUT [--force] [--no-variance] [--resample] [--batch-size N]
-                      [--max-seq-length N]
+                      [--max-seq-length N] [--trim-silence [DB]] [--loudness [LUFS]] [--peak-db DB] [--conditioned-wavs DIR]
 
 FILE.jsonl is kokoro-synth --ids's format, one utterance per line: {"name", "phoneme_indices"[, "stress_indices"]}, plus optional
 "phoneme_durations" (frames per phoneme, from kokoro-align or an MFA alignment; absent: the reference's even fallback estimate) and "text".
 DIR/<name>.wav is the audio, 22050 Hz; with --resample audio at another rate is resampled to 22050 Hz on the device first (the
 reference's torchaudio.transforms.Resample, data/dataset.py:662-665) instead of being refused.  The phonemizer and MFA alignment are
 not part of this tool: it takes their results.  Entries of the current cache version are skipped unless --force, as the reference's kokoro-precompute does.
+--trim-silence cuts what lies more than DB (default 40) dB under the loudest frame at either end of every waveform, keeping 50 ms
+(the reference trims its corpus with a VAD before alignment, cli/preprocess.py:24-33); --loudness scales every waveform to LUFS
+(default -23) integrated loudness under a peak of --peak-db (default -1) dB (kokoro_ruslan_amd.loudness).  Both run on the device
+after --resample and before the features, which are computed from the conditioned fp32 audio.  Durations made for the untrimmed audio
+no longer fit: --trim-silence refuses an --ids file that carries phoneme_durations; run kokoro-align on the new cache afterwards.
+--conditioned-wavs DIR writes every conditioned waveform as DIR/<name>.wav (int16: the rounding of the audio the features saw), so a
+corpus that trains with speed perturbation can point {data_dir}/wavs at audio that matches the cache.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 from typing import Dict, List
@@ -28,6 +36,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resample", action="store_true", help="resample audio at another rate to 22050 Hz on the device instead of refusing it")
     p.add_argument("--batch-size", type=int, default=32, help="utterances per device call")
     p.add_argument("--max-seq-length", type=int, default=1800, help="mel frames kept per utterance")
+    p.add_argument("--trim-silence", type=float, nargs="?", const=40.0, default=None, metavar="DB",
+                   help="cut leading and trailing audio more than DB (default 40) dB under the loudest frame, keeping 50 ms; not with "
+                        "phoneme_durations in --ids: run kokoro-align afterwards")
+    p.add_argument("--loudness", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS",
+                   help="scale every waveform to LUFS (default -23) integrated loudness")
+    p.add_argument("--peak-db", type=float, default=-1.0, metavar="DB", help="peak ceiling of --loudness in dB of full scale (default -1)")
+    p.add_argument("--conditioned-wavs", metavar="DIR", default=None,
+                   help="write every trimmed / levelled waveform as DIR/<name>.wav (needs --trim-silence or --loudness)")
     p.add_argument("--n-mels", type=int, default=80)
     p.add_argument("--hop-length", type=int, default=256)
     p.add_argument("--sample-rate", type=int, default=22050)
@@ -42,6 +58,17 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--batch-size must be >= 1")
     if args.max_seq_length < 1:
         p.error("--max-seq-length must be >= 1")
+    if args.trim_silence is not None and not (math.isfinite(args.trim_silence) and args.trim_silence > 0):
+        p.error("--trim-silence must be > 0 (dB under the loudest frame)")
+    if args.loudness is not None:
+        if not math.isfinite(args.loudness):
+            p.error("--loudness must be finite")
+        if not math.isfinite(args.peak_db) or args.peak_db > 0:
+            p.error("--peak-db must be <= 0")
+    elif args.peak_db != -1.0:
+        p.error("--peak-db needs --loudness")
+    if args.conditioned_wavs is not None and args.trim_silence is None and args.loudness is None:
+        p.error("--conditioned-wavs needs --trim-silence or --loudness: there is nothing else to write")
 
 
 def read_extras(path: str) -> Dict[str, Dict]:
@@ -66,6 +93,16 @@ def main(argv=None) -> int:
 
     names, ids, stress = read_ids(args.ids)
     extras = read_extras(args.ids)
+    if args.trim_silence is not None:
+        for name in names:
+            if extras[name]["phoneme_durations"] is not None:
+                p.error(f"--trim-silence: {name} carries phoneme_durations, which were made for the untrimmed audio and no longer sum "
+                        f"to the trimmed length; drop them from {args.ids} and run kokoro-align on the new cache")
+    conditioning = args.trim_silence is not None or args.loudness is not None
+    norm = None
+    trimmed_samples = limited = unmeasured = 0
+    if args.conditioned_wavs is not None:
+        os.makedirs(args.conditioned_wavs, exist_ok=True)
     todo: List[int] = []
     skipped = 0
     for i, name in enumerate(names):
@@ -100,6 +137,27 @@ def main(argv=None) -> int:
                 failed += len(batch)
                 print(f"kokoro-precompute: resampling the batch of {names[batch[0]]}: {e}", file=sys.stderr)
                 continue
+        if conditioning:
+            try:
+                if norm is None:
+                    from kokoro_ruslan_amd.loudness import LoudnessNormaliser
+                    norm = LoudnessNormaliser(sample_rate=args.sample_rate)
+                before = [int(w.numel()) for w in waves]
+                if args.loudness is not None:
+                    waves, info = norm.normalise(waves, args.loudness, args.peak_db, trim_db=args.trim_silence)
+                    limited += sum(i["limited"] for i in info)
+                    unmeasured += sum(i["measured"] is None for i in info)
+                else:
+                    waves = [w[s0:e0] for w, (s0, e0) in zip(waves, norm.trim_edges(waves, args.trim_silence))]
+                trimmed_samples += sum(before) - sum(int(w.numel()) for w in waves)
+                if args.conditioned_wavs is not None:
+                    from kokoro.inference.audio import write_wav
+                    for i, w in zip(batch, waves):
+                        write_wav(os.path.join(args.conditioned_wavs, names[i] + ".wav"), w, args.sample_rate, normalise=False)
+            except Exception as e:
+                failed += len(batch)
+                print(f"kokoro-precompute: conditioning the batch of {names[batch[0]]}: {e}", file=sys.stderr)
+                continue
         feats = ext.extract(waves, max_seq_length=args.max_seq_length, variance=not args.no_variance)
         for i, ft in zip(batch, feats):
             try:
@@ -111,6 +169,11 @@ def main(argv=None) -> int:
             except Exception as e:
                 failed += 1
                 print(f"kokoro-precompute: {names[i]}: {e}", file=sys.stderr)
+    if conditioning:
+        what = [f"{trimmed_samples} samples trimmed"] if args.trim_silence is not None else []
+        if args.loudness is not None:
+            what.append(f"{limited} gains peak-limited, {unmeasured} waveforms too short or quiet to measure (left at gain 1)")
+        print(f"kokoro-precompute: conditioning: {', '.join(what)}")
     print(f"kokoro-precompute: {computed} computed, {skipped} skipped, {failed} failed ({len(names)} utterances) -> {args.cache_dir}")
     return 0 if failed == 0 else 1
 

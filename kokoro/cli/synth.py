@@ -5,6 +5,7 @@
                  [--min-len-floor N] [--trim] [--math bf16|f32] [--stream [--slots 32]]
                  [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
                  [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]]
+                 [--loudness [LUFS] [--peak-db DB]]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
 --features reads phoneme_indices / stress_indices from a precomputed feature cache (kokoro.data.cached); --ids reads JSON lines
@@ -17,7 +18,10 @@ saved mel, clamped to [-11.5, 2] (:590), vocoded on the device in batches, int16
 times the magnitude spectrum of what the generator makes of a silent mel is subtracted from the magnitude of every STFT frame, the
 phase kept (kokoro_ruslan_amd.denoise).
 --griffin-lim writes the same <name>.wav with the reference's Griffin-Lim vocoder instead (kokoro_ruslan_amd.griffinlim, 80 mels,
-22050 Hz; :684-739), no checkpoint needed: N iterations (default 60) from random phases drawn under seed S (default: unseeded)."""
+22050 Hz; :684-739), no checkpoint needed: N iterations (default 60) from random phases drawn under seed S (default: unseeded).
+--loudness (with --vocoder or --griffin-lim) brings every waveform to LUFS (default -23) integrated loudness (ITU-R BS.1770-4,
+kokoro_ruslan_amd.loudness) with its peak at or under --peak-db (default -1) dB of full scale, after --denoise and before the .wav is
+written; the .wav then keeps that level instead of being peak-normalised.  A waveform shorter than one 400 ms block is left as it is."""
 from __future__ import annotations
 
 import argparse
@@ -56,6 +60,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--griffin-lim", action="store_true", help="vocode with Griffin-Lim (no checkpoint; not with --vocoder)")
     p.add_argument("--griffin-lim-iters", type=int, default=60, metavar="N")
     p.add_argument("--griffin-lim-seed", type=int, default=None, metavar="S", help="seed of the initial random phases")
+    p.add_argument("--loudness", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS",
+                   help="bring every waveform to LUFS (default -23) integrated loudness (needs --vocoder or --griffin-lim)")
+    p.add_argument("--peak-db", type=float, default=-1.0, metavar="DB", help="peak ceiling of --loudness in dB of full scale (default -1)")
     return p
 
 
@@ -71,6 +78,15 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
             p.error("--denoise needs --vocoder: the bias it subtracts is a HiFi-GAN generator's (not with --griffin-lim)")
         if not math.isfinite(args.denoise) or args.denoise < 0:
             p.error("--denoise must be >= 0")
+    if args.loudness is not None:
+        if not (args.vocoder or args.griffin_lim):
+            p.error("--loudness needs --vocoder or --griffin-lim: it works on the waveforms")
+        if not math.isfinite(args.loudness):
+            p.error("--loudness must be finite")
+        if not math.isfinite(args.peak_db) or args.peak_db > 0:
+            p.error("--peak-db must be <= 0")
+    elif args.peak_db != -1.0:
+        p.error("--peak-db needs --loudness")
     if args.slots is not None and not args.stream:
         p.error("--slots needs --stream")
     if args.slots is not None and args.slots < 1:
@@ -114,6 +130,26 @@ def read_features(cache_dir: str, indices=None) -> Tuple[List[str], List[torch.T
     return names, ids, stress
 
 
+def level_and_write(args, names, audio, sample_rate: int, device) -> str:
+    """Write <name>.wav per waveform; with --loudness at that level (not peak-normalised).  Returns what to add to the summary line."""
+    from kokoro.inference.audio import normalise_loudness, write_wav
+    note = ""
+    if args.loudness is not None:
+        from kokoro_ruslan_amd.loudness import LoudnessNormaliser
+        peak_db = args.peak_db
+        audio, info = normalise_loudness(LoudnessNormaliser(device=device, sample_rate=sample_rate), audio, args.loudness, peak_db)
+        limited = [n for n, i in zip(names, info) if i["limited"]]
+        unmeasured = [n for n, i in zip(names, info) if i["measured"] is None]
+        note = f", {args.loudness:g} LUFS under {peak_db:g} dB"
+        if limited:
+            note += f", {len(limited)} peak-limited: {' '.join(limited)}"
+        if unmeasured:
+            note += f", {len(unmeasured)} too short or quiet to measure: {' '.join(unmeasured)}"
+    for name, a in zip(names, audio):
+        write_wav(os.path.join(args.output, f"{name}.wav"), a, sample_rate, normalise=args.loudness is None)
+    return note
+
+
 def main(argv=None) -> int:
     import numpy as np
     from kokoro.inference.synth import load_for_inference, synthesize, trim_trailing_silence
@@ -143,7 +179,7 @@ def main(argv=None) -> int:
         saved.append(mel)
     print(f"kokoro-synth: {len(mels)} mels ({used} weights, {controls}) -> {args.output}")
     if args.vocoder:
-        from kokoro.inference.audio import vocode, write_wav
+        from kokoro.inference.audio import vocode
         from kokoro_ruslan_amd.vocoder import HifiganVocoder
         voc = HifiganVocoder.from_checkpoint(args.vocoder, args.vocoder_config, device=engine.device, math_mode=args.vocoder_math)
         audio = vocode(voc, saved)
@@ -155,19 +191,16 @@ def main(argv=None) -> int:
             den.bias_from_vocoder(voc)
             audio = denoise(den, audio, args.denoise)
             how += f", denoised at strength {args.denoise:g}"
-        for name, a in zip(names, audio):
-            write_wav(os.path.join(args.output, f"{name}.wav"), a, voc.sampling_rate)
+        how += level_and_write(args, names, audio, voc.sampling_rate, engine.device)
         print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({how}) -> {args.output}")
     if args.griffin_lim:
-        from kokoro.inference.audio import vocode, write_wav
+        from kokoro.inference.audio import vocode
         from kokoro_ruslan_amd.griffinlim import GriffinLimVocoder
         gen = torch.Generator().manual_seed(args.griffin_lim_seed) if args.griffin_lim_seed is not None else None
         voc = GriffinLimVocoder(device=engine.device)
         audio = vocode(voc, saved, n_iter=args.griffin_lim_iters, generator=gen)
-        for name, a in zip(names, audio):
-            write_wav(os.path.join(args.output, f"{name}.wav"), a, voc.sampling_rate)
-        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz (Griffin-Lim, {args.griffin_lim_iters} iterations) "
-              f"-> {args.output}")
+        how = f"Griffin-Lim, {args.griffin_lim_iters} iterations" + level_and_write(args, names, audio, voc.sampling_rate, engine.device)
+        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({how}) -> {args.output}")
     return 0
 
 

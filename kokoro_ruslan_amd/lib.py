@@ -244,6 +244,11 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_denoise_tile_frames": [],
     "kk_denoise": [_P, _P, _P, _I, _P, _F, _P, _P, _P, _P],
     "kk_stft_mag_mean": [_P, _L, _I, _I, _P, _P, _P, _P],
+    "kk_loud_hop_energy": [_P, _P, _P, _I, _I, _P, _P],
+    "kk_loud_edges": [_P, _P, _P, _I, _D, _I, _P, _P],
+    "kk_loud_kweight": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "kk_loud_gate": [_P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _P, _P],
+    "kk_loud_apply": [_P, _P, _P, _P, _I, _L, _P, _P],
     "kk_feat_mel_tile_frames": [],
     "kk_feat_peak": [_P, _P, _I, _L, _P, _P],
     "kk_feat_mel": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
