@@ -410,6 +410,22 @@ int kk_slot_admit(const void *kv_src, void *kv_pool, const uint8_t *fm_src, uint
                   int *t_rows, int *done, int *frames, int *clen, int *min_b, int *expected_b, int *max_b, float *mel_all, int *live,
                   int n, int T_adm, int S, int cap, int64_t row_bytes, int L1, int M, void *stream);
 
+/* ---- prosody control of the synthesis prefill (kokoro_ruslan_amd/prosody.py; kk_prosody.hip; fp32 restatement: prosody_torch.py).
+ * The tables are [B, Pn], one entry per phoneme; padding entries carry the neutral value (speed 1, scale 1, shift 0, forced -1 / NaN).
+ * prosody_durations: d = expm1(log_dur) fp32 [B, Pn].  base = max(rint(d), 0); scaled = base == 0 ? 0 : max(rint(d / speed), 1) (fp32
+ *   division, rounding half to even: torch.round(d / speed)); dur_out[b, p] (int64) = forced[b, p] >= 0 ? forced[b, p] : scaled, and 0
+ *   for p >= plens[b] (plens int32 [B], or NULL: every position counts).  sums_out[b] (int64) = the row's sum.  At speed 1 with
+ *   nothing forced this is clamp(round(d), 0).
+ * prosody_variance: pitch, energy [B, T] = the predictors' outputs; idx [B, T], lens [B] (int64) as kk_length_regulate_index wrote
+ *   them.  c = clamp(pred, 0, 1).  Frame t < lens[b] of phoneme j = idx[b, t]: pitch_out = fp[b, j] when that is not NaN, else
+ *   clamp(c * ps[b, j] + pb[b, j], 0, 1) when c > 0, else c (an unvoiced frame stays unvoiced); energy_out = fe[b, j] when that is not
+ *   NaN, else clamp(c * es[b, j] + eb[b, j], 0, 1).  The product and the sum round separately (no fma).  Frames t >= lens[b] get c. */
+int kk_prosody_durations(const float *d, const float *speed, const int *forced, const int *plens, int64_t *dur_out, int64_t *sums_out,
+                         int B, int Pn, void *stream);
+int kk_prosody_variance(const float *pitch, const float *energy, const int64_t *idx, const int64_t *lens, const float *ps, const float *pb,
+                        const float *es, const float *eb, const float *fp, const float *fe, float *pitch_out, float *energy_out, int B,
+                        int Pn, int T, void *stream);
+
 /* ---- HiFi-GAN vocoder (kokoro_ruslan_amd/vocoder.py; kk_vocoder.hip): mels -> waveforms for a packed batch ----
  * Activations are channels-last fp32 [rows, C]; the utterances are packed back to back along time and seg[0..nseg] holds their
  * start rows in the layer's INPUT row units (seg[0] = 0, seg[nseg] = rows).  A tap never reads outside its own utterance: each

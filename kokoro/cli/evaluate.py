@@ -3,6 +3,7 @@
     kokoro-eval --checkpoint CKPT --features CACHE_DIR [--indices ...] [--split val|train|all] [--validation-split 0.1]
                 [--weights auto|ema|model] [--math bf16|f32] [--no-stream] [--slots N] [--batch-size N] [--mcep K]
                 [--stop-threshold X] [--max-len N] [--min-len-ratio R] [--min-len-floor N] [--output REPORT.json]
+                [--oracle-durations]
 
 Synthesizes every selected utterance with the stop rule deciding its length (continuous batching in a pool of --slots rows, or with
 --no-stream in batches of --batch-size), aligns each mel with the cached ground truth by dynamic time warping on K mel cepstra and
@@ -10,7 +11,10 @@ prints, one line per metric, the mean, median and 95th percentile of: mcd_dtw (m
 mel_l1_dtw (mean |difference| of the aligned log-mels), len_ratio (synthesized / true frames), dur_abs_err (|sum of predicted
 durations - sum of true ones|, frames); plus the share of utterances that ran into their generation bound.  --split val takes the
 utterances `kokoro-train --validation-split` holds out (the same draw: kokoro.data.cached.split_indices), --indices names utterances
-of the cache's length-sorted order instead.  --output writes records, summary, controls and the weights used as JSON."""
+of the cache's length-sorted order instead.  --output writes records, summary, controls and the weights used as JSON.
+--oracle-durations forces the cache's phoneme_durations on every utterance (kokoro_ruslan_amd.prosody): dur_abs_err is then 0 and
+len_ratio, mcd_dtw and mel_l1_dtw show the decoder alone, without the duration predictor's errors.  An utterance whose cache entry
+holds no durations for its phonemes is an error that names it."""
 from __future__ import annotations
 
 import argparse
@@ -40,6 +44,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min-len-ratio", type=float, default=None)
     p.add_argument("--min-len-floor", type=int, default=None)
     p.add_argument("--output", metavar="REPORT.json", default=None)
+    p.add_argument("--oracle-durations", action="store_true", help="synthesize on the cache's phoneme_durations instead of the predicted ones")
     return p
 
 
@@ -90,6 +95,17 @@ def read_features(cache_dir: str, split: Optional[str], validation_split: float,
     return names, ids, stress, mels, durs
 
 
+def oracle_prosody(names, ids, durs):
+    """One Prosody per utterance that forces the cache's durations; ValueError names an utterance that has none for its phonemes."""
+    from kokoro_ruslan_amd.prosody import Prosody
+    out = []
+    for name, u, dur in zip(names, ids, durs):
+        if dur is None or dur.numel() != u.numel() or dur.numel() == 0 or bool((dur < 0).any()):
+            raise ValueError(f"--oracle-durations: utterance {name} has no durations for its {int(u.numel())} phonemes in the cache")
+        out.append(Prosody(durations=dur.to(torch.int64)).validate(int(u.numel())))
+    return out
+
+
 def main(argv=None) -> int:
     from kokoro.inference import evaluate as E
     from kokoro.inference import synth as S
@@ -104,9 +120,15 @@ def main(argv=None) -> int:
                                                   min_len_floor=args.min_len_floor)
     if engine.dims.mel != mels[0].shape[1]:
         parser.error(f"the checkpoint makes {engine.dims.mel} mel channels, the cache holds {mels[0].shape[1]}")
+    pkw = {}
+    if args.oracle_durations:
+        try:
+            pkw["prosody"] = oracle_prosody(names, ids, durs)
+        except ValueError as e:
+            parser.error(str(e))
     records, summary = E.evaluate(engine, ids, stress, mels, stream=not args.no_stream, slots=32 if args.slots is None else args.slots,
                                   batch_size=32 if args.batch_size is None else args.batch_size, durations=durs, names=names,
-                                  mcep=args.mcep, **controls.kwargs())
+                                  mcep=args.mcep, **pkw, **controls.kwargs())
     print(f"kokoro-eval: {summary['utterances']} utterances ({used} weights, {controls}), "
           f"{100.0 * summary['hit_bound_share']:.1f} % ended at their generation bound")
     for k in E.METRICS:
@@ -116,7 +138,8 @@ def main(argv=None) -> int:
     if args.output:
         with open(args.output, "w") as f:
             json.dump({"records": records, "summary": summary, "controls": controls.kwargs(), "weights": used, "mcep": args.mcep,
-                       "split": "indices" if args.indices is not None else (args.split or "val"), "checkpoint": args.checkpoint}, f, indent=1)
+                       "split": "indices" if args.indices is not None else (args.split or "val"), "checkpoint": args.checkpoint,
+                       **({"oracle_durations": True} if args.oracle_durations else {})}, f, indent=1)
         print(f"kokoro-eval: report -> {args.output}")
     return 0
 

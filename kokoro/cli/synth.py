@@ -6,6 +6,7 @@
                  [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
                  [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]]
                  [--loudness [LUFS] [--peak-db DB]]
+                 [--speed F] [--pitch-scale F] [--pitch-shift F] [--energy-scale F] [--energy-shift F]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
 --features reads phoneme_indices / stress_indices from a precomputed feature cache (kokoro.data.cached); --ids reads JSON lines
@@ -21,7 +22,11 @@ phase kept (kokoro_ruslan_amd.denoise).
 22050 Hz; :684-739), no checkpoint needed: N iterations (default 60) from random phases drawn under seed S (default: unseeded).
 --loudness (with --vocoder or --griffin-lim) brings every waveform to LUFS (default -23) integrated loudness (ITU-R BS.1770-4,
 kokoro_ruslan_amd.loudness) with its peak at or under --peak-db (default -1) dB of full scale, after --denoise and before the .wav is
-written; the .wav then keeps that level instead of being peak-normalised.  A waveform shorter than one 400 ms block is left as it is."""
+written; the .wav then keeps that level instead of being peak-normalised.  A waveform shorter than one 400 ms block is left as it is.
+--speed / --pitch-scale / --pitch-shift / --energy-scale / --energy-shift steer every utterance (kokoro_ruslan_amd.prosody.Prosody:
+frames per phoneme divided by the speed, in [0.25, 4]; scale and shift on the normalised pitch of voiced frames and on the normalised
+energy).  A line of --ids may carry "prosody": {...} with the fields of Prosody.from_json (also per-phoneme lists and forced
+"durations" / "pitch" / "energy"); its fields override the flags for that line."""
 from __future__ import annotations
 
 import argparse
@@ -63,6 +68,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loudness", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS",
                    help="bring every waveform to LUFS (default -23) integrated loudness (needs --vocoder or --griffin-lim)")
     p.add_argument("--peak-db", type=float, default=-1.0, metavar="DB", help="peak ceiling of --loudness in dB of full scale (default -1)")
+    # (prosody flags leave no attribute behind when they are not given: an invocation without them parses as it always did)
+    p.add_argument("--speed", type=float, default=argparse.SUPPRESS, metavar="F", help="frames per phoneme are divided by F, in [0.25, 4]")
+    p.add_argument("--pitch-scale", type=float, default=argparse.SUPPRESS, metavar="F", help="factor on the normalised pitch of voiced frames (>= 0)")
+    p.add_argument("--pitch-shift", type=float, default=argparse.SUPPRESS, metavar="F", help="added to the normalised pitch of voiced frames")
+    p.add_argument("--energy-scale", type=float, default=argparse.SUPPRESS, metavar="F", help="factor on the normalised energy (>= 0)")
+    p.add_argument("--energy-shift", type=float, default=argparse.SUPPRESS, metavar="F", help="added to the normalised energy")
     return p
 
 
@@ -87,6 +98,10 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
             p.error("--peak-db must be <= 0")
     elif args.peak_db != -1.0:
         p.error("--peak-db needs --loudness")
+    try:
+        prosody_flags(args)
+    except ValueError as e:
+        p.error(str(e))
     if args.slots is not None and not args.stream:
         p.error("--slots needs --stream")
     if args.slots is not None and args.slots < 1:
@@ -116,6 +131,38 @@ def read_ids(path: str) -> Tuple[List[str], List[torch.Tensor], Optional[List[to
     if any(s is None for s in stress):
         raise ValueError(f"{path}: stress_indices must be given on every line or on none")
     return names, ids, stress
+
+
+PROSODY_FLAGS = ("speed", "pitch_scale", "pitch_shift", "energy_scale", "energy_shift")
+
+
+def prosody_flags(args) -> dict:
+    """The prosody flags given on the command line as Prosody.from_json fields (validated; ValueError names the flag's field)."""
+    from kokoro_ruslan_amd.prosody import Prosody
+    given = {k: getattr(args, k) for k in PROSODY_FLAGS if getattr(args, k, None) is not None}       # (absent unless given)
+    Prosody.from_json(given, 1)
+    return given
+
+
+def read_prosody(path: str, flags: dict):
+    """One Prosody per line of a --ids file: the line's "prosody" object over the flags (its fields win), or None when neither the
+    flags nor any line asks for anything."""
+    from kokoro_ruslan_amd.prosody import Prosody
+    out, any_given = [], bool(flags)
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            rec = json.loads(line)
+            own = rec.get("prosody")
+            if own is not None and not isinstance(own, dict):
+                raise ValueError(f"{path}:{n}: 'prosody' must be an object")
+            any_given = any_given or own is not None
+            try:
+                out.append(Prosody.from_json({**flags, **(own or {})}, len(rec["phoneme_indices"])))
+            except ValueError as e:
+                raise ValueError(f"{path}:{n}: {e}") from None
+    return out if any_given else None
 
 
 def read_features(cache_dir: str, indices=None) -> Tuple[List[str], List[torch.Tensor], List[torch.Tensor]]:
@@ -156,19 +203,26 @@ def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
     check_args(parser, args)
+    flags = prosody_flags(args)
     if args.ids:
         names, ids, stress = read_ids(args.ids)
+        prosody = read_prosody(args.ids, flags)
     else:
         names, ids, stress = read_features(args.features, args.indices)
+        prosody = None
+        if flags:
+            from kokoro_ruslan_amd.prosody import Prosody
+            prosody = Prosody.from_json(flags, 1)              # (scalars only: one entry serves every utterance)
     engine, controls, used = load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,
                                                 stop_threshold=args.stop_threshold, min_len_ratio=args.min_len_ratio,
                                                 min_len_floor=args.min_len_floor)
     if args.griffin_lim and engine.dims.mel != 80:
         parser.error(f"--griffin-lim needs an 80-mel model; this checkpoint makes {engine.dims.mel} mel channels")
+    pkw = {} if prosody is None else {"prosody": prosody}
     if args.stream:
-        mels = synthesize(engine, ids, stress, stream=True, slots=32 if args.slots is None else args.slots, **controls.kwargs())
+        mels = synthesize(engine, ids, stress, stream=True, slots=32 if args.slots is None else args.slots, **pkw, **controls.kwargs())
     else:
-        mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **controls.kwargs())
+        mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **pkw, **controls.kwargs())
     os.makedirs(args.output, exist_ok=True)
     saved = []
     for name, mel in zip(names, mels):

@@ -11,11 +11,14 @@ import torch
 METRICS = ("mcd_dtw", "mel_l1_dtw", "len_ratio", "dur_abs_err")
 
 
-def _generate(engine, ids, stress, stream: bool, slots: int, batch_size: int, controls: Dict[str, Any]):
-    """(mels, info) in input order: one generate_stream call, or synthesize()'s batches (sorted by phoneme count) of generate_batch."""
+def _generate(engine, ids, stress, stream: bool, slots: int, batch_size: int, controls: Dict[str, Any], prosody=None):
+    """(mels, info) in input order: one generate_stream call, or synthesize()'s batches (sorted by phoneme count) of generate_batch.
+    prosody: None, or one entry per utterance, handed to the engine with its utterance."""
     if stream:
         if slots < 1:
             raise ValueError("slots must be >= 1")
+        if prosody is not None:
+            controls = dict(controls, prosody=prosody)
         return engine.generate_stream(list(ids), list(stress) if stress is not None else None, slots=slots, want_info=True, **controls)
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
@@ -25,8 +28,9 @@ def _generate(engine, ids, stress, stream: bool, slots: int, batch_size: int, co
     info = {"durations": [None] * N, "T": [None] * N, "bounds": [None] * N}
     for s in range(0, N, batch_size):
         part = order[s:s + batch_size]
+        kw = controls if prosody is None else dict(controls, prosody=[prosody[i] for i in part])
         m, inf = engine.generate_batch([ids[i] for i in part], [stress[i] for i in part] if stress is not None else None,
-                                       want_info=True, **controls)
+                                       want_info=True, **kw)
         for n, i in enumerate(part):
             mels[i] = m[n]
             for k in info:
@@ -48,12 +52,14 @@ def summarize(records: Sequence[Dict]) -> Dict[str, Any]:
 
 def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]], ref_mels: Sequence[torch.Tensor], *,
              stream: bool = True, slots: int = 32, batch_size: int = 32, durations: Optional[Sequence[torch.Tensor]] = None,
-             names: Optional[Sequence[str]] = None, mcep: int = 13, aligner=None, **controls) -> Tuple[List[Dict], Dict[str, Any]]:
+             names: Optional[Sequence[str]] = None, mcep: int = 13, aligner=None, prosody=None,
+             **controls) -> Tuple[List[Dict], Dict[str, Any]]:
     """Synthesize every utterance free-running (generate_stream with `slots` rows, or generate_batch `batch_size` at a time) and
     compare it with ref_mels[i] [frames, n_mels].  controls: the stop controls of generate_batch.  Returns (records, summary):
     per utterance {"name", "frames", "ref_frames", "len_ratio", "mcd_dtw" (dB), "mel_l1_dtw", "hit_bound" (the row ended at its
     generation bound, not by the stop rule)} and, with ground-truth `durations`, "dur_abs_err" = |sum predicted - sum true| frames;
-    summarize() of them."""
+    summarize() of them.  prosody: one kokoro_ruslan_amd.prosody.Prosody for every utterance or one per utterance (None: no controls):
+    with the ground-truth durations forced, dur_abs_err is 0 and the other metrics are the decoder's alone."""
     N = len(ids)
     if len(ref_mels) != N:
         raise ValueError(f"{len(ref_mels)} reference mels for {N} utterances")
@@ -62,7 +68,10 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
             raise ValueError(f"{what}: {len(v)} entries for {N} utterances")
     if N == 0:
         return [], summarize([])
-    mels, info = _generate(engine, ids, stress, stream, slots, batch_size, controls)
+    if prosody is not None:
+        from kokoro_ruslan_amd.prosody import as_list
+        prosody = as_list(prosody, N)
+    mels, info = _generate(engine, ids, stress, stream, slots, batch_size, controls, prosody)
     if aligner is None:
         from kokoro_ruslan_amd.dtw import MelAligner
         aligner = MelAligner(device=engine.device, K=mcep)

@@ -118,25 +118,33 @@ def load_for_inference(path: str, weights: str = "auto", device: str = "cuda", m
 
 
 def synthesize(engine, utterances: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]] = None, batch_size: int = 32,
-               stream: bool = False, slots: int = 32, **stop_kwargs) -> List[torch.Tensor]:
+               stream: bool = False, slots: int = 32, prosody=None, **stop_kwargs) -> List[torch.Tensor]:
     """Mels [frames_b, n_mels] of every utterance, in input order.  Utterances are sorted by phoneme count and decoded
     `batch_size` at a time by engine.generate_batch (sorting keeps the padding and the shared length bound of a batch small).
     stream=True decodes them all in one engine.generate_stream call instead: a pool of `slots` rows in which a finished row's
-    slot is refilled with the next utterance (continuous batching; input order, no sorting, batch_size unused)."""
+    slot is refilled with the next utterance (continuous batching; input order, no sorting, batch_size unused).
+    prosody: one kokoro_ruslan_amd.prosody.Prosody for every utterance, or one per utterance in input order (None entries: neutral);
+    each batch is handed its utterances' controls.  None: no controls, the engine is called as without the argument."""
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     if stress is not None and len(stress) != len(utterances):
         raise ValueError(f"stress: {len(stress)} vectors for {len(utterances)} utterances")
+    if prosody is not None:
+        from kokoro_ruslan_amd.prosody import as_list
+        prosody = as_list(prosody, len(utterances))
     if stream:
         if slots < 1:
             raise ValueError("slots must be >= 1")
+        if prosody is not None:
+            stop_kwargs = dict(stop_kwargs, prosody=prosody)
         return list(engine.generate_stream(list(utterances), list(stress) if stress is not None else None, slots=slots, **stop_kwargs))
     order = sorted(range(len(utterances)), key=lambda i: (int(utterances[i].numel()), i))
     out: List[Optional[torch.Tensor]] = [None] * len(utterances)
     for s in range(0, len(order), batch_size):
         part = order[s:s + batch_size]
+        kw = stop_kwargs if prosody is None else dict(stop_kwargs, prosody=[prosody[i] for i in part])
         mels = engine.generate_batch([utterances[i] for i in part], [stress[i] for i in part] if stress is not None else None,
-                                     **stop_kwargs)
+                                     **kw)
         for i, m in zip(part, mels):
             out[i] = m
     return out

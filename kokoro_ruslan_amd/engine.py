@@ -30,6 +30,8 @@ import torch
 
 from . import lib as kk
 from . import spec
+from .prosody import as_list as prosody_list
+from .prosody import pack as pack_prosody
 from .spec import VA, ModelDims, StepHyper
 
 CHUNK = 512   # variance_predictor.py:77
@@ -1734,12 +1736,14 @@ class KokoroEngine:
             x = xo
         return y1
 
-    def _expand_fwd(self, ns, enc, dur, B, Pn, T, flens=None):
+    def _expand_fwd(self, ns, enc, dur, B, Pn, T, flens=None, controls=None):
         """The variance adaptor behind the durations, without targets (variance_predictor.py:338-439): repeat phoneme p of
         each row dur[b, p] times up to T frames, predict pitch and energy, add the bucket embeddings of the clamped predictions,
         and project the result to the cross-attention K|V of every decoder layer (_cross_kv_fwd_all under `ns`).  flens (int32
         [B]) makes the predictors see row b as a sequence of flens[b] frames; None = the padded batch as one.  Workspace keys
-        `ns` + "lr.* / va.* / vp.* / out.*".  Returns (memory [B*T, H], fm2 = the frame mask [B, T])."""
+        `ns` + "lr.* / va.* / vp.* / out.*".  controls (prosody.PackedProsody, or None: none): kk_prosody_variance puts the
+        per-phoneme pitch / energy controls on the clamped predictions in front of the bucket embeddings.
+        Returns (memory [B*T, H], fm2 = the frame mask [B, T])."""
         d, P, H, ddt = self.dims, self.arena.P, self.dims.hidden, self.dec_dt
         Nd = B * T
         idx, lens, tot = (self._buf(ns + "lr.idx", B, T, dtype=torch.int64), self._buf(ns + "lr.lens", B, dtype=torch.int64),
@@ -1760,11 +1764,27 @@ class KokoroEngine:
         self._varpred_fwd(ns + "vp.energy", f"{VA}.energy_predictor", xf, col_f, B, T, fmask, energy, lens=flens)
         memory, fm2 = self._buf(ns + "va.memory", Nd, H, dtype=ddt), self._buf(ns + "va.fmask", B, T, dtype=torch.uint8)
         pidx, eidx = self._buf(ns + "va.pidx", B, T, dtype=torch.int32), self._buf(ns + "va.eidx", B, T, dtype=torch.int32)
-        kk.call("kk_bucket_embed_add_fwd", xf, pitch.clamp(0.0, 1.0), energy.clamp(0.0, 1.0), P[f"{VA}.pitch_bins"],
-                P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
-                pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
+        if controls is None:
+            kk.call("kk_bucket_embed_add_fwd", xf, pitch.clamp(0.0, 1.0), energy.clamp(0.0, 1.0), P[f"{VA}.pitch_bins"],
+                    P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
+                    pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
+        else:
+            c, pc, ec = controls, torch.empty_like(pitch), torch.empty_like(energy)
+            kk.call("kk_prosody_variance", pitch, energy, idx, lens, c.pitch_ss[0], c.pitch_ss[1], c.energy_ss[0], c.energy_ss[1],
+                    c.pitch, c.energy, pc, ec, B, Pn, T)
+            kk.call("kk_bucket_embed_add_fwd", xf, pc, ec, P[f"{VA}.pitch_bins"],
+                    P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
+                    pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
         self._cross_kv_fwd_all(memory, Nd, T, ddt, ns=ns)          # cross-attention K|V of every layer, normalised
         return memory, fm2
+
+    def _controlled_durations(self, log_dur, controls, plens, B, Pn):
+        """Durations under prosody controls (kk_prosody_durations on torch's expm1(log_dur), so that neutral controls give the bits
+        of the torch line they replace).  Returns (dur int64 [B, Pn], row sums int64 [B])."""
+        dur = torch.empty(B, Pn, dtype=torch.int64, device=self.device)
+        sums = torch.empty(B, dtype=torch.int64, device=self.device)
+        kk.call("kk_prosody_durations", torch.expm1(log_dur).contiguous(), controls.speed, controls.durations, plens, dur, sums, B, Pn)
+        return dur, sums
 
     def _generation_bounds(self, expected, max_len, min_len_ratio, min_len_floor, max_len_ratio, max_len_cap, who=""):
         """(min, expected, max) frames of an utterance of `expected` predicted frames (model.py:741-750); `who` opens the message
@@ -1820,7 +1840,7 @@ class KokoroEngine:
     def generate(self, ids: torch.Tensor, stress: Optional[torch.Tensor] = None, max_len: int = 4000,
                  stop_threshold: float = 0.5, min_len_ratio: float = 0.7, min_len_floor: int = 12,
                  max_len_ratio: float = 3.0, max_len_cap: int = 1600, post_expected_stop_threshold: float = 0.2,
-                 check_every: int = 16, decode_graph: bool = True) -> torch.Tensor:
+                 check_every: int = 16, decode_graph: bool = True, prosody=None) -> torch.Tensor:
         """KokoroModel.forward_inference (model/model.py:676-790) + KokoroGenerator.generate (model/generator.py:24-127):
         encode, expand by the model's own durations, pick the pitch / energy embeddings from its own (clamped)
         predictions (variance_predictor.py:338-439 without targets), then decode one mel frame at a time against a KV
@@ -1838,11 +1858,15 @@ class KokoroEngine:
 
         The stages are generate_batch's (_encode_text_fwd, _varpred_fwd, _expand_fwd, _generation_bounds, _decode_state_init,
         _decode_step, _decode_loop).  Up to the decode state they run on the train step's workspace keys (no prefix), so an
-        engine that trains and synthesises shares those buffers; the decode state is under "gen."."""
+        engine that trains and synthesises shares those buffers; the decode state is under "gen.".
+
+        prosody: a prosody.Prosody for every row, or a list of B (None entries: neutral), each over the Pn positions of the padded
+        batch; None: the model's own durations, pitch and energy, by the launches issued without this argument."""
         d, H, M = self.dims, self.dims.hidden, self.dims.mel
         ids = ids.to(self.device, torch.int64).contiguous()
         stress = stress.to(self.device, torch.int64).contiguous() if stress is not None else None
         B, Pn = ids.shape
+        controls = None if prosody is None else pack_prosody(prosody_list(prosody, B, "rows"), [Pn] * B, Pn, self.device)
         with self._no_dropout():
             text_mask = self._buf("gen.text_mask", B, Pn, dtype=torch.uint8)
             enc = self._encode_text_fwd("", ids, stress, B, Pn, text_mask)
@@ -1851,11 +1875,15 @@ class KokoroEngine:
             col_e = self._buf("vp.col_enc", B * Pn, 3 * H, dtype=self.enc_dt)
             kk.call("kk_im2col3_fwd", enc, col_e, B, Pn, H, CHUNK, _b16(col_e))
             self._varpred_fwd("vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, text_mask, log_dur)
-            dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
-            expected = T = max(int(dur.sum(dim=1).max()), 3)       # (host sync: the expanded length sizes everything below)
+            if controls is None:
+                dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
+                sums = dur.sum(dim=1)
+            else:                                                  # (no row lengths: the reference's pads keep their durations)
+                dur, sums = self._controlled_durations(log_dur, controls, None, B, Pn)
+            expected = T = max(int(sums.max()), 3)                 # (host sync: the expanded length sizes everything below)
             if T > d.max_len:
                 raise ValueError(f"predicted length {T} exceeds the positional table ({d.max_len})")
-            memory, fm2 = self._expand_fwd("", enc, dur, B, Pn, T)
+            memory, fm2 = self._expand_fwd("", enc, dur, B, Pn, T, controls=controls)
             min_expected, _, max_expected = self._generation_bounds(expected, max_len, min_len_ratio, min_len_floor, max_len_ratio,
                                                                     max_len_cap)
             mel_out, stop_logit, t_dev = self._decode_state_init("gen", B, max_expected)
@@ -1901,13 +1929,15 @@ class KokoroEngine:
             raise ValueError(f"utterance of {max(lens_p)} phonemes exceeds the positional table ({self.dims.max_len})")
         return stress, lens_p
 
-    def _prefill_rows(self, ns, utterances, stress, lens_p, first=0, frame_limit=None):
+    def _prefill_rows(self, ns, utterances, stress, lens_p, first=0, frame_limit=None, prosody=None):
         """Everything of a ragged batch in front of the decode loop, on the workspace keys under `ns`: pad, encode, the duration
         predictor over each row's own phonemes, the expansion with each row's own frame count (_expand_fwd(flens=...)).  Error
         messages name utterance `first` + row; frame_limit: a row predicted longer raises before anything is expanded.
+        prosody: one Prosody or None per row, or None for no controls at all (then neither prosody kernel is launched).
         Returns (dur [B, Pn], T_b, T = max(T_b), memory, fm2)."""
         d, H = self.dims, self.dims.hidden
         B, Pn = len(utterances), max(lens_p)
+        controls = None if prosody is None else pack_prosody(prosody, lens_p, Pn, self.device)
         ids_h = torch.zeros(B, Pn, dtype=torch.int64)
         st_h = torch.zeros(B, Pn, dtype=torch.int64) if stress is not None else None
         for b, u in enumerate(utterances):
@@ -1926,8 +1956,12 @@ class KokoroEngine:
         dmask = self._buf(ns + "vp.dur_mask", B, Pn, dtype=torch.uint8)
         kk.call("kk_varpred_row_mask", text_mask, plens, dmask, B, Pn, CHUNK)
         self._varpred_fwd(ns + "vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, dmask, log_dur, lens=plens)
-        dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
-        sums = dur.sum(dim=1).cpu().tolist()                   # (host sync: the row lengths size everything below)
+        if controls is None:
+            dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
+            sums = dur.sum(dim=1).cpu().tolist()               # (host sync: the row lengths size everything below)
+        else:
+            dur, sums = self._controlled_durations(log_dur, controls, plens, B, Pn)
+            sums = sums.cpu().tolist()
         Tb = [max(int(s_), 3) for s_ in sums]
         for b, tb in enumerate(Tb):
             if tb > d.max_len:
@@ -1935,14 +1969,15 @@ class KokoroEngine:
             if frame_limit is not None and tb > frame_limit:
                 raise ValueError(f"utterance {first + b}: predicted length {tb} exceeds slot_frames ({frame_limit})")
         T = max(Tb)
-        memory, fm2 = self._expand_fwd(ns, enc, dur, B, Pn, T, flens=torch.tensor(Tb, dtype=torch.int32).to(self.device))
+        memory, fm2 = self._expand_fwd(ns, enc, dur, B, Pn, T, flens=torch.tensor(Tb, dtype=torch.int32).to(self.device),
+                                       controls=controls)
         return dur, Tb, T, memory, fm2
 
     @torch.no_grad()
     def generate_batch(self, utterances: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]] = None, *, max_len: int = 4000,
                        stop_threshold: float = 0.5, min_len_ratio: float = 0.7, min_len_floor: int = 12, max_len_ratio: float = 3.0,
                        max_len_cap: int = 1600, post_expected_stop_threshold: float = 0.2, check_every: int = 16,
-                       decode_graph: bool = True, want_info: bool = False):
+                       decode_graph: bool = True, want_info: bool = False, prosody=None):
         """Synthesise a batch of utterances of different lengths; row b of the result equals generate() on utterance b alone (the
         reference's B = 1 forward_inference), not generate() on the padded batch, whose stop rule and predictors see the whole batch.
 
@@ -1956,14 +1991,19 @@ class KokoroEngine:
         and so run the row kernels (_varpred_fwd(lens=...), _expand_fwd(flens=...)); the encoder (key mask), length regulator,
         bucket embeddings and cross-attention (frame mask) are row-independent already.  Each row has its own bounds
         (_generation_bounds) and its own stop rule, applied on the device by kk_decode_epilogue_rows inside the replayed step; the
-        host reads only the count of live rows, every `check_every` frames."""
+        host reads only the count of live rows, every `check_every` frames.
+
+        prosody: one prosody.Prosody for every utterance or one per utterance (None entries: neutral); None: no controls, the
+        launches issued without this argument.  The controls act in the prefill only (durations, then pitch / energy per frame), so a row still equals what it
+        gets alone under the same controls, and "durations" of want_info are the ones used."""
         d, H, M = self.dims, self.dims.hidden, self.dims.mel
         B = len(utterances)
         if B == 0:
             return ([], {"durations": [], "T": [], "bounds": []}) if want_info else []
         stress, lens_p = self._check_utterances(utterances, stress)
+        prosody = prosody_list(prosody, B)
         with self._no_dropout():
-            dur, Tb, T, memory, fm2 = self._prefill_rows("syn.", utterances, stress, lens_p)
+            dur, Tb, T, memory, fm2 = self._prefill_rows("syn.", utterances, stress, lens_p, prosody=prosody)
             bounds = []
             for b, expected in enumerate(Tb):
                 bounds.append(self._generation_bounds(expected, max_len, min_len_ratio, min_len_floor, max_len_ratio, max_len_cap,
@@ -2038,7 +2078,7 @@ class KokoroEngine:
                         slot_frames: Optional[int] = None, max_len: int = 4000, stop_threshold: float = 0.5, min_len_ratio: float = 0.7,
                         min_len_floor: int = 12, max_len_ratio: float = 3.0, max_len_cap: int = 1600,
                         post_expected_stop_threshold: float = 0.2, check_every: int = 16, decode_graph: bool = True,
-                        want_info: bool = False):
+                        want_info: bool = False, prosody=None):
         """generate_batch with continuous batching: the utterances are decoded in a pool of `slots` slots of `slot_frames` frames and
         a finished row's slot is refilled with the next utterance, so the decode steps are spent on live rows instead of lasting as
         long as the longest row of a fixed batch.  Arguments, results (in input order) and the want_info dict are generate_batch's.
@@ -2055,7 +2095,8 @@ class KokoroEngine:
         is captured again.  Workspaces only grow, so that dies out after the first few admissions of an engine's life.
         Harvest: every `check_every` frames the host reads done | frames in one copy, clones the finished slots' mels and admits
         into them; the steps of a block behind the last finished row run with every slot done.  Idle slots have done = 1 and
-        klen = 0."""
+        klen = 0.
+        prosody: as in generate_batch; an utterance's controls go with it into whichever admission group prefills it."""
         d, H, M = self.dims, self.dims.hidden, self.dims.mel
         N = len(utterances)
         if N == 0:
@@ -2069,6 +2110,13 @@ class KokoroEngine:
         if cap > 8192:
             raise ValueError(f"slot_frames {cap} exceeds the decode attention's 8192 keys")
         stress, lens_p = self._check_utterances(utterances, stress)
+        prosody = prosody_list(prosody, N)
+        for i, pr in enumerate(prosody or ()):                     # (before anything is decoded, not at the utterance's admission)
+            if pr is not None:
+                try:
+                    pr.validate(lens_p[i])
+                except ValueError as e:
+                    raise ValueError(f"utterance {i}: {e}") from None
         with self._no_dropout():
             ddt, L1, W = self.dec_dt, cap + 1, 2 * H * d.dec_layers
             st = self._stream_state(S, cap)
@@ -2092,7 +2140,8 @@ class KokoroEngine:
                 grp = list(range(nxt, nxt + n))
                 dur, Tb, T, memory, fm2 = self._prefill_rows("str.adm.", [utterances[i] for i in grp],
                                                              [stress[i] for i in grp] if stress is not None else None,
-                                                             [lens_p[i] for i in grp], first=nxt, frame_limit=cap)
+                                                             [lens_p[i] for i in grp], first=nxt, frame_limit=cap,
+                                                             prosody=[prosody[i] for i in grp] if prosody is not None else None)
                 rb = []
                 for r, i in enumerate(grp):
                     b3 = self._generation_bounds(Tb[r], max_len, min_len_ratio, min_len_floor, max_len_ratio, min(max_len_cap, cap),
