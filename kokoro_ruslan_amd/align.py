@@ -105,7 +105,7 @@ class PhoneAligner:
         """The packed features [D, T_total] (fp32, on the device) of log-mels [T, M]: utterance after utterance along time."""
         self._check(mels, [torch.zeros(1, dtype=torch.long)] * len(mels), None)
         x = torch.cat([m.to(self.device, torch.float32) for m in mels]).contiguous()
-        foff = torch.tensor([0] + [int(m.shape[0]) for m in mels], dtype=torch.int64).cumsum(0).to(torch.int32).to(self.device)
+        foff = kk.packed_offsets([int(m.shape[0]) for m in mels], torch.int32, self.device)
         return self._features_packed(x, foff, len(mels))
 
     def params(self, model: Dict):
@@ -151,13 +151,13 @@ class PhoneAligner:
         dev = self.device
         x = mels if feats is None else feats
         nt, np_ = [int(m.shape[0]) for m in x], [int(t.shape[0]) for t in ids]
-        cum = lambda v, dt: torch.tensor([0] + v, dtype=torch.int64).cumsum(0).to(dt)
-        coff_h = cum([code_words(p, t) for p, t in zip(np_, nt)], torch.int64)
+        coff_h = kk.packed_offsets([code_words(p, t) for p, t in zip(np_, nt)])
         tok_h = torch.cat([t.to("cpu", torch.int64) for t in ids])
         opt_h = torch.isin(tok_h, torch.tensor(sorted(set(int(o) for o in optional_ids)), dtype=torch.int64))
-        pk = {"B": len(ids), "frames": nt, "tokens": np_, "foff": cum(nt, torch.int32).to(dev), "poff": cum(np_, torch.int32).to(dev),
-              "coff": coff_h.to(dev), "coff_host": coff_h.tolist(), "foff_host": cum(nt, torch.int64).tolist(),
-              "poff_host": cum(np_, torch.int64).tolist(), "ids_host": tok_h, "ids": tok_h.to(torch.int32).to(dev),
+        pk = {"B": len(ids), "frames": nt, "tokens": np_,
+              "foff": kk.packed_offsets(nt, torch.int32, dev), "poff": kk.packed_offsets(np_, torch.int32, dev),
+              "coff": coff_h.to(dev), "coff_host": coff_h.tolist(), "foff_host": kk.packed_offsets(nt).tolist(),
+              "poff_host": kk.packed_offsets(np_).tolist(), "ids_host": tok_h, "ids": tok_h.to(torch.int32).to(dev),
               "opt": opt_h.to(torch.uint8).to(dev), "threads": (max(np_) + 63) // 64 * 64}
         packed = torch.cat([m.to(dev, torch.float32) for m in x]).contiguous()
         pk["feat"] = self._features_packed(packed, pk["foff"], pk["B"]) if feats is None else packed.t().contiguous()

@@ -61,7 +61,7 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         if os.path.exists(stamp):
             os.remove(stamp)
     headers = [os.path.join(CSRC, "kk_common.h"), os.path.join(os.path.dirname(HERE), "include", "kokoro_hip.h")]
-    headers += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h") and not f.startswith(("kk_common", "kk_attn", "kk_gemm16_", "kk_gemm16x_", "kk_stop_rule"))]      # included widely
+    headers += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h") and not f.startswith(("kk_common", "kk_attn", "kk_gemm16_", "kk_gemm16x_", "kk_stop_rule", "kk_fft"))]      # included widely
     attn_h, incs = ["kk_attn.h", "kk_attn_host.h"], [f for f in sorted(os.listdir(CSRC)) if f.endswith(".inc")]
     gemm_dev = ["kk_gemm16_dev.h"]      # device code shared by the two bf16 GEMM bodies
     extra_deps = {      # what single sources include besides the headers above
@@ -72,7 +72,9 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         "kk_attn_bwd.hip": attn_h + incs,      # the .inc files: bodies of the DMA-staged backward kernels
         "kk_synth.hip": ["kk_stop_rule.h"],      # the stop rule of a row, shared by the two decode epilogues
         "kk_stream.hip": ["kk_stop_rule.h"],
-        "kk_denoise.hip": ["kk_fft.h"],      # the wave64 FFT it shares with kk_griffinlim.hip and kk_features.hip
+        "kk_features.hip": ["kk_fft.h"],      # the 1024-point real STFT of one wave, shared by the three audio sources
+        "kk_griffinlim.hip": ["kk_fft.h"],
+        "kk_denoise.hip": ["kk_fft.h"],
         # bodies compiled into kk_chain.hip: the GEMM and attention forward bodies from their device headers, kk_dropout.hip under KK_BODIES_ONLY
         "kk_chain.hip": gemm_dev + ["kk_gemm16x_body.h", "kk_gemm16_body.h", "kk_dropout.hip", "kk_attn.h", "kk_attn_fwd3.h"],
     }

@@ -5,70 +5,23 @@
 //                 ONE utterance: output samples [256 f0, 256 (f0 + DTF)) clipped to the utterance.  Sample j sits at position j + 512 of
 //                 the padded signal, which frames j / 256 - 1 .. j / 256 + 2 cover, so the tile transforms frames f0 - 1 .. f0 + DTF + 1
 //                 clipped to the utterance's 1 + N / 256 frames: DTF + 3 at most, the three extra ones being the halo its neighbours
-//                 transform as well.  One wave per frame: load with the reflect index formed in integers, window, 1024-point real FFT
-//                 (fft512 + the split step), gain, inverse real FFT, window, into LDS.  Then every thread sums the frames that cover its
-//                 samples in ascending frame order, divides by the window-square envelope and stores.  Nothing leaves the workgroup
-//                 but its own samples: no atomics, and no sum whose order depends on the tile or on the rest of the batch.
+//                 transform as well.  One wave per frame: forward frame, split step, gain, inverse pre-step and tail into LDS (all but
+//                 the gain from kk_fft.h).  Then every thread sums the frames that cover its samples in ascending frame order, divides
+//                 by the window-square envelope (stft_ola) and stores.  Nothing leaves the workgroup but its own samples: no atomics,
+//                 and no sum whose order depends on the tile or on the rest of the batch.
 //  stft_mag_mean  mean over frames [f_lo, f_hi) of |stft| of one waveform (the vocoder's bias): one workgroup, wave w sums frames
 //                 f_lo + w, f_lo + w + 4, ... in registers, then the four partial sums are added in wave order.
 //
-// A lane computes bins k = lane + 64 j and 512 - k together (the split step has both operands at hand), so the gated spectrum never
-// goes through LDS: the lane forms the inverse transform's input Z'[k] from Y[k] and Y[512 - k] directly.
+// A lane computes bins k = lane + 64 j and 512 - k together (stft_split_pair: the split step has both operands at hand), so the gated
+// spectrum never goes through LDS: the lane forms the inverse transform's input Z'[k] from Y[k] and Y[512 - k] directly.
+// This file owns the tiles, the gate and the magnitude sum.
 #include "kk_common.h"
 #include "kk_fft.h"
 
 namespace {
 
-constexpr int DN = 1024, DHOP = 256, DBINS = 513;
 constexpr int DTF = 13, DHF = DTF + 3;                         // hops of one tile, frames it transforms at most (64 KiB of LDS)
 constexpr int DTHREADS = 256, DWAVES = DTHREADS / 64;
-
-struct DnTw { float2 tw1[8], tw2[8], twk[8]; };
-
-__device__ __forceinline__ void dn_twiddles(const float2 *tw, int lane, DnTw &t) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        t.tw1[j] = tw[(2 * lane * j) & (DN - 1)];
-        t.tw2[j] = tw[(16 * (lane & 7) * j) & (DN - 1)];
-        t.twk[j] = tw[lane + 64 * j];                          // w1024^k of bin k = lane + 64 j (the split step)
-    }
-}
-
-// Frame t of x[0, N) (N >= 1024, t <= N / 256), windowed, through the 512-point complex transform: Z in natural order in the wave's slot sl.
-__device__ __forceinline__ void dn_frame_fwd(const float *__restrict__ x, int N, int t, const float *__restrict__ win, float2 *sl,
-                                             const DnTw &tw, int lane) {
-    float2 v[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const int n = lane + 64 * m;
-        float s[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int j = DHOP * t - DN / 2 + 2 * n + h;
-            j = j < 0 ? -j : (j >= N ? (N - 1) - (j - (N - 1)) : j);      // one reflection is enough: -512 <= j <= N + 511, N >= 1024
-            s[h] = x[j];
-        }
-        const float2 w = *reinterpret_cast<const float2 *>(win + 2 * n);
-        v[m] = make_float2(s[0] * w.x, s[1] * w.y);
-    }
-    fft512<-1>(v, sl, tw.tw1, tw.tw2, lane);
-    const int qa = lane >> 3, qb = lane & 7;                       // output lane q holds index qa + 8 qb + 64 k2
-    __syncwarp();
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) sl[qa + 8 * qb + 64 * k2] = v[k2];
-    __syncwarp();
-}
-
-// The split step: X = bin k = lane + 64 j of the 1024-point real transform, Xm = bin 512 - k (k = 0: bins 0 and 512), from Z in sl.
-// X[k] = fe + w^k fo, X[512 - k] = conj(fe - w^k fo), fe = (Z[k] + conj Z[512-k]) / 2, fo = (Z[k] - conj Z[512-k]) / 2i.
-__device__ __forceinline__ void dn_split(const float2 *sl, float2 twk, int k, float2 &X, float2 &Xm) {
-    const float2 zk = sl[k], zm = sl[(DN / 2 - k) & (DN / 2 - 1)];
-    const float2 fe = make_float2((zk.x + zm.x) * 0.5f, (zk.y - zm.y) * 0.5f);
-    const float2 fo = make_float2((zk.y + zm.y) * 0.5f, (zm.x - zk.x) * 0.5f);
-    const float2 c = cmul(twk, fo);
-    X = make_float2(fe.x + c.x, fe.y + c.y);
-    Xm = make_float2(fe.x - c.x, c.y - fe.y);
-}
 
 __device__ __forceinline__ float2 dn_gate(float2 x, float sb) {   // x . max(1 - sb / |x|, 0), 0 at |x| = 0
     const float m = sqrtf(x.x * x.x + x.y * x.y);
@@ -80,92 +33,75 @@ __global__ __launch_bounds__(DTHREADS, 2) void denoise_kernel(const float *__res
                                                            const int2 *__restrict__ tiles, const float *__restrict__ bias, float strength,
                                                            const float2 *__restrict__ twt, const float *__restrict__ win,
                                                            float *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float frm[DHF][DN];    // FFT slot of a frame, then its windowed inverse transform
+    __shared__ __attribute__((aligned(16))) float frm[DHF][STFT_N]; // FFT slot of a frame, then its windowed inverse transform
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int2 tl = tiles[blockIdx.x];
     const int64_t base = woff[tl.x];
     const int64_t len = woff[tl.x + 1] - base;
     const int f0 = tl.y;
-    if (len < DN || len > 0x7fffffff - DN || f0 < 0 || (int64_t)DHOP * f0 >= len) return;      // (the host refuses these)
-    const int N = (int)len, F = 1 + N / DHOP;
+    if (len < STFT_N || len > 0x7fffffff - STFT_N || f0 < 0 || (int64_t)STFT_HOP * f0 >= len) return;      // (the host refuses these)
+    const int N = (int)len, F = 1 + N / STFT_HOP;
     const int f1 = min(f0 + DTF, F), h0 = max(f0 - 1, 0), h1 = min(f1 + 2, F);
     const float *x = wave + base;
 
-    DnTw tw;
-    dn_twiddles(twt, lane, tw);
-    const int qa = lane >> 3, qb = lane & 7;
+    StftTw tw;
+    stft_twiddles(twt, lane, tw);
 
     // 1. every frame that covers the tile's samples: forward, gain, inverse, window
 #pragma unroll 1
     for (int i = wv; i < h1 - h0; i += DWAVES) {
         float2 *sl = reinterpret_cast<float2 *>(frm[i]);
         float2 v[8];
-        dn_frame_fwd(x, N, h0 + i, win, sl, tw, lane);
+        stft_frame_fwd([&](int j) { return x[j]; }, h0 + i, N, win, sl, tw, lane);
 #pragma unroll
-        for (int m = 0; m < 8; ++m) {                              // Z'[k] = Y[k] + conj Y[512-k] + i w^-k (Y[k] - conj Y[512-k])
+        for (int m = 0; m < 8; ++m) {
             float2 X, Xm;
-            dn_split(sl, tw.twk[m], lane + 64 * m, X, Xm);
-            const float2 yk = dn_gate(X, strength * bias[lane + 64 * m]), ym = dn_gate(Xm, strength * bias[DN / 2 - lane - 64 * m]);
-            const float2 A = make_float2(yk.x + ym.x, yk.y - ym.y);
-            const float2 C = cmul(make_float2(yk.x - ym.x, yk.y + ym.y), make_float2(tw.twk[m].x, -tw.twk[m].y));
-            v[m] = make_float2(A.x - C.y, A.y + C.x);
+            stft_split_pair(sl, tw.twk[m], lane + 64 * m, X, Xm);
+            const float2 yk = dn_gate(X, strength * bias[lane + 64 * m]), ym = dn_gate(Xm, strength * bias[STFT_N / 2 - lane - 64 * m]);
+            v[m] = stft_inv_pre(yk, ym, tw.twk[m]);
         }
-        fft512<1>(v, sl, tw.tw1, tw.tw2, lane);
-        __syncwarp();
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) {
-            const int n = qa + 8 * qb + 64 * k2;
-            const float2 w = *reinterpret_cast<const float2 *>(win + 2 * n);
-            sl[n] = make_float2(v[k2].x * (1.f / DN) * w.x, v[k2].y * (1.f / DN) * w.y);
-        }
+        stft_inv_tail(v, sl, win, tw, lane);
     }
     __syncthreads();
 
     // 2. overlap-add in ascending frame order, envelope division, store: sample j is position p = j + 512 of the padded signal
-    const int j1 = min(DHOP * f1, N);
-    for (int j = DHOP * f0 + threadIdx.x; j < j1; j += DTHREADS) {
-        const int p = j + DN / 2;
-        const int tlo = max(p >= DN ? (p - DN) / DHOP + 1 : 0, h0), thi = min(p / DHOP, h1 - 1);
-        float acc = 0.f, env = 0.f;
-        for (int t = tlo; t <= thi; ++t) {
-            const int o = p - DHOP * t;
-            const float w = win[o];
-            acc += frm[t - h0][o];
-            env += w * w;
-        }
-        out[base + j] = acc / env;
+    const int j1 = min(STFT_HOP * f1, N);
+    for (int j = STFT_HOP * f0 + threadIdx.x; j < j1; j += DTHREADS) {
+        const int p = j + STFT_N / 2;
+        const int tlo = max(p >= STFT_N ? (p - STFT_N) / STFT_HOP + 1 : 0, h0), thi = min(p / STFT_HOP, h1 - 1);
+        out[base + j] = stft_ola(frm, h0, tlo, thi, p, win);
     }
 }
 
 __global__ __launch_bounds__(DTHREADS) void stft_mag_mean_kernel(const float *__restrict__ x, int N, int f_lo, int f_hi,
                                                                  const float2 *__restrict__ twt, const float *__restrict__ win,
                                                                  float *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float slot[DWAVES][DN];
-    __shared__ float part[DWAVES][DBINS];
+    __shared__ __attribute__((aligned(16))) float slot[DWAVES][STFT_N];
+    __shared__ float part[DWAVES][STFT_BINS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    DnTw tw;
-    dn_twiddles(twt, lane, tw);
+    StftTw tw;
+    stft_twiddles(twt, lane, tw);
     float acc[8], acc512 = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = 0.f;
 #pragma unroll 1
     for (int t = f_lo + wv; t < f_hi; t += DWAVES) {
         const float2 *sl = reinterpret_cast<const float2 *>(slot[wv]);
-        dn_frame_fwd(x, N, t, win, reinterpret_cast<float2 *>(slot[wv]), tw, lane);
+        stft_frame_fwd([&](int j) { return x[j]; }, t, N, win, reinterpret_cast<float2 *>(slot[wv]), tw, lane);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float2 X, Xm;
-            dn_split(sl, tw.twk[j], lane + 64 * j, X, Xm);
+            stft_split_pair(sl, tw.twk[j], lane + 64 * j, X, Xm);
             acc[j] += sqrtf(X.x * X.x + X.y * X.y);
             if (j == 0) acc512 += sqrtf(Xm.x * Xm.x + Xm.y * Xm.y);      // lane 0: bin 512
         }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) part[wv][lane + 64 * j] = acc[j];
-    if (lane == 0) part[wv][DN / 2] = acc512;
+    if (lane == 0) part[wv][STFT_N / 2] = acc512;
     __syncthreads();
     const float inv = 1.f / (float)(f_hi - f_lo);
-    for (int k = threadIdx.x; k < DBINS; k += DTHREADS) out[k] = (((part[0][k] + part[1][k]) + part[2][k]) + part[3][k]) * inv;
+    for (int k = threadIdx.x; k < STFT_BINS; k += DTHREADS) out[k] = (((part[0][k] + part[1][k]) + part[2][k]) + part[3][k]) * inv;
 }
 
 }  // namespace
@@ -186,9 +122,9 @@ extern "C" int kk_denoise(const float *wave, const int64_t *woff, const int *til
 extern "C" int kk_stft_mag_mean(const float *wave, int64_t n, int f_lo, int f_hi, const void *tw, const float *win, float *out,
                                 void *stream) {
     KK_REQUIRE(wave && tw && win && out, "kk_stft_mag_mean: bad args");
-    KK_REQUIRE(n >= DN && n <= 0x7fffffff - DN, "kk_stft_mag_mean: %lld samples, need 1024 .. 2^31 - 1025", (long long)n);
-    KK_REQUIRE(0 <= f_lo && f_lo < f_hi && f_hi <= 1 + n / DHOP, "kk_stft_mag_mean: frames [%d, %d) of %lld", f_lo, f_hi,
-               (long long)(1 + n / DHOP));
+    KK_REQUIRE(n >= STFT_N && n <= 0x7fffffff - STFT_N, "kk_stft_mag_mean: %lld samples, need 1024 .. 2^31 - 1025", (long long)n);
+    KK_REQUIRE(0 <= f_lo && f_lo < f_hi && f_hi <= 1 + n / STFT_HOP, "kk_stft_mag_mean: frames [%d, %d) of %lld", f_lo, f_hi,
+               (long long)(1 + n / STFT_HOP));
     kk_note_kernel("stft_mag_mean");
     hipLaunchKernelGGL(stft_mag_mean_kernel, dim3(1), dim3(DTHREADS), 0, (hipStream_t)stream, wave, (int)n, f_lo, f_hi,
                        (const float2 *)tw, win, out);

@@ -12,12 +12,15 @@
 // Layout: the waveforms of a batch are packed back to back (woff: sample offsets, B + 1), and so are the outputs: mel frames by moff
 // (the frames kept after the cut to max_seq_length), pitch frames by poff (all of them: the pitch statistics run over every frame).
 // Every sum runs in an order fixed by the frame's position in its own utterance, so an utterance's output does not depend on the batch.
+//
+// This file owns the sample load (x / (peak + 1e-9), zero past the samples given), the mel tile and the power / filterbank step per
+// bin, and all of pitch and finish.  The frame transform, the split step and the reflect rule are kk_fft.h's.
 #include "kk_common.h"
 #include "kk_fft.h"
 
 namespace {
 
-constexpr int FN = 1024, FHOP = 256, FBINS = 513, FMELS = 80;
+constexpr int FMELS = 80;
 constexpr int FTHREADS = 256, FWAVES = FTHREADS / 64;
 constexpr int MTF = 16;                                       // mel frames per workgroup (64-byte runs of a [80, T] row)
 constexpr int PW = 2048, PLAGS = 448, PLMIN = 27, PLMAX = 441;  // pitch window; lags computed (8 per lane group); the search range
@@ -40,8 +43,6 @@ __device__ __forceinline__ Utt load_utt(const int64_t *woff, const float *peak, 
     u.d = peak[b] + 1e-9f;
     return u;
 }
-
-__device__ __forceinline__ int reflect(int j, int n) { return j < 0 ? -j : (j >= n ? 2 * (n - 1) - j : j); }
 
 __global__ __launch_bounds__(FTHREADS) void feat_peak_kernel(const float *__restrict__ wave, const int64_t *__restrict__ woff,
                                                              unsigned *__restrict__ peak_bits) {
@@ -73,59 +74,27 @@ struct MelArgs {
 };
 
 __global__ __launch_bounds__(FTHREADS) void feat_mel_kernel(const MelArgs a) {
-    __shared__ __attribute__((aligned(16))) float2 slot[FWAVES][FN / 2];
-    __shared__ float pw[FWAVES][FBINS + 7];
+    __shared__ __attribute__((aligned(16))) float2 slot[FWAVES][STFT_N / 2];
+    __shared__ float pw[FWAVES][STFT_BINS + 7];
     __shared__ float st[2][FMELS][MTF + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int2 tl = a.tiles[blockIdx.x];
     const int b = tl.x, f0 = tl.y;
-    const Utt u = load_utt(a.woff, a.peak, b, FN);
+    const Utt u = load_utt(a.woff, a.peak, b, STFT_N);
     const int m0 = a.moff[b], T = a.moff[b + 1] - m0, f1 = min(f0 + MTF, T);
 
-    float2 tw1[8], tw2[8], twk[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        tw1[j] = a.tw[(2 * lane * j) & (FN - 1)];
-        tw2[j] = a.tw[(16 * (lane & 7) * j) & (FN - 1)];
-        twk[j] = a.tw[lane + 64 * j];
-    }
-    const int qa = lane >> 3, qb = lane & 7;
+    StftTw tw;
+    stft_twiddles(a.tw, lane, tw);
     float2 *sl = slot[wave];
     float *p = pw[wave];
 
     for (int t = f0 + wave; t < f1; t += FWAVES) {
-        float2 v[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int n = lane + 64 * m;
-            float s[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = reflect(FHOP * t - FN / 2 + 2 * n + h, u.n);
-                s[h] = j < u.n_raw ? a.wave[u.w0 + j] / u.d : 0.f;
-            }
-            const float2 w = *reinterpret_cast<const float2 *>(a.win + 2 * n);
-            v[m] = make_float2(s[0] * w.x, s[1] * w.y);
-        }
-        fft512<-1>(v, sl, tw1, tw2, lane);
-        __syncwarp();
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) sl[qa + 8 * qb + 64 * k2] = v[k2];
-        __syncwarp();
+        stft_frame_fwd([&](int j) { return j < u.n_raw ? a.wave[u.w0 + j] / u.d : 0.f; }, t, u.n, a.win, sl, tw, lane);
 #pragma unroll
         for (int j = 0; j <= 8; ++j) {
             if (j == 8 && lane != 0) break;
-            const int k = j < 8 ? lane + 64 * j : FN / 2;
-            const float2 zk = sl[k & (FN / 2 - 1)], zm = sl[(FN / 2 - k) & (FN / 2 - 1)];
-            float2 X;
-            if (j < 8) {                                            // X[k] = (Z[k] + conj Z[512-k]) / 2 + w^k (Z[k] - conj Z[512-k]) / 2i
-                const float2 fe = make_float2((zk.x + zm.x) * 0.5f, (zk.y - zm.y) * 0.5f);
-                const float2 fo = make_float2((zk.y + zm.y) * 0.5f, (zm.x - zk.x) * 0.5f);
-                const float2 c = cmul(twk[j], fo);
-                X = make_float2(fe.x + c.x, fe.y + c.y);
-            } else {
-                X = make_float2(zk.x - zk.y, 0.f);
-            }
+            const int k = j < 8 ? lane + 64 * j : STFT_N / 2;
+            const float2 X = j < 8 ? stft_split(sl, tw.twk[j], k) : stft_bin512(sl);
             p[k] = X.x * X.x + X.y * X.y;
         }
         __syncwarp();
@@ -182,7 +151,7 @@ __global__ __launch_bounds__(FTHREADS) void feat_pitch_kernel(const PitchArgs a)
     for (int i = threadIdx.x; i < PXS; i += FTHREADS) {
         float s = 0.f;
         if (i < PW) {
-            const int j = reflect(FHOP * t - PW / 2 + i, u.n);
+            const int j = reflect(STFT_HOP * t - PW / 2 + i, u.n);
             const float x1 = j < u.n_raw ? a.wave[u.w0 + j] / u.d : 0.f;
             const float x0 = j > 0 && j - 1 < u.n_raw ? a.wave[u.w0 + j - 1] / u.d : 0.f;
             s = (j > 0 ? x1 - 0.97f * x0 : x1) * a.win[i];

@@ -1,6 +1,16 @@
-// The wave64 FFT the Griffin-Lim (kk_griffinlim.hip) and feature-extraction (kk_features.hip) kernels share: a 512-point complex
-// transform per wave, 8 points per lane, three radix-8 passes in registers with two LDS exchanges (XOR-swizzled so each b64 access is
-// conflict-free within its lane group).  A 1024-point real transform is this plus the split step at the call site.
+// The 1024-point real STFT of one wave64, the single copy that feature extraction (kk_features.hip), Griffin-Lim (kk_griffinlim.hip) and
+// spectral denoising (kk_denoise.hip) share: n_fft = win = 1024, hop 256, 513 bins, center = True with reflect padding by index.
+//
+//  fft512       a 512-point complex transform per wave, 8 points per lane, three radix-8 passes in registers with two LDS exchanges
+//               (XOR-swizzled so each b64 access is conflict-free within its lane group)
+//  forward      stft_frame_fwd (reflected index, the caller's sample load, window, fft512<-1>, Z in natural order in the wave's slot), then
+//               the split step per bin: stft_split_pair (bins k and 512 - k from one pair of loads; bin 512 from the k = 0 pair) or
+//               stft_split (bin k alone) with stft_bin512.  The two forms may differ in the last bit or the sign of a zero on bin 512:
+//               a kernel keeps the one it has.
+//  inverse      stft_inv_pre (Z'[k] from Y[k] and Y[512 - k]), stft_inv_tail (fft512<1>, 1 / 1024, window, into the frame's LDS row),
+//               stft_ola (one padded position: the frames that cover it summed in ascending order, over the window-square envelope)
+//
+// Where a sample comes from, which frames a tile owns and what is done to a bin stay with each kernel.  Everything here inlines.
 #pragma once
 #include "kk_common.h"
 
@@ -61,6 +71,106 @@ template <int SIGN> __device__ __forceinline__ void fft512(float2 *v, float2 *sl
 #pragma unroll
     for (int l0 = 0; l0 < 8; ++l0) v[l0] = sl[a * 64 + 8 * (b ^ a) + (l0 ^ b)];     // lane (k0 = a, k1 = b)
     dft8<SIGN>(v);
+}
+
+constexpr int STFT_N = 1024, STFT_HOP = 256, STFT_BINS = STFT_N / 2 + 1;
+
+struct StftTw { float2 tw1[8], tw2[8], twk[8]; };             // of one lane, from the table tw[j] = exp(-2 pi i j / 1024)
+
+__device__ __forceinline__ void stft_twiddles(const float2 *tw, int lane, StftTw &t) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        t.tw1[j] = tw[(2 * lane * j) & (STFT_N - 1)];
+        t.tw2[j] = tw[(16 * (lane & 7) * j) & (STFT_N - 1)];
+        t.twk[j] = tw[lane + 64 * j];                          // w1024^k of bin k = lane + 64 j (the split step)
+    }
+}
+
+// Index j of a signal of n samples under reflect padding.  One reflection: -n < j < 2 n - 1.  No overflow for n < 2^31.
+__device__ __forceinline__ int reflect(int j, int n) { return j < 0 ? -j : (j >= n ? (n - 1) - (j - (n - 1)) : j); }
+
+// fft512's output lane holds, in v[k2], the element of this natural-order index.
+__device__ __forceinline__ int stft_nat(int lane, int k2) { return (lane >> 3) + 8 * (lane & 7) + 64 * k2; }
+
+// Frame t of a signal of n samples (n > 512, t <= n / 256), windowed, through the 512-point complex transform: Z in natural order in the
+// wave's slot sl.  load(j): sample j, 0 <= j < n.
+template <class Load> __device__ __forceinline__ void stft_frame_fwd(Load load, int t, int n, const float *__restrict__ win, float2 *sl,
+                                                                     const StftTw &tw, int lane) {
+    float2 v[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const int i = lane + 64 * m;
+        float s[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) s[h] = load(reflect(STFT_HOP * t - STFT_N / 2 + 2 * i + h, n));
+        const float2 w = *reinterpret_cast<const float2 *>(win + 2 * i);
+        v[m] = make_float2(s[0] * w.x, s[1] * w.y);
+    }
+    fft512<-1>(v, sl, tw.tw1, tw.tw2, lane);
+    __syncwarp();
+#pragma unroll
+    for (int k2 = 0; k2 < 8; ++k2) sl[stft_nat(lane, k2)] = v[k2];
+    __syncwarp();
+}
+
+// The split step for bin k < 512 from Z in sl: X[k] = fe + c, X[512 - k] = conj(fe - c), with c = w^k fo,
+// fe = (Z[k] + conj Z[512-k]) / 2, fo = (Z[k] - conj Z[512-k]) / 2i.
+__device__ __forceinline__ void stft_split_parts(const float2 *sl, float2 twk, int k, float2 &fe, float2 &c) {
+    const float2 zk = sl[k], zm = sl[(STFT_N / 2 - k) & (STFT_N / 2 - 1)];
+    fe = make_float2((zk.x + zm.x) * 0.5f, (zk.y - zm.y) * 0.5f);
+    const float2 fo = make_float2((zk.y + zm.y) * 0.5f, (zm.x - zk.x) * 0.5f);
+    c = cmul(twk, fo);
+}
+
+// X = bin k, Xm = bin 512 - k (k = 0: bins 0 and 512).
+__device__ __forceinline__ void stft_split_pair(const float2 *sl, float2 twk, int k, float2 &X, float2 &Xm) {
+    float2 fe, c;
+    stft_split_parts(sl, twk, k, fe, c);
+    X = make_float2(fe.x + c.x, fe.y + c.y);
+    Xm = make_float2(fe.x - c.x, c.y - fe.y);
+}
+
+// Bin k alone; bin 512 is then stft_bin512 on lane 0: even sum minus odd sum.
+__device__ __forceinline__ float2 stft_split(const float2 *sl, float2 twk, int k) {
+    float2 fe, c;
+    stft_split_parts(sl, twk, k, fe, c);
+    return make_float2(fe.x + c.x, fe.y + c.y);
+}
+__device__ __forceinline__ float2 stft_bin512(const float2 *sl) {
+    const float2 z0 = sl[0];
+    return make_float2(z0.x - z0.y, 0.f);
+}
+
+// The inverse transform's input: Z'[k] = Y[k] + conj Y[512-k] + i w^-k (Y[k] - conj Y[512-k]), yk = Y[k], ym = Y[512 - k].
+__device__ __forceinline__ float2 stft_inv_pre(float2 yk, float2 ym, float2 twk) {
+    const float2 A = make_float2(yk.x + ym.x, yk.y - ym.y);
+    const float2 C = cmul(make_float2(yk.x - ym.x, yk.y + ym.y), make_float2(twk.x, -twk.y));
+    return make_float2(A.x - C.y, A.y + C.x);
+}
+
+// v = Z' of one frame (lane's v[m]: k = lane + 64 m) to its 1024 samples, scaled by 1 / 1024 and windowed, in the LDS row sl.
+__device__ __forceinline__ void stft_inv_tail(float2 (&v)[8], float2 *sl, const float *__restrict__ win, const StftTw &tw, int lane) {
+    fft512<1>(v, sl, tw.tw1, tw.tw2, lane);
+    __syncwarp();
+#pragma unroll
+    for (int k2 = 0; k2 < 8; ++k2) {
+        const int i = stft_nat(lane, k2);
+        const float2 w = *reinterpret_cast<const float2 *>(win + 2 * i);
+        sl[i] = make_float2(v[k2].x * (1.f / STFT_N) * w.x, v[k2].y * (1.f / STFT_N) * w.y);
+    }
+}
+
+// Overlap-add at position p of the padded signal: frames tlo .. thi (rows tlo - h0 .. of frm, stft_inv_tail's output) in ascending
+// order, over the window-square envelope of the same frames.
+__device__ __forceinline__ float stft_ola(const float (*frm)[STFT_N], int h0, int tlo, int thi, int p, const float *__restrict__ win) {
+    float acc = 0.f, env = 0.f;
+    for (int t = tlo; t <= thi; ++t) {
+        const int o = p - STFT_HOP * t;
+        const float w = win[o];
+        acc += frm[t - h0][o];
+        env += w * w;
+    }
+    return acc / env;
 }
 
 }  // namespace

@@ -12,9 +12,10 @@
 // utterance (4 on the left for a one-frame last tile), which is every frame that overlaps the samples the tile's forward frames
 // read, reflect padding included.
 //
-// FFT: a 1024-point real transform is a 512-point complex one plus the split step.  One wave64 per frame, 8 points per lane, three
-// radix-8 passes in registers with two LDS exchanges (XOR-swizzled so each b64 access is conflict-free within its lane group).
-// Twiddles and the window come from host tables computed in fp64.
+// This file owns the tile and halo bookkeeping, the xs array the forward frames read, and the per-bin work: the k = 0 clearing of the
+// imaginary parts on the way in, momentum and normalisation on the way out.  The transforms themselves (forward frame, split step with
+// bin 512 on lane 0, inverse pre-step and tail, overlap-add of one position) are kk_fft.h's, one wave64 per frame.  Twiddles and the
+// window come from host tables computed in fp64.
 //
 // Determinism: every sum runs in an order fixed by the frame's (or sample's) position in its own utterance: the overlap-add of a
 // sample sums its frames in ascending order whichever tile computes it.  So a waveform's bits do not depend on the rest of the batch.
@@ -23,9 +24,9 @@
 
 namespace {
 
-constexpr int GN = 1024, GHOP = 256, GBINS = 513, GMELS = 80;
+constexpr int GMELS = 80;
 constexpr int GTF = 8, GHALO = 3, GHF = GTF + 2 * GHALO;     // tile frames, halo frames per side, inverse FFTs per tile (at most)
-constexpr int GXS = GHF * GHOP + GN - GHOP;                  // samples the halo frames cover
+constexpr int GXS = GHF * STFT_HOP + STFT_N - STFT_HOP;      // samples the halo frames cover
 constexpr int GTHREADS = 256, GWAVES = GTHREADS / 64;
 constexpr int GINIT_F = 8;                                   // frames per init workgroup
 
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(GTHREADS) void gl_init_kernel(const float *__restri
         e[f][m] = r0 + f < frames ? expf(mel[(r0 + f) * GMELS + m]) : 0.f;
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < GBINS; k += GTHREADS) {
+    for (int k = threadIdx.x; k < STFT_BINS; k += GTHREADS) {
         float acc[GINIT_F];
 #pragma unroll
         for (int f = 0; f < GINIT_F; ++f) acc[f] = 0.f;
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(GTHREADS) void gl_init_kernel(const float *__restri
         for (int f = 0; f < GINIT_F; ++f) {
             const int64_t row = r0 + f;
             if (row >= frames) break;
-            const int64_t i = row * GBINS + k;
+            const int64_t i = row * STFT_BINS + k;
             const float s = sqrtf(fmaxf(acc[f], 0.f));
             const float2 a = ang ? ang[i] : make_float2(1.f, 0.f);
             S[i] = s;
@@ -77,70 +78,47 @@ __global__ __launch_bounds__(GTHREADS) void gl_init_kernel(const float *__restri
 }
 
 __global__ __launch_bounds__(GTHREADS) void gl_iter_kernel(const GlIter a) {
-    __shared__ __attribute__((aligned(16))) float frm[GHF][GN];     // windowed inverse FFTs of the halo frames; then FFT slots
+    __shared__ __attribute__((aligned(16))) float frm[GHF][STFT_N]; // windowed inverse FFTs of the halo frames; then FFT slots
     __shared__ float xs[GXS];                                       // istft samples the tile reads, by overlap-add position
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int4 tl = a.tiles[blockIdx.x];
     const int start = tl.x, T = tl.y, f0 = tl.z;
     // the reflection at the end reads sample 256 (T - 1) - 1, which frames T - 5 .. T - 2 cover: a one-frame last tile reaches 4 back
     const int f1 = min(f0 + GTF, T), h0 = max(min(f0 - GHALO, T - 5), 0), h1 = min(f1 + GHALO, T);
-    const int pbase = h0 * GHOP, L = GHOP * (T - 1);
+    const int pbase = h0 * STFT_HOP, L = STFT_HOP * (T - 1);
 
-    float2 tw1[8], tw2[8], twk[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        tw1[j] = a.tw[(2 * lane * j) & (GN - 1)];
-        tw2[j] = a.tw[(16 * (lane & 7) * j) & (GN - 1)];
-        twk[j] = a.tw[lane + 64 * j];                              // w1024^k of bin k = lane + 64 j (the split step)
-    }
-    const int qa = lane >> 3, qb = lane & 7;                       // output lane q holds index qa + 8 qb + 64 k2
+    StftTw tw;
+    stft_twiddles(a.tw, lane, tw);
 
     // 1. inverse real FFTs of the halo frames, windowed, into frm
     for (int i = wave; i < h1 - h0; i += GWAVES) {
-        const float2 *yr = a.yin + (int64_t)(start + h0 + i) * GBINS;
+        const float2 *yr = a.yin + (int64_t)(start + h0 + i) * STFT_BINS;
         float2 v[8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) {                              // Z[k] = X[k] + conj X[512-k] + i w^-k (X[k] - conj X[512-k])
+        for (int m = 0; m < 8; ++m) {
             const int k = lane + 64 * m;
-            float2 xk = yr[k], xm = yr[GN / 2 - k];
+            float2 xk = yr[k], xm = yr[STFT_N / 2 - k];
             if (k == 0) { xk.y = 0.f; xm.y = 0.f; }               // c2r ignores the imaginary parts of bins 0 and 512
-            const float2 A = make_float2(xk.x + xm.x, xk.y - xm.y);
-            const float2 C = cmul(make_float2(xk.x - xm.x, xk.y + xm.y), make_float2(twk[m].x, -twk[m].y));
-            v[m] = make_float2(A.x - C.y, A.y + C.x);
+            v[m] = stft_inv_pre(xk, xm, tw.twk[m]);
         }
-        float2 *sl = reinterpret_cast<float2 *>(frm[i]);
-        fft512<1>(v, sl, tw1, tw2, lane);
-        __syncwarp();
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) {
-            const int n = qa + 8 * qb + 64 * k2;
-            const float2 w = *reinterpret_cast<const float2 *>(a.win + 2 * n);
-            sl[n] = make_float2(v[k2].x * (1.f / GN) * w.x, v[k2].y * (1.f / GN) * w.y);
-        }
+        stft_inv_tail(v, reinterpret_cast<float2 *>(frm[i]), a.win, tw, lane);
     }
     __syncthreads();
 
     // 2. overlap-add / window-square envelope at every position the halo frames cover, inside the trimmed signal [512, 256 T + 256)
-    const int nxs = (h1 - h0) * GHOP + GN - GHOP;
+    const int nxs = (h1 - h0) * STFT_HOP + STFT_N - STFT_HOP;
     for (int idx = threadIdx.x; idx < nxs; idx += GTHREADS) {
         const int p = pbase + idx;
-        if (p < GN / 2 || p >= GHOP * T + GHOP) continue;
-        const int tlo = max(p >= GN ? (p - GN) / GHOP + 1 : 0, h0), thi = min(min(T - 1, p / GHOP), h1 - 1);
+        if (p < STFT_N / 2 || p >= STFT_HOP * T + STFT_HOP) continue;
+        const int tlo = max(p >= STFT_N ? (p - STFT_N) / STFT_HOP + 1 : 0, h0), thi = min(min(T - 1, p / STFT_HOP), h1 - 1);
         if (tlo > thi) continue;                                    // no halo frame here: never read
-        float acc = 0.f, env = 0.f;
-        for (int t = tlo; t <= thi; ++t) {
-            const int o = p - GHOP * t;
-            const float w = a.win[o];
-            acc += frm[t - h0][o];
-            env += w * w;
-        }
-        xs[idx] = acc / env;
+        xs[idx] = stft_ola(frm, h0, tlo, thi, p, a.win);
     }
     __syncthreads();
 
     if (a.final_istft) {                                            // 3'. the tile's own samples [256 f0, 256 f1) of the waveform
-        const int j1 = min(GHOP * f1, L);
-        for (int j = GHOP * f0 + threadIdx.x; j < j1; j += GTHREADS) a.wave[tl.w + j] = xs[j + GN / 2 - pbase];
+        const int j1 = min(STFT_HOP * f1, L);
+        for (int j = STFT_HOP * f0 + threadIdx.x; j < j1; j += GTHREADS) a.wave[tl.w + j] = xs[j + STFT_N / 2 - pbase];
         return;
     }
 
@@ -148,40 +126,13 @@ __global__ __launch_bounds__(GTHREADS) void gl_iter_kernel(const GlIter a) {
     float2 *sl = reinterpret_cast<float2 *>(frm[wave]);            // frm is free now: one exchange slot per wave
     for (int i = wave; i < f1 - f0; i += GWAVES) {
         const int t = f0 + i;
-        float2 v[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int n = lane + 64 * m;
-            float s[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                int j = GHOP * t - GN / 2 + 2 * n + h;
-                j = j < 0 ? -j : (j >= L ? 2 * (L - 1) - j : j);
-                s[h] = xs[j + GN / 2 - pbase];
-            }
-            const float2 w = *reinterpret_cast<const float2 *>(a.win + 2 * n);
-            v[m] = make_float2(s[0] * w.x, s[1] * w.y);
-        }
-        fft512<-1>(v, sl, tw1, tw2, lane);
-        __syncwarp();
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) sl[qa + 8 * qb + 64 * k2] = v[k2];
-        __syncwarp();
-        const int64_t row = (int64_t)(start + t) * GBINS;
+        stft_frame_fwd([&](int j) { return xs[j + STFT_N / 2 - pbase]; }, t, L, a.win, sl, tw, lane);
+        const int64_t row = (int64_t)(start + t) * STFT_BINS;
 #pragma unroll
         for (int j = 0; j <= 8; ++j) {
             if (j == 8 && lane != 0) break;
-            const int k = j < 8 ? lane + 64 * j : GN / 2;
-            const float2 zk = sl[k & (GN / 2 - 1)], zm = sl[(GN / 2 - k) & (GN / 2 - 1)];
-            float2 X;
-            if (j < 8) {                                            // X[k] = (Z[k] + conj Z[512-k]) / 2 + w^k (Z[k] - conj Z[512-k]) / 2i
-                const float2 fe = make_float2((zk.x + zm.x) * 0.5f, (zk.y - zm.y) * 0.5f);
-                const float2 fo = make_float2((zk.y + zm.y) * 0.5f, (zm.x - zk.x) * 0.5f);
-                const float2 c = cmul(twk[j], fo);
-                X = make_float2(fe.x + c.x, fe.y + c.y);
-            } else {
-                X = make_float2(zk.x - zk.y, 0.f);                  // bin 512: even sum minus odd sum
-            }
+            const int k = j < 8 ? lane + 64 * j : STFT_N / 2;
+            const float2 X = j < 8 ? stft_split(sl, tw.twk[j], k) : stft_bin512(sl);
             float2 c = X;
             if (a.beta != 0.f) {
                 const float2 p = a.reb[row + k];

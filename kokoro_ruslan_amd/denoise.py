@@ -15,7 +15,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from kokoro_ruslan_amd import lib as kk
-from kokoro_ruslan_amd.griffinlim import HOP, N_BINS, N_FFT, N_MELS, hann_window, twiddles
+from kokoro_ruslan_amd.stft import HOP, N_BINS, N_FFT, N_MELS, device_tables
 
 MIN_SAMPLES = N_FFT                     # the reflect padding and the five frames of the shortest bias: a 4-frame HiFi-GAN mel
 DEFAULT_STRENGTH = 0.005
@@ -33,8 +33,7 @@ class SpectralDenoiser:
 
     def __init__(self, device: str = "cuda"):
         self.device = torch.device(device)
-        self.window = hann_window(torch.float64).to(torch.float32).to(self.device)
-        self.tw = torch.view_as_real(twiddles()).contiguous().to(self.device)
+        self.window, self.tw = device_tables(self.device)
         self.tile_frames = int(kk.load().kk_denoise_tile_frames())
         self.bias: Optional[torch.Tensor] = None
 
@@ -80,7 +79,7 @@ class SpectralDenoiser:
             return []
         n = [int(w.numel()) for w in waves]
         x = torch.cat([w.to(self.device, torch.float32) for w in waves]).contiguous()
-        woff = torch.tensor([0] + n, dtype=torch.int64).cumsum(0).to(self.device)
+        woff = kk.packed_offsets(n, torch.int64, self.device)
         tiles = self.tiles(n).to(self.device)
         y = torch.empty_like(x)
         kk.call("kk_denoise", x, woff, tiles, tiles.shape[0], self.bias, s, self.tw, self.window, y)

@@ -109,9 +109,9 @@ class MelAligner:
         xa = torch.cat([s.to(dev, torch.float32) for s in syn]).contiguous()
         xb = torch.cat([r.to(dev, torch.float32) for r in ref]).contiguous()
         M = xa.shape[1]
-        cum = lambda v, dt: torch.tensor([0] + v, dtype=torch.int64).cumsum(0).to(dt)
-        doff_h, poff_h = cum([dir_words(a, b) for a, b in zip(na, nb)], torch.int64), cum([a + b - 1 for a, b in zip(na, nb)], torch.int64)
-        aoff, boff = cum(na, torch.int32).to(dev), cum(nb, torch.int32).to(dev)
+        doff_h = kk.packed_offsets([dir_words(a, b) for a, b in zip(na, nb)])
+        poff_h = kk.packed_offsets([a + b - 1 for a, b in zip(na, nb)])
+        aoff, boff = kk.packed_offsets(na, torch.int32, dev), kk.packed_offsets(nb, torch.int32, dev)
         doff, poff = doff_h.to(dev), poff_h.to(dev)
         ca, cb = self.mcep(xa), self.mcep(xb)
         total = torch.zeros(B, dtype=torch.float32, device=dev)

@@ -15,7 +15,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from kokoro_ruslan_amd import lib as kk
-from kokoro_ruslan_amd.griffinlim import HOP, N_FFT, N_MELS, SAMPLE_RATE, hann_window, melscale_fbanks, twiddles
+from kokoro_ruslan_amd.griffinlim import melscale_fbanks
+from kokoro_ruslan_amd.stft import HOP, N_FFT, N_MELS, SAMPLE_RATE, device_tables
 
 PITCH_WIN = 2048
 DEFAULT_MAX_SAMPLES = 1 << 26           # packed samples per group (256 MB of fp32 waveform; a longer waveform runs alone)
@@ -53,9 +54,8 @@ class FeatureExtractor:
         fb = melscale_fbanks(torch.float64)
         self.fb = fb.to(torch.float32).contiguous().to(self.device)
         self.span = mel_spans(fb).to(self.device)
-        self.window = hann_window(torch.float64).to(torch.float32).to(self.device)
+        self.window, self.tw = device_tables(self.device)
         self.pitch_window = torch.hann_window(PITCH_WIN, periodic=True, dtype=torch.float64).to(torch.float32).to(self.device)
-        self.tw = torch.view_as_real(twiddles()).contiguous().to(self.device)
         self.tile_frames = int(kk.load().kk_feat_mel_tile_frames())
         self._resampler = None
 
@@ -129,9 +129,8 @@ class FeatureExtractor:
         B = len(n)
         T = [min(1 + max(v, N_FFT) // HOP, max_T) for v in n]
         Tp = [1 + max(v, PITCH_WIN) // HOP for v in n]
-        cum = lambda v: torch.tensor([0] + v).cumsum(0)
-        woff = cum(n).to(torch.int64).to(dev)
-        moff, poff = cum(T).to(torch.int32).to(dev), cum(Tp).to(torch.int32).to(dev)
+        woff = kk.packed_offsets(n, torch.int64, dev)
+        moff, poff = kk.packed_offsets(T, torch.int32, dev), kk.packed_offsets(Tp, torch.int32, dev)
         tiles = torch.tensor([[b, f0] for b, t in enumerate(T) for f0 in range(0, t, self.tile_frames)], dtype=torch.int32).to(dev)
         nm, npf = sum(T), sum(Tp)
         peak = torch.empty(B, dtype=torch.float32, device=dev)

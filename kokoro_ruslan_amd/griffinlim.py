@@ -15,9 +15,10 @@ from typing import List, Optional, Sequence
 import torch
 
 from kokoro_ruslan_amd import lib as kk
+from kokoro_ruslan_amd.stft import HOP, N_BINS, N_FFT, N_MELS, SAMPLE_RATE, device_tables
+from kokoro_ruslan_amd.stft import hann_window, twiddles  # noqa: F401  (re-exported: tests and tools import them from here)
 
-SAMPLE_RATE, N_FFT, HOP, N_MELS, F_MAX = 22050, 1024, 256, 80, 8000.0
-N_BINS = N_FFT // 2 + 1
+F_MAX = 8000.0
 MIN_FRAMES = 4                          # the STFT's reflect padding (512) needs a signal of 256 (T - 1) > 512 samples
 DEFAULT_MAX_FRAMES = 1 << 18            # packed frames per group (S, rebuilt and two spectra: 7 x 513 floats per frame, ~3.8 GB)
 
@@ -38,16 +39,6 @@ def melscale_fbanks(dtype: torch.dtype = torch.float64) -> torch.Tensor:
 def inverse_mel_matrix() -> torch.Tensor:
     """pinv(fb^T) [513, 80] in fp64: P = relu(pinv(fb^T) . exp(mel)) is InverseMelScale's gels solution (fb^T has full row rank)."""
     return torch.linalg.pinv(melscale_fbanks(torch.float64).t())
-
-
-def hann_window(dtype: torch.dtype = torch.float64) -> torch.Tensor:
-    return torch.hann_window(N_FFT, periodic=True, dtype=dtype)
-
-
-def twiddles() -> torch.Tensor:
-    """exp(-2 pi i j / 1024) for j < 1024, computed in fp64, as complex64."""
-    ang = -2.0 * math.pi * torch.arange(N_FFT, dtype=torch.float64) / N_FFT
-    return torch.polar(torch.ones_like(ang), ang).to(torch.complex64)
 
 
 def check_args(n_iter: int, momentum: float, init: str) -> None:
@@ -82,8 +73,7 @@ class GriffinLimVocoder:
     def __init__(self, device: str = "cuda"):
         self.device = torch.device(device)
         self.pinv = inverse_mel_matrix().to(torch.float32).contiguous().to(self.device)
-        self.window = hann_window(torch.float64).to(torch.float32).to(self.device)
-        self.tw = torch.view_as_real(twiddles()).contiguous().to(self.device)
+        self.window, self.tw = device_tables(self.device)
         self.tile_frames = int(kk.load().kk_gl_tile_frames())
         self._ws: Optional[torch.Tensor] = None
 

@@ -126,6 +126,11 @@ def pointer_table(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def packed_offsets(lengths, dtype=torch.int64, device="cpu") -> "torch.Tensor":
+    """[0, n0, n0 + n1, ...]: where each row of a packed batch starts, and the total (summed in int64)."""
+    return torch.tensor([0] + list(lengths), dtype=torch.int64).cumsum(0).to(dtype).to(device)
+
+
 def copy_many(pairs) -> None:
     """dst.copy_(src) for up to 16 (dst, src) pairs of contiguous same-size device tensors per launch."""
     for i in range(0, len(pairs), 16):

@@ -71,11 +71,11 @@ class LoudnessNormaliser:
         if sum(n) >= 2 ** 31:
             raise ValueError(f"{sum(n)} samples in the batch: the kernels index fewer than 2^31; split the call")
         x = torch.cat([w.detach().to(self.device, torch.float32) for w in waves]).contiguous()
-        woff = torch.tensor([0] + n, dtype=torch.int64).cumsum(0).to(self.device)
+        woff = kk.packed_offsets(n, torch.int64, self.device)
         return n, x, woff
 
     def _offsets(self, n: Sequence[int], unit: int) -> Tuple[torch.Tensor, int]:
-        off = torch.tensor([0] + [-(-v // unit) for v in n], dtype=torch.int64).cumsum(0)
+        off = kk.packed_offsets([-(-v // unit) for v in n])
         return off.to(torch.int32).to(self.device), int(off[-1])
 
     def _edges(self, n, x, woff, top_db: float, margin_ms: float) -> torch.Tensor:

@@ -118,8 +118,7 @@ class Resampler:
         (the resampled waveforms back to back, their lengths); nothing comes back to the host in between."""
         dev, B = self.device, len(n)
         m = [out_length(v, r) for v, r in zip(n, rows)]
-        cum = lambda v: torch.tensor([0] + v, dtype=torch.int64).cumsum(0).to(dev)
-        woff_in, woff_out = cum(n), cum(m)
+        woff_in, woff_out = kk.packed_offsets(n, torch.int64, dev), kk.packed_offsets(m, torch.int64, dev)
         rate = torch.tensor(rows, dtype=torch.int32).to(dev)
         tiles = torch.tensor([[b, j0] for b, v in enumerate(m) for j0 in range(0, v, self.tile)], dtype=torch.int32).to(dev)
         out = torch.empty(sum(m), dtype=torch.float32, device=dev)
