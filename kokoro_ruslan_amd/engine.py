@@ -24,7 +24,8 @@ import math
 import os
 import threading
 from collections import OrderedDict
-from typing import Dict, Optional, Sequence, Tuple
+from functools import lru_cache
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -41,6 +42,74 @@ _ITEMSIZE = {torch.float32: 4, torch.bfloat16: 2, torch.float64: 8, torch.int64:
 def _b16(t) -> int:
     """1 when the tensor is stored as bf16 (the C ABI's *_bf16 flags are derived from the tensors themselves)."""
     return 1 if t is not None and t.dtype == torch.bfloat16 else 0
+
+
+class LayerNames(NamedTuple):
+    """What the launches of one transformer layer are addressed by.  site / next_ln are per sub-layer: "sa", "ff" and, in the
+    decoder, "ca".  A site seeds the sub-layer's dropout masks (its kernels add small fixed offsets), so the forward and the
+    backward of a layer must take it from here; next_ln = (workspace key, parameter prefix, dtype) of the LayerNorm that reads
+    the sub-layer's output, which its fused tail computes.  (The two functions below cache what they return: read only.)"""
+    prefix: str                                     # parameters: "transformer_encoder_layers.<i>" / "decoder.layers.<i>"
+    key: str                                        # workspace buffers: "<ns>enc<i>" / "<ns>dec<i>"
+    site: Dict[str, int]
+    next_ln: Dict[str, Tuple[str, str, torch.dtype]]
+
+
+_SUBLAYER = {"sa": ".self_attn", "ca": ".cross_attn", "ff": ".ff"}     # parameter prefix of a sub-layer within its layer
+
+
+@lru_cache(maxsize=None)
+def encoder_layer_names(i: int, n_layers: int, dtype: torch.dtype, ns: str = "") -> LayerNames:
+    """Text-encoder layer i of n_layers with activations stored as `dtype`, workspace keys under the namespace `ns`
+    (inference: "syn." ...).  The stack ends in encoder_norm, whose output is fp32."""
+    pf, key, site = f"transformer_encoder_layers.{i}", f"{ns}enc{i}", 1000 + 32 * i
+    after = ((f"{ns}enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", dtype) if i + 1 < n_layers
+             else (f"{ns}enc.norm", "encoder_norm", torch.float32))
+    return LayerNames(pf, key, {"sa": site, "ff": site + 8}, {"sa": (key + ".ln2", pf + ".norm2", dtype), "ff": after})
+
+
+@lru_cache(maxsize=None)
+def decoder_layer_names(i: int, n_layers: int, dtype: torch.dtype, ns: str = "") -> LayerNames:
+    """Decoder layer i of n_layers (self-attention, cross-attention, feed-forward); the stack ends in decoder.norm."""
+    pf, key, site = f"decoder.layers.{i}", f"{ns}dec{i}", 2000 + 32 * i
+    after = ((f"{ns}dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", dtype) if i + 1 < n_layers
+             else (f"{ns}dec.norm", "decoder.norm", dtype))
+    return LayerNames(pf, key, {"sa": site, "ca": site + 8, "ff": site + 16},
+                      {"sa": (key + ".ln2", pf + ".norm2", dtype), "ca": (key + ".ln3", pf + ".norm3", dtype), "ff": after})
+
+
+class _Step:
+    """What the stages of one training micro-batch share (KokoroEngine._fb_launches).  _step_setup makes it with every decision
+    taken; what a later stage fills in is None (deferred0: []) until then, so no stage reads a name that nothing has bound."""
+    __slots__ = (
+        "batch", "backward", "zero_grads",
+        "B", "Pn", "T", "Tp", "Ne", "Nd", "Np",           # Tp: frames the durations expand to (>= T); rows B * Pn, B * T, B * Tp
+        "p_din", "pe_drop", "p_enc", "p_dec", "p_var",    # dropout rates (0 with train_dropout off)
+        "stack",                                          # text encoder as one persistent launch (_encoder_stack_ok)
+        "gen_keep", "gen_layers",                         # attention keep bits generated beside it, for so many decoder layers
+        "spec_aug",
+        "sort_buckets",                                   # bucket-embedding gradients as the sorted segmented sum (embed_bwd_sorted)
+        "tail_mode",                                      # where the backward's memory tail runs (tail_aside, resolved)
+        "lcfg", "largs",                                  # kk.KkLossCfg; the loss kernels' common arguments (_fb_losses)
+        "fork",                                           # events: behind the loss gradients (_fb_loss_grads),
+        "tail_fork",                                      # behind the last cross-attention dK / dV (tail_mode 1, 3, 4; 2: the decoder backward),
+        "wgrad0_fork", "deferred0",                       # behind decoder layer 0's backward when its grouped weight gradients wait: those
+        # workspace views that cross stages, set by the stage that first writes them:
+        "text_mask",                                                                  # _step_setup
+        "shifted", "dec_head",                                                        # _fb_decoder_head: (x0, dec0.xa, dec0.ln2.y)
+        "enc_last", "enc",                                                            # _fb_encoder_fwd: last stream, encoder_norm of it
+        "dur_pred", "col_e", "col_f", "idx", "lens", "memory", "fmask", "pidx", "eidx", "pitch_pred", "energy_pred",   # _fb_variance_adaptor
+        "xf_p", "fmask_p", "pitch_l", "energy_l",         # (the predictors' Tp-frame views, what the losses read; the T-frame ones when Tp == T)
+        "be_order", "be_items",                                                       # _fb_predictors_fwd, with sort_buckets
+        "dec_last", "dec_out", "mel_pred", "stop",                                    # _fb_decoder_fwd
+        "dmel", "ddur", "dstop", "dpitch", "denergy",                                 # _fb_loss_grads
+        "dy", "dmem")                                                                 # _fb_decoder_bwd: gradients of the decoder stream, the memory
+
+    def __init__(self, **decided):
+        for name in self.__slots__:
+            setattr(self, name, decided.pop(name, None))
+        assert not decided, decided
+        self.deferred0 = []
 
 
 class Arena:
@@ -865,12 +934,13 @@ class KokoroEngine:
         """kk_attn_keep_gen for every decoder attention launch of a (B, T) step; False when that shape has no keep-bit arrays."""
         d, ents = self.dims, []
         for li in range(d.dec_layers if layers is None else min(layers, d.dec_layers)):
-            for sub, off, cz in ((".sa", 0, True), (".ca", 8, False)):
-                kb = self._attn_keep(f"dec{li}{sub}", B, T, T, p_dec, 1)
+            lay = self._dec_layer(li)
+            for sub, cz in (("sa", True), ("ca", False)):
+                kb = self._attn_keep(f"{lay.key}.{sub}", B, T, T, p_dec, 1)
                 if kb is not None:
-                    ents.append((kb, 2000 + 32 * li + off + 3, p_dec, B, d.heads, T, T, cz))
+                    ents.append((kb, lay.site[sub] + 3, p_dec, B, d.heads, T, T, cz))      # (+ 3: the attention kernels' own offset)
                     if mark_ready:
-                        self._keep_ready.add(f"dec{li}{sub}")
+                        self._keep_ready.add(f"{lay.key}.{sub}")
         for c0 in range(0, len(ents), 16):
             part = ents[c0:c0 + 16]
             table = self._table(("keepgen",) + tuple((e[0].data_ptr(), e[1], e[2], B, T) for e in part), lambda part=part: kk.keep_sites(part))
@@ -1076,9 +1146,8 @@ class KokoroEngine:
         cos, sin = self._rope_tables(Pn)
         layers = []
         for i in range(L):
-            pf, key = f"transformer_encoder_layers.{i}", f"enc{i}"
-            nkey, npf, ndt = ((f"enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", edt) if i + 1 < L
-                              else ("enc.norm", "encoder_norm", torch.float32))
+            lay = self._enc_layer(i)
+            pf, key, (nkey, npf, ndt) = lay.prefix, lay.key, lay.next_ln["ff"]
             sa, ff = key + ".sa", key + ".ff"
             layers.append(dict(
                 w_qkv=self._Wf(pf + ".self_attn.w_q.weight", 3), g_q=P[pf + ".self_attn.q_norm.weight"],
@@ -1098,7 +1167,7 @@ class KokoroEngine:
                 f2=self._buf(ff + ".f2", Ne, H, dtype=edt), rstd_f=self._buf(ff + ".rstd_f", Ne),
                 xo=self._buf(key + ".xo", Ne, H), next_y=self._buf(nkey + ".y", Ne, H, dtype=ndt),
                 next_mean=self._buf(nkey + ".mean", Ne), next_rstd=self._buf(nkey + ".rstd", Ne),
-                next_y_bf16=1 if ndt == torch.bfloat16 else 0, site=1000 + 32 * i, p=float(p_enc), dpr=float(self._dpr(i, L))))
+                next_y_bf16=1 if ndt == torch.bfloat16 else 0, site=lay.site["sa"], p=float(p_enc), dpr=float(self._dpr(i, L))))
         sig = ("encstack", B, Pn, float(p_enc), self.train_dropout, self.enc_placement) + tuple(v.data_ptr() for v in layers[0].values() if hasattr(v, "data_ptr"))
         desc = self._table(sig, lambda: kk.enc_stack(B, Pn, H, F, h, text_mask, cos, sin, self.rng, self._enc_sync, layers, self.enc_placement,
                                                      self.enc_trace, self.enc_trace_wg))
@@ -1230,236 +1299,288 @@ class KokoroEngine:
             self._wgrad_queue.clear()
 
     def _fb_launches(self, batch, loss_scale, adaptive, backward, zero_grads=False, expanded_len=None):
-        d, a, P, G = self.dims, self.arena, self.arena.P, self.arena.G
+        """The stages of one micro-batch in launch order.  Streams: the decoder head runs on _kv beside the encoder, the predictors'
+        forward and (forked from st.fork) the side backward on _side; the decoder chain, captured first, stays on this one."""
+        st = self._step_setup(batch, loss_scale, adaptive, backward, zero_grads, expanded_len)
+        self._fb_decoder_head(st)
+        self._fb_encoder_fwd(st)
+        self._fb_variance_adaptor(st)
+        # ---- decoder (model.py:519-531; transformers.py:543-583,660) ----
+        self._mark("memory ready")
+        self._cross_kv_fwd_all(st.memory, st.Nd, st.T, self.dec_dt)        # every layer's cross-attention K/V in one GEMM
+        self._mark("cross K/V fwd done")
+        self._fb_predictors_fwd(st)
+        self._fb_decoder_fwd(st)
+        out = self._fb_losses(st)
+        if not st.backward:
+            return out
+        # =========================== backward ===========================
+        self._fb_loss_grads(st)
+        # The decoder backward is the critical path, so it is captured first and the predictors' + encoder's backward
+        # after it, forked from the point right after the loss gradients (see _on_stream).
+        self._fb_decoder_bwd(st)
+        # the memory tail needs the cross-attention dK / dV of all layers and nothing else of the decoder backward: it runs on the
+        # third stream beside layer 0's self-attention backward (1) or beside the input projection's backward (2), or on the side
+        # stream behind the encoder's backward (3, 4: _fb_side_bwd), or at the end of the main chain (0)
+        if st.tail_mode == 2:
+            st.tail_fork = self._fork_point()
+        self._fb_input_projection_bwd(st)
+        if st.tail_mode in (1, 2):
+            with self._on_stream(self._kv, "kv.", after=st.tail_fork):
+                self._fb_memory_tail(st)
+            self._join(self._kv)
+        elif st.tail_mode == 0:
+            self._fb_memory_tail(st)
+        self._mark("main: backward tail done")
+        self._fb_side_bwd(st)
+        self._fb_finish(st)
+        return out
+
+    # ---- the stages: each takes the step's record; the views it leaves for later stages are listed in _Step ----
+    def _enc_layer(self, i, ns="") -> LayerNames:
+        return encoder_layer_names(i, self.dims.enc_layers, self.enc_dt, ns)
+
+    def _dec_layer(self, i, ns="") -> LayerNames:
+        return decoder_layer_names(i, self.dims.dec_layers, self.dec_dt, ns)
+
+    def _step_setup(self, batch, loss_scale, adaptive, backward, zero_grads, expanded_len) -> _Step:
+        """Validate the batch, take every decision of the step, issue the launches in front of the first fork."""
+        d, hp = self.dims, self.hp
         self._grads_fresh = bool(zero_grads) or self._first_micro
         self._ow_seen = set() if (self._grads_fresh and backward) else None
         self._ow_expect = None
-        H, M, Fv = d.hidden, d.mel, d.var_filter
-        ids, mel, dur = batch["phoneme_indices"], batch["mel_specs"], batch["phoneme_durations"]
-        stress = batch.get("stress_indices")
-        B, Pn = ids.shape
-        T = mel.shape[1]
-        Ne, Nd = B * Pn, B * T
-        edt, ddt = self.enc_dt, self.dec_dt               # activation storage of the encoder / decoder stacks
-        pe = P["positional_encoding.pe"].view(d.max_len, H)
+        B, Pn = batch["phoneme_indices"].shape
+        T = batch["mel_specs"].shape[1]
         Tp = T if expanded_len is None else max(int(expanded_len), 3)     # variance_predictor.py:358-360 (at least 3 frames)
         if Tp < T:
             raise RuntimeError(f"The size of tensor a ({Tp}) must match the size of tensor b ({T}) at non-singleton dimension 1 "
                                f"(durations expand to {Tp} frames, the batch has {T} mel frames: losses.py:126)")
         if max(T, Tp) > d.max_len or Pn > d.max_len:
             raise ValueError(f"sequence longer than the positional table ({d.max_len})")
-        Np = B * Tp
+        if self.tail_aside not in (-1, 0, 1, 2, 3, 4):
+            raise ValueError(f"tail_aside = {self.tail_aside!r}: -1 or one of the modes 0 ... 4")
+        p_dec = self._p(hp.decoder_dropout)
+        stack = self._encoder_stack_ok(B, Pn)
+        # beside the persistent encoder forward, where that pays (measured: -0.4 % at 8 x 512, +1.6 % at 8 x 1024, where the generator
+        # outlasts the encoder and delays the decoder head; profiles/r06_keep_bits_gen_ab.txt)
+        gen_keep = bool(self.attn_keep_gen and self.attn_keep_bits and self.train_dropout and p_dec > 0.0 and self.dec_dt == torch.bfloat16 and
+                        self.overlap and stack and self.dec_head_aside)
+        gen_layers = 0
+        if gen_keep:
+            units = B * d.heads * ((T + 31) // 32) ** 2 * 1.5          # a layer: the causal self-attention (half) + the cross-attention
+            gen_layers = min(d.dec_layers, int(self.attn_keep_gen_rate * (160.0 + 2.0 * Pn) / units))
+            gen_keep = gen_layers > 0
+        tail_mode = (4 if B * T <= 4096 else 3) if self.tail_aside < 0 else self.tail_aside
+        st = _Step(batch=batch, backward=bool(backward), zero_grads=bool(zero_grads), B=B, Pn=Pn, T=T, Tp=Tp, Ne=B * Pn, Nd=B * T, Np=B * Tp,
+                   p_din=self._p(hp.decoder_input_dropout), pe_drop=self._p(hp.encoder_dropout), p_enc=self._p(hp.encoder_dropout),
+                   p_dec=p_dec, p_var=self._p(hp.variance_dropout), stack=stack, gen_keep=gen_keep, gen_layers=gen_layers,
+                   spec_aug=bool(self.train_dropout and hp.use_spec_augment and self.spec_augment_active),
+                   sort_buckets=bool(backward and self.embed_bwd_sorted and d.var_bins <= 1024),
+                   tail_mode=tail_mode if self.overlap else 0,
+                   lcfg=kk.KkLossCfg(hp.duration_loss_weight, hp.stop_token_loss_weight, hp.pitch_loss_weight, hp.energy_loss_weight,
+                                     hp.duration_huber_delta, hp.pitch_huber_delta, hp.energy_huber_delta, hp.stop_token_pos_weight,
+                                     float(loss_scale), 1 if adaptive else 0))
+        self._keep_ready = set()
+        st.text_mask = self._buf("text_mask", B, Pn, dtype=torch.uint8)
+        if not self.fuse_enc_prologue:
+            kk.call("kk_ids_eq_zero", batch["phoneme_indices"], st.text_mask, st.Ne)
+        if self.train_dropout:
+            self.rng.add_(1)                              # fresh masks every micro-batch (captured in the hipGraph)
+        self._mark("step.start")
+        return st
 
-        # ---- decoder head: mel input projection + layer-0 self-attention need no encoder output (model.py:519-531) ----
-        p_din = self._p(self.hp.decoder_input_dropout)
-        shifted = self._buf("dec.shifted", Nd, M)
+    def _dec_self_attn_fwd(self, st, i, y_in, n1_in):
+        """Self-attention sub-layer of decoder layer i: (stream behind it, its norm2 output)."""
+        lay = self._dec_layer(i)
+        ya = self._buf(lay.key + ".xa", st.Nd, self.dims.hidden)
+        n2 = self._attn_fwd(lay.key + ".sa", lay.prefix + ".self_attn", n1_in, None, st.B, st.T, st.T, True, True, None, y_in, ya,
+                            lay.site["sa"], st.p_dec, self._dpr(i, self.dims.dec_layers), next_ln=lay.next_ln["sa"])
+        return ya, n2
 
-        def self_attn(i, y_in, n1_in):
-            key, pf, st = f"dec{i}", f"decoder.layers.{i}", 2000 + 32 * i
-            ya_ = self._buf(key + ".xa", Nd, H)
-            n2_ = self._attn_fwd(key + ".sa", pf + ".self_attn", n1_in, None, B, T, T, True, True, None, y_in, ya_, st, p_dec,
-                                 self._dpr(i, d.dec_layers), next_ln=(key + ".ln2", pf + ".norm2", ddt))
-            return ya_, (n2_ if n2_ is not None else self._ln_fwd(key + ".ln2", ya_, pf + ".norm2", ddt))
-
-        def decoder_head():
-            kk.call("kk_shift_right", mel, shifted, B, T, M)
+    def _fb_decoder_head(self, st) -> None:
+        """---- decoder head: mel input projection + layer-0 self-attention need no encoder output (model.py:519-531) ----
+        On the _kv stream beside the encoder; joined before the first cross-attention (_fb_decoder_fwd)."""
+        P, H, M, B, T, Nd = self.arena.P, self.dims.hidden, self.dims.mel, st.B, st.T, st.Nd
+        pe = P["positional_encoding.pe"].view(self.dims.max_len, H)
+        st.shifted = shifted = self._buf("dec.shifted", Nd, M)
+        with self._on_stream(self._kv, "kv.", self.dec_head_aside):
+            if st.zero_grads and not self.zero_late:
+                self._zero_grad_step()
+            kk.call("kk_max_i64", st.batch["phoneme_durations"], st.Ne, self.max_dur)  # (read by the losses only: not in front of the encoder)
+            kk.call("kk_shift_right", st.batch["mel_specs"], shifted, B, T, M)
             y0 = self._buf("dec.x0", Nd, H)
-            if self.train_dropout and (p_din > 0.0 or pe_drop > 0.0):    # dropout(proj) + pe, then the PE module's dropout
+            if self.train_dropout and (st.p_din > 0.0 or st.pe_drop > 0.0):    # dropout(proj) + pe, then the PE module's dropout
                 lin, t1 = self._buf("tmp.dec_lin", Nd, H), self._buf("tmp.dec_t1", Nd, H)
                 self._linear(shifted, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], lin)
-                kk.call("kk_dropout_fwd", lin, pe, T, t1, Nd, H, T, self.rng, 30, p_din, 0, 0.0, 0, 0.0)
-                kk.call("kk_dropout_fwd", t1, None, 0, y0, Nd, H, T, self.rng, 31, pe_drop, 0, 0.0, 0, 0.0)
+                kk.call("kk_dropout_fwd", lin, pe, T, t1, Nd, H, T, self.rng, 30, st.p_din, 0, 0.0, 0, 0.0)
+                kk.call("kk_dropout_fwd", t1, None, 0, y0, Nd, H, T, self.rng, 31, st.pe_drop, 0, 0.0, 0, 0.0)
             else:
                 self._linear(shifted, self._W("mel_projection_in.weight"), P["mel_projection_in.bias"], y0, res=pe, res_mod=T)
-            n10 = self._ln_fwd("dec0.ln1", y0, "decoder.layers.0.norm1", ddt)
+            n10 = self._ln_fwd("dec0.ln1", y0, "decoder.layers.0.norm1", self.dec_dt)
             # The 200 MB gradient zero-fill goes HERE: the launches above are in flight before the persistent encoder
             # kernel (which takes every CU's LDS) starts; the fill needs no LDS and runs beside it, while the GEMMs and
             # the attention below cannot and follow the encoder — with the fill in front of the whole head, none of the
             # head ran early and it ended 46 us after the cross-attention K/V GEMM, on the critical path.
-            if zero_grads and self.zero_late:
+            if st.zero_grads and self.zero_late:
                 self._zero_grad_step()
             self._mark("kv: zero_grad done")
-            if gen_keep:
+            if st.gen_keep:
                 # the keep bits of every decoder attention launch of this step, HERE: this stream idles until the persistent encoder
                 # launch (which holds every CU's LDS) has ended, and the generator needs no LDS — it runs beside the encoder
-                self._keep_gen_launch(B, T, p_dec, 0, True, layers=gen_layers)
+                self._keep_gen_launch(B, T, st.p_dec, 0, True, layers=st.gen_layers)
                 self._mark("kv: keep bits generated")
-            ya0, n20 = self_attn(0, y0, n10)
-            return y0, ya0, n20
-
-        # ---- encoder (model.py:375-388) ----
-        text_mask = self._buf("text_mask", B, Pn, dtype=torch.uint8)
-        if not self.fuse_enc_prologue:
-            kk.call("kk_ids_eq_zero", ids, text_mask, Ne)
-        x = self._buf("enc.x0", Ne, H)
-        hp = self.hp
-        if self.train_dropout:
-            self.rng.add_(1)                              # fresh masks every micro-batch (captured in the hipGraph)
-        pe_drop, p_enc, p_dec, p_var = self._p(hp.encoder_dropout), self._p(hp.encoder_dropout), self._p(hp.decoder_dropout), self._p(hp.variance_dropout)
-        self._mark("step.start")
-        stack = self._encoder_stack_ok(B, Pn)
-        self._keep_ready = set()
-        # beside the persistent encoder forward, where that pays (measured: -0.4 % at 8 x 512, +1.6 % at 8 x 1024, where the generator
-        # outlasts the encoder and delays the decoder head; profiles/r06_keep_bits_gen_ab.txt)
-        gen_keep = bool(self.attn_keep_gen and self.attn_keep_bits and self.train_dropout and p_dec > 0.0 and ddt == torch.bfloat16 and
-                        self.overlap and stack and self.dec_head_aside)
-        gen_layers = 0
-        if gen_keep:
-            units = B * self.dims.heads * ((T + 31) // 32) ** 2 * 1.5          # a layer: the causal self-attention (half) + the cross-attention
-            gen_layers = min(self.dims.dec_layers, int(self.attn_keep_gen_rate * (160.0 + 2.0 * Pn) / units))
-            gen_keep = gen_layers > 0
-        with self._on_stream(self._kv, "kv.", self.dec_head_aside):     # beside the encoder; joined before the first cross-attention
-            if zero_grads and not self.zero_late:
-                self._zero_grad_step()
-            kk.call("kk_max_i64", dur, Ne, self.max_dur)  # (read by the losses only: not in front of the encoder)
-            dec_head = decoder_head()                     # (includes the gradient zero-fill, see there)
+            st.dec_head = (y0,) + self._dec_self_attn_fwd(st, 0, y0, n10)
             self._mark("kv: decoder head done")
-        y1 = None                                         # LayerNorm outputs come from the previous sub-layer's fused tail
+
+    def _encoder_layers_fwd(self, ns, first, x, y1, B, Pn, text_mask, p=0.0, train=False):
+        """Encoder layers [first, enc_layers) as one launch sequence per layer, on the workspace keys `ns` + "enc<i>...": x = the
+        stream entering layer `first`, y1 = its norm1 output.  train: RNG sites, drop-path and the step's marks apply (the inference
+        callers run with dropout off and the kernels' default site).  Returns (stream behind the last layer, encoder_norm output)."""
+        d, H, Ne = self.dims, self.dims.hidden, B * Pn
+        for i in range(first, d.enc_layers):
+            lay = self._enc_layer(i, ns)
+            dpr = self._dpr(i, d.enc_layers) if train else 0.0
+            xm, xo = self._buf(lay.key + ".xm", Ne, H), self._buf(lay.key + ".xo", Ne, H)
+            y2 = self._attn_fwd(lay.key + ".sa", lay.prefix + ".self_attn", y1, None, B, Pn, Pn, True, False, text_mask, x, xm,
+                                lay.site["sa"] if train else 0, p, dpr, next_ln=lay.next_ln["sa"])
+            y1 = self._ffn_fwd(lay.key + ".ff", lay.prefix + ".ff", y2, xm, xo, d.enc_ff, Pn, lay.site["ff"] if train else 0, p, dpr,
+                               next_ln=lay.next_ln["ff"])
+            x = xo
+            if train:
+                self._mark(f"enc{i} fwd done")
+        return x, y1
+
+    def _fb_encoder_fwd(self, st) -> None:
+        """---- encoder (model.py:375-388) ----"""
+        d, P, H, edt, B, Pn, Ne = self.dims, self.arena.P, self.dims.hidden, self.enc_dt, st.B, st.Pn, st.Ne
+        ids, stress = st.batch["phoneme_indices"], st.batch.get("stress_indices")
+        pe = P["positional_encoding.pe"].view(d.max_len, H)
+        x, lay0 = self._buf("enc.x0", Ne, H), self._enc_layer(0)
+        # LayerNorm outputs come from the previous sub-layer's fused tail; layer 0's from the prologue
         if self.fuse_enc_prologue:                        # key mask + embedding + layer 0's pre-norm: ONE launch in front of the encoder
             y1, m1, r1 = self._buf("enc0.ln1.y", Ne, H, dtype=edt), self._buf("enc0.ln1.mean", Ne), self._buf("enc0.ln1.rstd", Ne)
             kk.call("kk_embed_ln_fwd", ids, stress, P["text_embedding.weight"], P["stress_embedding.weight"] if stress is not None else None,
-                    pe, x, B, Pn, H, float(H ** 0.5), self.rng, 1, pe_drop, text_mask, P["transformer_encoder_layers.0.norm1.weight"],
-                    P["transformer_encoder_layers.0.norm1.bias"], y1, _b16(y1), m1, r1)
+                    pe, x, B, Pn, H, float(H ** 0.5), self.rng, 1, st.pe_drop, st.text_mask, P[lay0.prefix + ".norm1.weight"],
+                    P[lay0.prefix + ".norm1.bias"], y1, _b16(y1), m1, r1)
         else:
             kk.call("kk_embed_fwd", ids, stress, P["text_embedding.weight"], P["stress_embedding.weight"] if stress is not None else None,
-                    pe, x, B, Pn, H, float(H ** 0.5), self.rng, 1, pe_drop)
-        if stack:                                         # all layers in ONE persistent launch (csrc/kk_encstack.hip)
-            if y1 is None:
-                y1 = self._ln_fwd("enc0.ln1", x, "transformer_encoder_layers.0.norm1", edt)
-            x, y1 = self._encoder_stack_fwd(x, B, Pn, text_mask, p_enc)
+                    pe, x, B, Pn, H, float(H ** 0.5), self.rng, 1, st.pe_drop)
+            y1 = self._ln_fwd(lay0.key + ".ln1", x, lay0.prefix + ".norm1", edt)
+        if st.stack:                                      # all layers in ONE persistent launch (csrc/kk_encstack.hip)
+            x, y1 = self._encoder_stack_fwd(x, B, Pn, st.text_mask, st.p_enc)
             self._mark(f"enc{d.enc_layers - 1} fwd done")
-        for i in range(0 if not stack else d.enc_layers, d.enc_layers):      # when dropout is on, from _ln_fwd otherwise
-            pf, key, st = f"transformer_encoder_layers.{i}", f"enc{i}", 1000 + 32 * i
-            dpr = self._dpr(i, d.enc_layers)
-            if y1 is None:
-                y1 = self._ln_fwd(key + ".ln1", x, pf + ".norm1", edt)
-            xm = self._buf(key + ".xm", Ne, H)
-            y2 = self._attn_fwd(key + ".sa", pf + ".self_attn", y1, None, B, Pn, Pn, True, False, text_mask, x, xm, st, p_enc, dpr,
-                                next_ln=(key + ".ln2", pf + ".norm2", edt))
-            if y2 is None:
-                y2 = self._ln_fwd(key + ".ln2", xm, pf + ".norm2", edt)
-            xo = self._buf(key + ".xo", Ne, H)
-            nxt = ((f"enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", edt) if i + 1 < d.enc_layers
-                   else ("enc.norm", "encoder_norm", torch.float32))
-            y1 = self._ffn_fwd(key + ".ff", pf + ".ff", y2, xm, xo, d.enc_ff, Pn, st + 8, p_enc, dpr, next_ln=nxt)
-            x = xo
-            self._mark(f"enc{i} fwd done")
-        enc_last = x
-        enc = y1 if y1 is not None else self._ln_fwd("enc.norm", enc_last, "encoder_norm")
+        st.enc_last, st.enc = self._encoder_layers_fwd("", d.enc_layers if st.stack else 0, x, y1, B, Pn, st.text_mask, st.p_enc, train=True)
 
-        # ---- variance adaptor (variance_predictor.py:338-439) ----
-        dur_pred = self._buf("out.log_dur", B, Pn)
-        col_e = self._buf("vp.col_enc", Ne, 3 * H, dtype=edt)      # (both conv unfolds are the predictors' inputs only: side stream)
+    def _fb_variance_adaptor(self, st) -> None:
+        """---- variance adaptor (variance_predictor.py:338-439) ----"""
+        d, P, H, hp, edt, ddt = self.dims, self.arena.P, self.dims.hidden, self.hp, self.enc_dt, self.dec_dt
+        batch, B, Pn, T, Tp, Ne, Nd, Np = st.batch, st.B, st.Pn, st.T, st.Tp, st.Ne, st.Nd, st.Np
+        st.dur_pred = self._buf("out.log_dur", B, Pn)
+        st.col_e = self._buf("vp.col_enc", Ne, 3 * H, dtype=edt)      # (both conv unfolds are the predictors' inputs only: side stream)
         # (teacher forcing: the regulator and the embeddings below use the batch's durations / pitch / energy, so the three
-        #  predictors feed only the losses and run on the side stream — see predictors())
-        idx, lens, tot = (self._buf("lr.idx", B, T, dtype=torch.int64), self._buf("lr.lens", B, dtype=torch.int64),
-                          self._buf("lr.total", B, dtype=torch.int64))
-        kk.call("kk_length_regulate_index", dur, idx, lens, tot, B, Pn, T)
+        #  predictors feed only the losses and run on the side stream — see _fb_predictors_fwd)
+        st.idx, st.lens, tot = (self._buf("lr.idx", B, T, dtype=torch.int64), self._buf("lr.lens", B, dtype=torch.int64),
+                                self._buf("lr.total", B, dtype=torch.int64))
+        kk.call("kk_length_regulate_index", batch["phoneme_durations"], st.idx, st.lens, tot, B, Pn, T)
         xf = self._buf("va.xf", Nd, H)
-        memory, fmask = self._buf("va.memory", Nd, H, dtype=ddt), self._buf("va.fmask", B, T, dtype=torch.uint8)
-        pidx, eidx = self._buf("va.pidx", B, T, dtype=torch.int32), self._buf("va.eidx", B, T, dtype=torch.int32)
-        spec_aug = self.train_dropout and hp.use_spec_augment and self.spec_augment_active
+        st.memory, st.fmask = memory, fmask = self._buf("va.memory", Nd, H, dtype=ddt), self._buf("va.fmask", B, T, dtype=torch.uint8)
+        st.pidx, st.eidx = pidx, eidx = self._buf("va.pidx", B, T, dtype=torch.int32), self._buf("va.eidx", B, T, dtype=torch.int32)
         if self.fuse_memory_fwd:     # gather + embedding adds + SpecAugment: ONE launch between the encoder and the cross-attention K/V GEMM
-            kk.call("kk_regulate_embed_fwd", enc, idx, batch["pitches"], batch["energies"], P[f"{VA}.pitch_bins"], P[f"{VA}.energy_bins"],
-                    P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, xf, memory, pidx, eidx, fmask, B, Pn, T, H,
-                    d.var_bins, _b16(memory), self.rng if spec_aug else None, 20, hp.spec_augment_time_mask_max,
+            kk.call("kk_regulate_embed_fwd", st.enc, st.idx, batch["pitches"], batch["energies"], P[f"{VA}.pitch_bins"], P[f"{VA}.energy_bins"],
+                    P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], st.lens, xf, memory, pidx, eidx, fmask, B, Pn, T, H,
+                    d.var_bins, _b16(memory), self.rng if st.spec_aug else None, 20, hp.spec_augment_time_mask_max,
                     hp.spec_augment_freq_mask_max, hp.spec_augment_num_time_masks, hp.spec_augment_num_freq_masks)
         else:
-            kk.call("kk_length_regulate_gather", enc, idx, xf, B, Pn, T, H)       # detached by construction
+            kk.call("kk_length_regulate_gather", st.enc, st.idx, xf, B, Pn, T, H)       # detached by construction
             kk.call("kk_bucket_embed_add_fwd", xf, batch["pitches"], batch["energies"], P[f"{VA}.pitch_bins"], P[f"{VA}.energy_bins"],
-                    P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory, pidx, eidx, fmask, B, T, H,
+                    P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], st.lens, memory, pidx, eidx, fmask, B, T, H,
                     d.var_bins, _b16(memory))
-        pitch_pred, energy_pred = self._buf("out.pitch", B, Tp), self._buf("out.energy", B, Tp)
-        col_f = self._buf("vp.col_frames", Np, 3 * H, dtype=ddt)
+        st.pitch_pred, st.energy_pred = self._buf("out.pitch", B, Tp), self._buf("out.energy", B, Tp)
+        st.col_f = self._buf("vp.col_frames", Np, 3 * H, dtype=ddt)
         if Tp != T:      # the predictors' own T'-frame view of the expansion; the losses read the first T columns
-            xf_p, fmask_p = self._buf("va.xf_p", Np, H), self._buf("va.fmask_p", B, Tp, dtype=torch.uint8)
-            pitch_l, energy_l = self._buf("out.pitch_T", B, T), self._buf("out.energy_T", B, T)
+            st.xf_p, st.fmask_p = self._buf("va.xf_p", Np, H), self._buf("va.fmask_p", B, Tp, dtype=torch.uint8)
+            st.pitch_l, st.energy_l = self._buf("out.pitch_T", B, T), self._buf("out.energy_T", B, T)
         else:
-            xf_p, fmask_p, pitch_l, energy_l = xf, fmask, pitch_pred, energy_pred
-        if spec_aug and not self.fuse_memory_fwd:         # on the cross-attention memory only (model.py:636-639)
+            st.xf_p, st.fmask_p, st.pitch_l, st.energy_l = xf, fmask, st.pitch_pred, st.energy_pred
+        if st.spec_aug and not self.fuse_memory_fwd:         # on the cross-attention memory only (model.py:636-639)
             kk.call("kk_specaug", memory, B, T, H, self.rng, 20, hp.spec_augment_time_mask_max, hp.spec_augment_freq_mask_max,
                     hp.spec_augment_num_time_masks, hp.spec_augment_num_freq_masks, _b16(memory))
 
-        # ---- decoder (model.py:519-531; transformers.py:543-583,660) ----
-        self._mark("memory ready")
-        self._cross_kv_fwd_all(memory, Nd, T, ddt)        # every layer's cross-attention K/V in one GEMM
-        self._mark("cross K/V fwd done")
+    def _fb_predictors_fwd(self, st) -> None:
+        """The three variance predictors (and the bucket sort the backward wants) on the side stream; joined before the losses."""
+        d, H, B, Pn, T, Tp, Nd = self.dims, self.dims.hidden, st.B, st.Pn, st.T, st.Tp, st.Nd
+        dur = st.batch["phoneme_durations"]
         # Forked only here, after the K/V GEMM: started earlier (right after im2col3) the predictors' fp32 GEMMs compete
         # with the critical path into the decoder; 2.8 % of the step (729K -> 749K frames/s).
         with self._on_side_stream():                      # joined before the losses
             self._mark("side: predictors fwd start")
-            if backward and self.embed_bwd_sorted and d.var_bins <= 1024:
+            if st.sort_buckets:
                 n_items = kk.load().kk_bucket_sort_items(Nd, d.var_bins)
-                be_order, be_items = self._buf("va.be_order", 2, Nd, dtype=torch.int32), self._buf("va.be_items", 2, n_items, 4, dtype=torch.int32)
-                kk.call("kk_bucket_sort", pidx, eidx, fmask, Nd, d.var_bins, be_order, be_items)
-            kk.call("kk_im2col3_fwd", enc, col_e, B, Pn, H, CHUNK, _b16(col_e))
+                st.be_order, st.be_items = (self._buf("va.be_order", 2, Nd, dtype=torch.int32),
+                                            self._buf("va.be_items", 2, n_items, 4, dtype=torch.int32))
+                kk.call("kk_bucket_sort", st.pidx, st.eidx, st.fmask, Nd, d.var_bins, st.be_order, st.be_items)
+            kk.call("kk_im2col3_fwd", st.enc, st.col_e, B, Pn, H, CHUNK, _b16(st.col_e))
             if Tp != T:
                 idx_p, lens_p = self._buf("lr.idx_p", B, Tp, dtype=torch.int64), self._buf("lr.lens_p", B, dtype=torch.int64)
                 kk.call("kk_length_regulate_index", dur, idx_p, lens_p, self._buf("lr.total_p", B, dtype=torch.int64), B, Pn, Tp)
-                kk.call("kk_length_regulate_gather", enc, idx_p, xf_p, B, Pn, Tp, H)
-                kk.call("kk_frame_mask", lens_p, fmask_p, B, Tp)
-            kk.call("kk_im2col3_fwd", xf_p, col_f, B, Tp, H, CHUNK, _b16(col_f))
-            self._varpred_fwd("vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, text_mask, dur_pred, 10, p_var)
-            self._varpred_fwd("vp.pitch", f"{VA}.pitch_predictor", xf_p, col_f, B, Tp, fmask_p, pitch_pred, 12, p_var)
-            self._varpred_fwd("vp.energy", f"{VA}.energy_predictor", xf_p, col_f, B, Tp, fmask_p, energy_pred, 14, p_var)
+                kk.call("kk_length_regulate_gather", st.enc, idx_p, st.xf_p, B, Pn, Tp, H)
+                kk.call("kk_frame_mask", lens_p, st.fmask_p, B, Tp)
+            kk.call("kk_im2col3_fwd", st.xf_p, st.col_f, B, Tp, H, CHUNK, _b16(st.col_f))
+            self._varpred_fwd("vp.dur", f"{VA}.duration_predictor", st.enc, st.col_e, B, Pn, st.text_mask, st.dur_pred, 10, st.p_var)
+            self._varpred_fwd("vp.pitch", f"{VA}.pitch_predictor", st.xf_p, st.col_f, B, Tp, st.fmask_p, st.pitch_pred, 12, st.p_var)
+            self._varpred_fwd("vp.energy", f"{VA}.energy_predictor", st.xf_p, st.col_f, B, Tp, st.fmask_p, st.energy_pred, 14, st.p_var)
             if Tp != T:
-                kk.call("kk_pad2d_f32", pitch_pred, Tp, Tp, pitch_l, T, T, B)
-                kk.call("kk_pad2d_f32", energy_pred, Tp, Tp, energy_l, T, T, B)
+                kk.call("kk_pad2d_f32", st.pitch_pred, Tp, Tp, st.pitch_l, T, T, B)
+                kk.call("kk_pad2d_f32", st.energy_pred, Tp, Tp, st.energy_l, T, T, B)
             self._mark("side: predictors fwd done")
-        n1 = None
+
+    def _fb_decoder_fwd(self, st) -> None:
+        """The decoder layers behind the head (cross-attention and feed-forward of layer 0, then layers 1 ...) and the two output heads."""
+        d, P, H, M, B, T, Nd = self.dims, self.arena.P, self.dims.hidden, self.dims.mel, st.B, st.T, st.Nd
+        self._join(self._kv)                             # input projection + layer-0 self-attention ran beside the encoder
+        y, ya, n2 = st.dec_head
         for i in range(d.dec_layers):
-            pf, key, st = f"decoder.layers.{i}", f"dec{i}", 2000 + 32 * i
-            dpr = self._dpr(i, d.dec_layers)
-            if i == 0:                                    # input projection + layer-0 self-attention ran beside the encoder
-                self._join(self._kv)
-                y, ya, n2 = dec_head
-            else:
-                if n1 is None:
-                    n1 = self._ln_fwd(key + ".ln1", y, pf + ".norm1", ddt)
-                ya, n2 = self_attn(i, y, n1)
-            yc = self._buf(key + ".xc", Nd, H)
-            n3 = self._attn_fwd(key + ".ca", pf + ".cross_attn", n2, memory, B, T, T, False, False, fmask, ya, yc, st + 8, p_dec, dpr,
-                                next_ln=(key + ".ln3", pf + ".norm3", ddt), layer=i)
-            if n3 is None:
-                n3 = self._ln_fwd(key + ".ln3", yc, pf + ".norm3", ddt)
-            yo = self._buf(key + ".xo", Nd, H)
-            nxt = ((f"dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", ddt) if i + 1 < d.dec_layers
-                   else ("dec.norm", "decoder.norm", ddt))
-            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, T, st + 16, p_dec, dpr, next_ln=nxt)
+            lay, dpr = self._dec_layer(i), self._dpr(i, d.dec_layers)
+            if i > 0:
+                ya, n2 = self._dec_self_attn_fwd(st, i, y, n1)
+            yc, yo = self._buf(lay.key + ".xc", Nd, H), self._buf(lay.key + ".xo", Nd, H)
+            n3 = self._attn_fwd(lay.key + ".ca", lay.prefix + ".cross_attn", n2, st.memory, B, T, T, False, False, st.fmask, ya, yc,
+                                lay.site["ca"], st.p_dec, dpr, next_ln=lay.next_ln["ca"], layer=i)
+            n1 = self._ffn_fwd(lay.key + ".ff", lay.prefix + ".ff", n3, yc, yo, d.dec_ff, T, lay.site["ff"], st.p_dec, dpr,
+                               next_ln=lay.next_ln["ff"])
             y = yo
             self._mark(f"dec{i} fwd done")
-        dec_last = y
-        dec_out = n1 if n1 is not None else self._ln_fwd("dec.norm", dec_last, "decoder.norm", ddt)
-        mel_pred, stop = self._buf("out.mel", B, T, M), self._buf("out.stop", B, T)
-        self._linear(dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], mel_pred.view(Nd, M))
-        kk.call("kk_rowdot_fwd", dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop, Nd, H, T, 0,
-                _b16(dec_out))
+        st.dec_last, st.dec_out = y, n1                   # (n1: decoder.norm of the last stream, from the last feed-forward's tail)
+        st.mel_pred, st.stop = self._buf("out.mel", B, T, M), self._buf("out.stop", B, T)
+        self._linear(st.dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], st.mel_pred.view(Nd, M))
+        kk.call("kk_rowdot_fwd", st.dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, st.stop, Nd, H, T, 0,
+                _b16(st.dec_out))
 
-        # ---- losses (losses.py) ----
+    def _fb_losses(self, st) -> Dict[str, torch.Tensor]:
+        """---- losses (losses.py) ----  Returns forward_backward's result."""
+        batch, B, T = st.batch, st.B, st.T
         self._join_side()
-        lcfg = kk.KkLossCfg(hp.duration_loss_weight, hp.stop_token_loss_weight, hp.pitch_loss_weight, hp.energy_loss_weight,
-                            hp.duration_huber_delta, hp.pitch_huber_delta, hp.energy_huber_delta, hp.stop_token_pos_weight,
-                            float(loss_scale), 1 if adaptive else 0)
-        largs = (mel_pred, mel, dur_pred, dur, stop, batch["stop_token_targets"], pitch_l, batch["pitches"], energy_l,
-                 batch["energies"], batch["mel_lengths"], batch["phoneme_lengths"], B, T, Pn, M, lcfg)
+        st.largs = (st.mel_pred, batch["mel_specs"], st.dur_pred, batch["phoneme_durations"], st.stop, batch["stop_token_targets"],
+                    st.pitch_l, batch["pitches"], st.energy_l, batch["energies"], batch["mel_lengths"], batch["phoneme_lengths"],
+                    B, T, st.Pn, self.dims.mel, st.lcfg)
         # per-micro-batch finite-output / finite-loss guard (trainer.py:3233-3296), device side: a flagged micro-batch
         # back-propagates nothing and its accumulation cycle takes no optimizer step; forward-only calls (validation) do
         # not touch the training cycle's flag
-        guard = self.opt_state[kk.OS["MICRO_BAD"]:] if backward else None
+        guard = self.opt_state[kk.OS["MICRO_BAD"]:] if st.backward else None
         # (loss_acc is handed round zero: allocated zero, cleared by its last reader — no zero-fill launch on the critical chain)
         sc = 1 if self.self_cleaning_acc else 0
-        kk.call("kk_losses_fwd", *largs, self.max_dur, self.loss_acc, self.losses, self.loss_coef,
+        kk.call("kk_losses_fwd", *st.largs, self.max_dur, self.loss_acc, self.losses, self.loss_coef,
                 guard if self.loss_sync is None else None, sc * (1 if self.loss_sync is not None else 3))
         if self.loss_sync is not None:                    # global normalisers for ragged shards (one more collective of the step)
             self.loss_sync.loss_sync(self.loss_acc, self.max_dur)
-            kk.call("kk_losses_finalize", self.loss_acc, lcfg, self.max_dur, canonical_mel_length(self.global_mel_length, T), self.losses,
+            kk.call("kk_losses_finalize", self.loss_acc, st.lcfg, self.max_dur, canonical_mel_length(self.global_mel_length, T), self.losses,
                     self.loss_coef, guard, sc)
-        out = {"losses": self.losses, "mel": mel_pred, "log_dur": dur_pred, "stop": stop, "pitch": pitch_pred,
-               "energy": energy_pred, "lr_idx": idx, "lr_lens": lens, "memory": memory.view(B, T, H)}
-        if not backward:
-            return out
+        return {"losses": self.losses, "mel": st.mel_pred, "log_dur": st.dur_pred, "stop": st.stop, "pitch": st.pitch_pred,
+                "energy": st.energy_pred, "lr_idx": st.idx, "lr_lens": st.lens, "memory": st.memory.view(B, T, self.dims.hidden)}
 
-        # =========================== backward ===========================
+    def _fb_loss_grads(self, st) -> None:
+        """The backward's book-keeping and the loss gradients; st.fork = the point the side backward forks from."""
+        B, T = st.B, st.T
         self._ss_ready = None
         if self.grad_norm_from_wgrads and self.dp_comm is None and not self._external_sync and self.group_wgrads:
             self._ss_step = dict(rec=kk.C.c_void_p(self.sumsq_ws.data_ptr() + int(kk.load().kk_seg_sumsq_rec_offset())), count=kk.C.c_int32(0),
@@ -1469,159 +1590,158 @@ class KokoroEngine:
         if self.dp_comm is not None and self._exchange_now:
             self.dp_comm.begin_step()
             self._comm_events = {}
-        dmel, ddur = self._buf("g.mel", B, T, M), self._buf("g.dur", B, Pn)
-        dstop, dpitch, denergy = self._buf("g.stop", B, T), self._buf("g.pitch", B, T), self._buf("g.energy", B, T)
-        kk.call("kk_losses_bwd", *largs, self.loss_coef, dmel, ddur, dstop, dpitch, denergy)
+        st.dmel, st.ddur = self._buf("g.mel", B, T, self.dims.mel), self._buf("g.dur", B, st.Pn)
+        st.dstop, st.dpitch, st.denergy = self._buf("g.stop", B, T), self._buf("g.pitch", B, T), self._buf("g.energy", B, T)
+        kk.call("kk_losses_bwd", *st.largs, self.loss_coef, st.dmel, st.ddur, st.dstop, st.dpitch, st.denergy)
         self._mark("losses + loss gradients done")
-        fork = self._fork_point()
+        st.fork = self._fork_point()
 
-        def heads_and_frame_predictors():
-            # the output heads' weight gradients have no consumer on the decoder chain (the stop head's input is
-            # detached, model.py:561-562): 50 us off the critical path
-            kk.call("kk_rowdot_bwd", dstop, dec_out, P["stop_token_predictor.weight"], None, None, G["stop_token_predictor.weight"],
-                    G["stop_token_predictor.bias"], Nd, H, T, 0, _b16(dec_out),
-                    self._rowdot_partials("stop", Nd, H, G["stop_token_predictor.weight"], G["stop_token_predictor.bias"]))
-            self._wgrad(dmel.view(Nd, M), dec_out, G["mel_projection_out.weight"], G["mel_projection_out.bias"])
-            dpitch_p, denergy_p = dpitch, denergy
-            if Tp != T:                               # frames past T carry no loss: zero gradient there
-                dpitch_p, denergy_p = self._buf("g.pitch_p", B, Tp), self._buf("g.energy_p", B, Tp)
-                kk.call("kk_pad2d_f32", dpitch, T, T, dpitch_p, Tp, Tp, B)
-                kk.call("kk_pad2d_f32", denergy, T, T, denergy_p, Tp, Tp, B)
-            self._varpred_bwd("vp.pitch", f"{VA}.pitch_predictor", dpitch_p, xf_p, col_f, B, Tp, fmask_p, None, p_var)
-            self._varpred_bwd("vp.energy", f"{VA}.energy_predictor", denergy_p, xf_p, col_f, B, Tp, fmask_p, None, p_var)
+    def _enc_bwd_head(self, st, i, sub):
+        """_tail_bwd's `head` for sub-layer `sub` of encoder layer i (every LayerNorm's backward is fused with the head of the
+        backward of the sub-layer that produced its input): (kind, ffn buffer key, parameter prefix, S, site, p, drop-path, dtype)."""
+        lay = self._enc_layer(i)
+        return ("ffn" if sub == "ff" else "attn", lay.key + ".ff", lay.prefix + _SUBLAYER[sub], st.Pn, lay.site[sub], st.p_enc,
+                self._dpr(i, self.dims.enc_layers), self.enc_dt)
 
-        def side_backward(after):                         # independent of the decoder backward (disjoint gradient segments)
-            with self._on_side_stream(after=after):
-                self._mark("side: backward start")
-                heads_and_frame_predictors()
-                d_enc = self._buf("g.enc_out", Ne, H)
-                self._varpred_bwd("vp.dur", f"{VA}.duration_predictor", ddur, enc, col_e, B, Pn, text_mask, d_enc, p_var)
-                self._mark("side: predictors bwd done")
-                dx = self._buf("g.enc_stream", Ne, H)
-                # every LayerNorm's backward is fused with the head of the backward of the sub-layer that produced its input
-                ehead = lambda kind, i: (kind, f"enc{i}.ff", f"transformer_encoder_layers.{i}" + (".ff" if kind == "ffn" else ".self_attn"),
-                                         Pn, 1000 + 32 * i + (8 if kind == "ffn" else 0), p_enc, self._dpr(i, d.enc_layers), edt)
-                self._tail_bwd("enc.norm", d_enc, enc_last, "encoder_norm", dx, False, ehead("ffn", d.enc_layers - 1))
-                dne = self._buf("tmp.dne", Ne, H, dtype=edt)
-                for i in reversed(range(d.enc_layers)):
-                    pf, key, st = f"transformer_encoder_layers.{i}", f"enc{i}", 1000 + 32 * i
-                    dpr = self._dpr(i, d.enc_layers)
-                    x_in = self._buf(f"enc{i - 1}.xo", Ne, H) if i > 0 else self._buf("enc.x0", Ne, H)
-                    xm = self._buf(key + ".xm", Ne, H)
-                    y1, y2 = self._buf(key + ".ln1.y", Ne, H, dtype=edt), self._buf(key + ".ln2.y", Ne, H, dtype=edt)
-                    with self._grouped_wgrads():
-                        self._ffn_bwd(key + ".ff", pf + ".ff", dx, y2, dne, d.enc_ff, Pn, st + 8, p_enc, dpr)
-                        self._tail_bwd(key + ".ln2", dne, xm, pf + ".norm2", dx, True, ehead("attn", i))
-                        self._attn_bwd(key + ".sa", pf + ".self_attn", dx, y1, None, B, Pn, Pn, True, False, text_mask, dne, None, 0.0,
-                                       st, p_enc, dpr)
-                    self._comm_bucket(f"enc{i}")            # (the grouped weight-gradient launch is behind us)
-                    if i > 0:
-                        self._tail_bwd(key + ".ln1", dne, x_in, pf + ".norm1", dx, True, ehead("ffn", i - 1))
-                    else:
-                        self._ln_bwd(key + ".ln1", dne, x_in, pf + ".norm1", dx, accumulate=True)
-                    self._mark(f"side: enc{i} bwd done")
-                kk.call("kk_embed_bwd", ids, stress, dx, G["text_embedding.weight"],
-                        G["stress_embedding.weight"] if stress is not None else None, B, Pn, H, float(H ** 0.5), self.rng, 1, pe_drop)
-                self._mark("side: backward done")
-                if tail_mode in (3, 4):                   # the memory tail behind the encoder's backward (no third branch)
-                    torch.cuda.current_stream().wait_event(tail_fork)
-                    memory_tail()
-                    if deferred0:
-                        torch.cuda.current_stream().wait_event(wgrad0_fork)
-                        for q in deferred0:
-                            self._issue_wgrad_group(q)
+    def _dec_bwd_head(self, st, i, sub):
+        """The same for sub-layer `sub` of decoder layer i."""
+        lay = self._dec_layer(i)
+        return ("ffn" if sub == "ff" else "attn", lay.key + ".ff", lay.prefix + _SUBLAYER[sub], st.T, lay.site[sub], st.p_dec,
+                self._dpr(i, self.dims.dec_layers), self.dec_dt)
 
-        # The decoder backward is the critical path, so it is captured first and the predictors' + encoder's backward
-        # after it, forked from the point right after the loss gradients (see _on_stream).
+    def _fb_decoder_bwd(self, st) -> None:
+        """The mel head's input gradient and the decoder layers, last to first, on the main chain.  Leaves st.tail_fork where the
+        memory tail may start, and layer 0's grouped weight gradients in st.deferred0 (behind st.wgrad0_fork) when they wait."""
+        d, H, M, ddt, B, T, Nd = self.dims, self.dims.hidden, self.dims.mel, self.dec_dt, st.B, st.T, st.Nd
         # heads: only the mel projection's input gradient continues down the decoder (the two heads' weight gradients are
-        # on the side branch, see side_backward)
+        # on the side branch, see _fb_side_bwd)
         d_dec_out = self._buf("tmp.d_dec_out", Nd, H, dtype=ddt)
-        self._dgrad(dmel.view(Nd, M), self._W("mel_projection_out.weight"), d_dec_out)
-        dy = self._buf("g.dec_stream", Nd, H)          # gradient of the decoder residual stream, updated in place
-        def dhead(kind, i):                            # (kind, ffn buffer key, parameter prefix, S, site, p, drop-path, dtype)
-            sub = {"ffn": (".ff", 16), "ca": (".cross_attn", 8), "sa": (".self_attn", 0)}[kind]
-            return ("ffn" if kind == "ffn" else "attn", f"dec{i}.ff", f"decoder.layers.{i}" + sub[0], T, 2000 + 32 * i + sub[1],
-                    p_dec, self._dpr(i, d.dec_layers), ddt)
-        self._tail_bwd("dec.norm", d_dec_out, dec_last, "decoder.norm", dy, False, dhead("ffn", d.dec_layers - 1))
-        dmem = self._buf("g.memory", Nd, H)
-        tail_mode = (4 if Nd <= 4096 else 3) if self.tail_aside < 0 else self.tail_aside
-        tail_mode = tail_mode if self.overlap else 0
-        deferred0 = []
+        self._dgrad(st.dmel.view(Nd, M), self._W("mel_projection_out.weight"), d_dec_out)
+        st.dy = dy = self._buf("g.dec_stream", Nd, H)          # gradient of the decoder residual stream, updated in place
+        self._tail_bwd("dec.norm", d_dec_out, st.dec_last, "decoder.norm", dy, False, self._dec_bwd_head(st, d.dec_layers - 1, "ff"))
+        st.dmem = dmem = self._buf("g.memory", Nd, H)
         dn = self._buf("tmp.dn", Nd, H, dtype=ddt)
         for i in reversed(range(d.dec_layers)):
-            pf, key, st = f"decoder.layers.{i}", f"dec{i}", 2000 + 32 * i
-            dpr = self._dpr(i, d.dec_layers)
+            lay, dpr = self._dec_layer(i), self._dpr(i, d.dec_layers)
+            pf, key = lay.prefix, lay.key
             x_in = self._buf(f"dec{i - 1}.xo", Nd, H) if i > 0 else self._buf("dec.x0", Nd, H)
             ya, yc = self._buf(key + ".xa", Nd, H), self._buf(key + ".xc", Nd, H)
             n1, n2, n3 = (self._buf(f"{key}.ln{j}.y", Nd, H, dtype=ddt) for j in (1, 2, 3))
             # layer 0's grouped weight gradients: nothing on the main chain overwrites their operands any more (the layer-norm backward and
             # the input projection below use their own buffers), so the launch can wait for the side stream's idle end (wgrad0_aside)
-            defer0 = i == 0 and tail_mode in (3, 4) and self.group_wgrads and self.dp_comm is None and \
-                (self.wgrad0_aside > 0 or (self.wgrad0_aside < 0 and tail_mode == 3))
+            defer0 = i == 0 and st.tail_mode in (3, 4) and self.group_wgrads and self.dp_comm is None and \
+                (self.wgrad0_aside > 0 or (self.wgrad0_aside < 0 and st.tail_mode == 3))
             if defer0:
-                self._defer_wgrads = deferred0 = []           # (reset by _fb whatever happens in between)
+                self._defer_wgrads = st.deferred0           # (reset by _fb whatever happens in between)
             with self._grouped_wgrads():
-                self._ffn_bwd(key + ".ff", pf + ".ff", dy, n3, dn, d.dec_ff, T, st + 16, p_dec, dpr)
-                self._tail_bwd(key + ".ln3", dn, yc, pf + ".norm3", dy, True, dhead("ca", i))
-                self._attn_bwd(key + ".ca", pf + ".cross_attn", dy, n2, memory, B, T, T, False, False, fmask, dn, dmem,
-                               0.0, st + 8, p_dec, dpr, layer=i)
-                if i == 0 and tail_mode in (1, 3, 4):  # every layer's cross-attention dK / dV is written: the memory tail may start
-                    tail_fork = self._fork_point()
-                    if tail_mode == 4:            # (4: the K/V weight gradient as one more member of layer 0's grouped launch)
-                        self._cross_kv_bwd_all(memory, Nd, ddt, dmem, dgrad=False)
-                self._tail_bwd(key + ".ln2", dn, ya, pf + ".norm2", dy, True, dhead("sa", i))
-                self._attn_bwd(key + ".sa", pf + ".self_attn", dy, n1, None, B, T, T, True, True, None, dn, None, 0.0, st, p_dec, dpr)
+                self._ffn_bwd(key + ".ff", pf + ".ff", dy, n3, dn, d.dec_ff, T, lay.site["ff"], st.p_dec, dpr)
+                self._tail_bwd(key + ".ln3", dn, yc, pf + ".norm3", dy, True, self._dec_bwd_head(st, i, "ca"))
+                self._attn_bwd(key + ".ca", pf + ".cross_attn", dy, n2, st.memory, B, T, T, False, False, st.fmask, dn, dmem,
+                               0.0, lay.site["ca"], st.p_dec, dpr, layer=i)
+                if i == 0 and st.tail_mode in (1, 3, 4):  # every layer's cross-attention dK / dV is written: the memory tail may start
+                    st.tail_fork = self._fork_point()
+                    if st.tail_mode == 4:            # (4: the K/V weight gradient as one more member of layer 0's grouped launch)
+                        self._cross_kv_bwd_all(st.memory, Nd, ddt, dmem, dgrad=False)
+                self._tail_bwd(key + ".ln2", dn, ya, pf + ".norm2", dy, True, self._dec_bwd_head(st, i, "sa"))
+                self._attn_bwd(key + ".sa", pf + ".self_attn", dy, n1, None, B, T, T, True, True, None, dn, None, 0.0, lay.site["sa"],
+                               st.p_dec, dpr)
             if defer0:
                 self._defer_wgrads = None
-                wgrad0_fork = self._fork_point()
+                st.wgrad0_fork = self._fork_point()
             self._comm_bucket(f"dec{i}")                    # the layer's weight matrices are final: exchange beside the rest
             if i > 0:
-                self._tail_bwd(key + ".ln1", dn, x_in, pf + ".norm1", dy, True, dhead("ffn", i - 1))
+                self._tail_bwd(key + ".ln1", dn, x_in, pf + ".norm1", dy, True, self._dec_bwd_head(st, i - 1, "ff"))
             else:
                 self._ln_bwd(key + ".ln1", dn, x_in, pf + ".norm1", dy, accumulate=True)
             self._mark(f"dec{i} bwd done")
-        def input_projection_bwd():                    # (the PE add and the shift are parameter-free; mel is data)
-            if self.train_dropout and (p_din > 0.0 or pe_drop > 0.0):
-                t1, dlin = self._buf("tmp.d_dec_t1", Nd, H), self._buf("tmp.d_dec_lin", Nd, H)
-                kk.call("kk_dropout_bwd", dy, t1, Nd, H, T, self.rng, 31, pe_drop, 0, 0.0, 0, 0.0, 0)
-                kk.call("kk_dropout_bwd", t1, dlin, Nd, H, T, self.rng, 30, p_din, 0, 0.0, 0, 0.0, 0)
-                self._wgrad(dlin, shifted, G["mel_projection_in.weight"], G["mel_projection_in.bias"])
-            else:
-                self._wgrad(dy, shifted, G["mel_projection_in.weight"], G["mel_projection_in.bias"])
-            self._mark("decoder input projection bwd done")
 
-        def memory_tail():
-            # variance adaptor: memory gradient feeds only the two embedding tables (xf is detached, lengths.py:30)
-            self._cross_kv_bwd_all(memory, Nd, ddt, dmem, wgrad=tail_mode != 4)   # K/V weight gradients and the memory gradient, all layers at once
-            self._mark("cross K/V bwd (all layers) done")
-            if spec_aug:
-                kk.call("kk_specaug", dmem, B, T, H, self.rng, 20, hp.spec_augment_time_mask_max, hp.spec_augment_freq_mask_max,
-                        hp.spec_augment_num_time_masks, hp.spec_augment_num_freq_masks, 0)
-            if self.embed_bwd_sorted and d.var_bins <= 1024:
-                kk.call("kk_bucket_embed_add_bwd_sorted", dmem, be_order, be_items, G[f"{VA}.pitch_embedding.weight"],
-                        G[f"{VA}.energy_embedding.weight"], Nd, H, d.var_bins)
-            else:
-                kk.call("kk_bucket_embed_add_bwd", dmem, pidx, eidx, fmask, G[f"{VA}.pitch_embedding.weight"],
-                        G[f"{VA}.energy_embedding.weight"], B, T, H, d.var_bins)
-
-        if tail_mode:
-            # the memory tail needs the cross-attention dK / dV of all layers and nothing else of the decoder backward: it runs on the
-            # third stream beside layer 0's self-attention backward (1) or beside the input projection's backward (2), or on the side
-            # stream behind the encoder's backward (3)
-            if tail_mode == 2:
-                tail_fork = self._fork_point()
-            input_projection_bwd()
-            if tail_mode not in (3, 4):
-                with self._on_stream(self._kv, "kv.", after=tail_fork):
-                    memory_tail()
-                self._join(self._kv)
+    def _fb_input_projection_bwd(self, st) -> None:
+        """(the PE add and the shift are parameter-free; mel is data)"""
+        G, H, T, Nd = self.arena.G, self.dims.hidden, st.T, st.Nd
+        if self.train_dropout and (st.p_din > 0.0 or st.pe_drop > 0.0):
+            t1, dlin = self._buf("tmp.d_dec_t1", Nd, H), self._buf("tmp.d_dec_lin", Nd, H)
+            kk.call("kk_dropout_bwd", st.dy, t1, Nd, H, T, self.rng, 31, st.pe_drop, 0, 0.0, 0, 0.0, 0)
+            kk.call("kk_dropout_bwd", t1, dlin, Nd, H, T, self.rng, 30, st.p_din, 0, 0.0, 0, 0.0, 0)
+            self._wgrad(dlin, st.shifted, G["mel_projection_in.weight"], G["mel_projection_in.bias"])
         else:
-            input_projection_bwd()
-            memory_tail()
-        self._mark("main: backward tail done")
-        side_backward(fork)
+            self._wgrad(st.dy, st.shifted, G["mel_projection_in.weight"], G["mel_projection_in.bias"])
+        self._mark("decoder input projection bwd done")
+
+    def _fb_memory_tail(self, st) -> None:
+        """variance adaptor: memory gradient feeds only the two embedding tables (xf is detached, lengths.py:30)"""
+        d, G, hp, H, B, T, Nd = self.dims, self.arena.G, self.hp, self.dims.hidden, st.B, st.T, st.Nd
+        self._cross_kv_bwd_all(st.memory, Nd, self.dec_dt, st.dmem, wgrad=st.tail_mode != 4)   # K/V weight gradients and the memory gradient, all layers at once
+        self._mark("cross K/V bwd (all layers) done")
+        if st.spec_aug:
+            kk.call("kk_specaug", st.dmem, B, T, H, self.rng, 20, hp.spec_augment_time_mask_max, hp.spec_augment_freq_mask_max,
+                    hp.spec_augment_num_time_masks, hp.spec_augment_num_freq_masks, 0)
+        if st.sort_buckets:
+            kk.call("kk_bucket_embed_add_bwd_sorted", st.dmem, st.be_order, st.be_items, G[f"{VA}.pitch_embedding.weight"],
+                    G[f"{VA}.energy_embedding.weight"], Nd, H, d.var_bins)
+        else:
+            kk.call("kk_bucket_embed_add_bwd", st.dmem, st.pidx, st.eidx, st.fmask, G[f"{VA}.pitch_embedding.weight"],
+                    G[f"{VA}.energy_embedding.weight"], B, T, H, d.var_bins)
+
+    def _fb_side_bwd(self, st) -> None:
+        """On the side stream, forked from st.fork: the output heads' weight gradients, the three predictors, the text encoder and
+        the embedding — independent of the decoder backward (disjoint gradient segments) — and, in tail modes 3 / 4, the memory
+        tail and decoder layer 0's deferred weight gradients behind them."""
+        d, P, G, H, M, edt = self.dims, self.arena.P, self.arena.G, self.dims.hidden, self.dims.mel, self.enc_dt
+        B, Pn, T, Tp, Ne, Nd = st.B, st.Pn, st.T, st.Tp, st.Ne, st.Nd
+        ids, stress = st.batch["phoneme_indices"], st.batch.get("stress_indices")
+        with self._on_side_stream(after=st.fork):
+            self._mark("side: backward start")
+            # the output heads' weight gradients have no consumer on the decoder chain (the stop head's input is
+            # detached, model.py:561-562): 50 us off the critical path
+            kk.call("kk_rowdot_bwd", st.dstop, st.dec_out, P["stop_token_predictor.weight"], None, None, G["stop_token_predictor.weight"],
+                    G["stop_token_predictor.bias"], Nd, H, T, 0, _b16(st.dec_out),
+                    self._rowdot_partials("stop", Nd, H, G["stop_token_predictor.weight"], G["stop_token_predictor.bias"]))
+            self._wgrad(st.dmel.view(Nd, M), st.dec_out, G["mel_projection_out.weight"], G["mel_projection_out.bias"])
+            dpitch_p, denergy_p = st.dpitch, st.denergy
+            if Tp != T:                               # frames past T carry no loss: zero gradient there
+                dpitch_p, denergy_p = self._buf("g.pitch_p", B, Tp), self._buf("g.energy_p", B, Tp)
+                kk.call("kk_pad2d_f32", st.dpitch, T, T, dpitch_p, Tp, Tp, B)
+                kk.call("kk_pad2d_f32", st.denergy, T, T, denergy_p, Tp, Tp, B)
+            self._varpred_bwd("vp.pitch", f"{VA}.pitch_predictor", dpitch_p, st.xf_p, st.col_f, B, Tp, st.fmask_p, None, st.p_var)
+            self._varpred_bwd("vp.energy", f"{VA}.energy_predictor", denergy_p, st.xf_p, st.col_f, B, Tp, st.fmask_p, None, st.p_var)
+            d_enc = self._buf("g.enc_out", Ne, H)
+            self._varpred_bwd("vp.dur", f"{VA}.duration_predictor", st.ddur, st.enc, st.col_e, B, Pn, st.text_mask, d_enc, st.p_var)
+            self._mark("side: predictors bwd done")
+            dx = self._buf("g.enc_stream", Ne, H)
+            self._tail_bwd("enc.norm", d_enc, st.enc_last, "encoder_norm", dx, False, self._enc_bwd_head(st, d.enc_layers - 1, "ff"))
+            dne = self._buf("tmp.dne", Ne, H, dtype=edt)
+            for i in reversed(range(d.enc_layers)):
+                lay, dpr = self._enc_layer(i), self._dpr(i, d.enc_layers)
+                pf, key = lay.prefix, lay.key
+                x_in = self._buf(f"enc{i - 1}.xo", Ne, H) if i > 0 else self._buf("enc.x0", Ne, H)
+                xm = self._buf(key + ".xm", Ne, H)
+                y1, y2 = self._buf(key + ".ln1.y", Ne, H, dtype=edt), self._buf(key + ".ln2.y", Ne, H, dtype=edt)
+                with self._grouped_wgrads():
+                    self._ffn_bwd(key + ".ff", pf + ".ff", dx, y2, dne, d.enc_ff, Pn, lay.site["ff"], st.p_enc, dpr)
+                    self._tail_bwd(key + ".ln2", dne, xm, pf + ".norm2", dx, True, self._enc_bwd_head(st, i, "sa"))
+                    self._attn_bwd(key + ".sa", pf + ".self_attn", dx, y1, None, B, Pn, Pn, True, False, st.text_mask, dne, None, 0.0,
+                                   lay.site["sa"], st.p_enc, dpr)
+                self._comm_bucket(f"enc{i}")            # (the grouped weight-gradient launch is behind us)
+                if i > 0:
+                    self._tail_bwd(key + ".ln1", dne, x_in, pf + ".norm1", dx, True, self._enc_bwd_head(st, i - 1, "ff"))
+                else:
+                    self._ln_bwd(key + ".ln1", dne, x_in, pf + ".norm1", dx, accumulate=True)
+                self._mark(f"side: enc{i} bwd done")
+            kk.call("kk_embed_bwd", ids, stress, dx, G["text_embedding.weight"],
+                    G["stress_embedding.weight"] if stress is not None else None, B, Pn, H, float(H ** 0.5), self.rng, 1, st.pe_drop)
+            self._mark("side: backward done")
+            if st.tail_mode in (3, 4):                   # the memory tail behind the encoder's backward (no third branch)
+                torch.cuda.current_stream().wait_event(st.tail_fork)
+                self._fb_memory_tail(st)
+                if st.deferred0:
+                    torch.cuda.current_stream().wait_event(st.wgrad0_fork)
+                    for q in st.deferred0:
+                        self._issue_wgrad_group(q)
+
+    def _fb_finish(self, st) -> None:
+        """Join the branches, reduce the partial sums, hand the tail bucket to the exchange, close the step's records."""
         self._join(self._side)
-        self._reduce_partials((B, T, Pn, Tp))
+        self._reduce_partials((st.B, st.T, st.Pn, st.Tp))
         self._comm_bucket("tail")                       # everything that was not a layer's weight matrix
         self._comm_join()
         self._mark("backward joined, partials reduced")
@@ -1636,7 +1756,6 @@ class KokoroEngine:
                                    f"{len(self._ow_expect - seen)} tensors were skipped but not overwritten")
             self._ow_sets[self._ow_key()] = seen
             self._ow_seen = None
-        return out
 
     # ------------------------------------------------------------------ inference
     def _decoder_step(self, ns, rows, pe_res, res_mod, cos, sin, S, split_k, self_attn, cross_attn):
@@ -1654,7 +1773,8 @@ class KokoroEngine:
         n1 = self._ln_fwd(f"{ns}.dec0.ln1", y, "decoder.layers.0.norm1", ddt)
         yl = y
         for i in range(d.dec_layers):
-            pf, key = f"decoder.layers.{i}", f"{ns}.dec{i}"
+            lay = self._dec_layer(i, ns + ".")
+            pf, key = lay.prefix, lay.key
             sp, cp = pf + ".self_attn", pf + ".cross_attn"
             raw, nrm = self._buf(key + ".qkv_raw", rows, 3 * H, dtype=ddt), self._buf(key + ".qkv_n", rows, 3 * H, dtype=ddt)
             # K alone is rotated, by the row's absolute position; the single query by position 0, i.e. not at all (generate)
@@ -1664,17 +1784,15 @@ class KokoroEngine:
             proj = self._buf("str.proj" if ns == "str" else f"tmp.{ns}_proj", rows, H)
             self._linear(ctx, self._W(sp + ".w_o.weight"), P[sp + ".w_o.bias"], proj, split_k=split_k)
             ya = self._buf(key + ".xa", rows, H)
-            n2 = self._sublayer_tail(proj, yl, ya, 1, 0, 0.0, 0.0, 0.0, None, None, (key + ".ln2", pf + ".norm2", ddt))
+            n2 = self._sublayer_tail(proj, yl, ya, 1, 0, 0.0, 0.0, 0.0, None, None, lay.next_ln["sa"])
             # cross-attention: _attn_fwd's launches without dropout, with the caller's attention kernel
             q_raw, q_n = self._buf(key + ".ca.q_raw", rows, H, dtype=ddt), self._buf(key + ".ca.q_n", rows, H, dtype=ddt)
             self._proj_headnorm(n2, self._W(cp + ".w_q.weight"), q_raw, q_n, 1, (P[cp + ".q_norm.weight"],), 0, None, None, split_k=split_k)
             ctx = cross_attn(i, key, q_n)
             yc = self._buf(key + ".xc", rows, H)
-            n3 = self._attn_out(key + ".ca", cp, ctx, rows, 1, ya, yc, 0, 0.0, 0.0, (key + ".ln3", pf + ".norm3", ddt), split_k=split_k)
+            n3 = self._attn_out(key + ".ca", cp, ctx, rows, 1, ya, yc, 0, 0.0, 0.0, lay.next_ln["ca"], split_k=split_k)
             yo = self._buf(key + ".xo", rows, H)
-            nxt = ((f"{ns}.dec{i + 1}.ln1", f"decoder.layers.{i + 1}.norm1", ddt) if i + 1 < d.dec_layers
-                   else (f"{ns}.dec.norm", "decoder.norm", ddt))
-            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=nxt, split_k=split_k)
+            n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=lay.next_ln["ff"], split_k=split_k)
             yl = yo
         self._linear(n1, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out, split_k=split_k)
         kk.call("kk_rowdot_fwd", n1, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now, rows, H, 1, 0, _b16(n1))
@@ -1721,20 +1839,9 @@ class KokoroEngine:
         x = self._buf(ns + "enc.x0", Ne, H)
         kk.call("kk_embed_fwd", ids, stress, P["text_embedding.weight"], P["stress_embedding.weight"] if stress is not None else None,
                 P["positional_encoding.pe"].view(d.max_len, H), x, B, Pn, H, float(H ** 0.5), self.rng, 1, 0.0)
-        y1 = None
-        for i in range(d.enc_layers):
-            pf, key = f"transformer_encoder_layers.{i}", f"{ns}enc{i}"
-            if y1 is None:
-                y1 = self._ln_fwd(key + ".ln1", x, pf + ".norm1", edt)
-            xm = self._buf(key + ".xm", Ne, H)
-            y2 = self._attn_fwd(key + ".sa", pf + ".self_attn", y1, None, B, Pn, Pn, True, False, text_mask, x, xm,
-                                next_ln=(key + ".ln2", pf + ".norm2", edt))
-            xo = self._buf(key + ".xo", Ne, H)
-            nxt = ((f"{ns}enc{i + 1}.ln1", f"transformer_encoder_layers.{i + 1}.norm1", edt) if i + 1 < d.enc_layers
-                   else (ns + "enc.norm", "encoder_norm", torch.float32))
-            y1 = self._ffn_fwd(key + ".ff", pf + ".ff", y2, xm, xo, d.enc_ff, Pn, next_ln=nxt)
-            x = xo
-        return y1
+        lay0 = self._enc_layer(0, ns)
+        y1 = self._ln_fwd(lay0.key + ".ln1", x, lay0.prefix + ".norm1", edt)
+        return self._encoder_layers_fwd(ns, 0, x, y1, B, Pn, text_mask)[1]
 
     def _expand_fwd(self, ns, enc, dur, B, Pn, T, flens=None, controls=None):
         """The variance adaptor behind the durations, without targets (variance_predictor.py:338-439): repeat phoneme p of
