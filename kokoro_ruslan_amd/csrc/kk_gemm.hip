@@ -307,6 +307,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
 
 template <bool BF16, int TM, bool A16, bool B16>
 int launch2(int ta, int tb, const GemmArgs &a, dim3 grid, hipStream_t s) {
+    kk_note_kernelf("gemm<%d,%d,%d,%d,%d,%d>", ta, tb, (int)BF16, TM, (int)A16, (int)B16);
     if (!ta && !tb) hipLaunchKernelGGL((gemm_kernel<false, false, BF16, TM, A16, B16>), grid, dim3(256), 0, s, a);
     else if (!ta && tb) hipLaunchKernelGGL((gemm_kernel<false, true, BF16, TM, A16, B16>), grid, dim3(256), 0, s, a);
     else if (ta && !tb) hipLaunchKernelGGL((gemm_kernel<true, false, BF16, TM, A16, B16>), grid, dim3(256), 0, s, a);
