@@ -865,6 +865,27 @@ int kk_cast_bf16_f32(const void *x, float *y, int64_t n, float scale, void *stre
 int kk_cast_ranges(const void *src, void *dst, const int64_t *begin, const int64_t *end, int n, int to_bf16, float scale,
                    void *stream);
 
+/* ---- long-form synthesis: finish a batch of mels, join chunk waveforms per document (kokoro_ruslan_amd/longform.py; kk_longform.hip) ----
+ * Both work on rows packed back to back and compute nothing of a row that depends on the rest of the launch; the definitions are
+ * restated in fp64 in kokoro_ruslan_amd/longform_torch.py. */
+/* mel: fp32 [frames][n_mels], moff: int64 [B + 1] frame offsets (moff[B] <= frames), 1 <= T_b <= 4096, 1 <= n_mels <= 128; one
+ * workgroup per mel.  out (same layout, out != mel) = clamp(mel, lo, hi), a NaN kept.  With m_t the fp32 mean of clamped frame t
+ * (a fixed order over the channels), q10 and q20 the 0.1 and 0.2 quantiles of m by torch.quantile's linear definition: thr =
+ * max(thr_lo, min(thr_hi, (q10 + q20) / 2)), or thr_hi when the mel holds a NaN; last_voiced = the last t with m_t > thr, or -1;
+ * t_end = min(T, max(min_keep, min(T, last_voiced + margin + 1))), or T when last_voiced = -1.  ends: int32 [B][2] = {t_end,
+ * last_voiced}; stats: double [B][6] = {thr, min, max, mean, unbiased std, NaN count} of the UNCLAMPED mel: min and max over the
+ * values that are not NaN (+inf / -inf when there is none), mean and std by fp64 sums in a fixed order, the deviations in a second
+ * pass about the mean (NaN when the mel holds one). */
+int kk_mel_finish(const float *mel, const int64_t *moff, int B, int64_t frames, int n_mels, float lo, float hi, double thr_lo,
+                  double thr_hi, int margin, int min_keep, float *out, int *ends, double *stats, void *stream);
+/* wave: fp32 chunks packed back to back, woff: int64 [C + 1], every chunk >= 1 sample; dst: int64 [C] ascending, the first output sample
+ * of every chunk, dst[c] + n_c <= dst[c + 1] and <= total.  Every out[i], i < total, is written: chunk c's sample i - dst[c] where that
+ * is < n_c, zero otherwise.  The first and last min(F, n_c / 2) samples of a chunk are multiplied by fade[j] and fade[n_c - 1 - j]
+ * (fade: fp32 [F], may be NULL when F = 0: a plain copy).  peak: fp32 [C] = max |x| of every chunk before the fade (NaN when the chunk
+ * holds one).  wave and out 16-byte aligned, out != wave, total < 2^31. */
+int kk_wave_join(const float *wave, const int64_t *woff, const int64_t *dst, int C, const float *fade, int F, int64_t total, float *out,
+                 float *peak, void *stream);
+
 /* ---- misc ---- */
 /* *slot = device wall clock (100 MHz ticks) at the time this launch executes: in-graph time stamps for timelines. */
 int kk_timestamp(uint64_t *slot, void *stream);

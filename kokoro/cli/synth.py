@@ -7,6 +7,7 @@
                  [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]]
                  [--loudness [LUFS] [--peak-db DB]]
                  [--speed F] [--pitch-scale F] [--pitch-shift F] [--energy-scale F] [--energy-shift F]
+                 [--documents [--gap-ms F] [--fade-ms F]] [--report FILE.json]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
 --features reads phoneme_indices / stress_indices from a precomputed feature cache (kokoro.data.cached); --ids reads JSON lines
@@ -26,7 +27,17 @@ written; the .wav then keeps that level instead of being peak-normalised.  A wav
 --speed / --pitch-scale / --pitch-shift / --energy-scale / --energy-shift steer every utterance (kokoro_ruslan_amd.prosody.Prosody:
 frames per phoneme divided by the speed, in [0.25, 4]; scale and shift on the normalised pitch of voiced frames and on the normalised
 energy).  A line of --ids may carry "prosody": {...} with the fields of Prosody.from_json (also per-phoneme lists and forced
-"durations" / "pitch" / "energy"); its fields override the flags for that line."""
+"durations" / "pitch" / "energy"); its fields override the flags for that line.
+--documents (with --ids and --vocoder or --griffin-lim) is long-form synthesis, the last stretch of the reference's text_to_speech
+(:566-648): a line of --ids may carry "document": "NAME"; the lines of one document are its chunks, played in file order, and a line
+without the field is a document of its own named by its "name".  All chunks of all documents are synthesized in the one call, every mel
+is health-checked, clamped and trimmed of its trailing silence on the device (kokoro_ruslan_amd.longform; <name>.npy is the finished
+mel), vocoded (and denoised) per chunk, and the chunks of a document are joined with --gap-ms (default 150, the reference's 0.15 s) of
+silence between them into <document>.wav; --loudness then works per document, so that a document has one level.  No per-chunk .wav is
+written.  --fade-ms F (default 0: none, as the reference) fades every chunk in and out over F ms before the join.
+--report FILE.json writes the health check per chunk: the mel's frames, kept frames, last voiced frame, threshold, min, max, mean, std,
+NaN count and the flat flag (std < 1e-5, :579), its document and, with a vocoder, the waveform's peak before --loudness and the silent
+flag (peak < 1e-4, :639).  The summary line names the chunks with NaNs, flat mels and silent audio."""
 from __future__ import annotations
 
 import argparse
@@ -74,6 +85,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pitch-shift", type=float, default=argparse.SUPPRESS, metavar="F", help="added to the normalised pitch of voiced frames")
     p.add_argument("--energy-scale", type=float, default=argparse.SUPPRESS, metavar="F", help="factor on the normalised energy (>= 0)")
     p.add_argument("--energy-shift", type=float, default=argparse.SUPPRESS, metavar="F", help="added to the normalised energy")
+    # (the long-form flags too leave no attribute behind when they are not given: long_form() reads them)
+    p.add_argument("--documents", action="store_true", default=argparse.SUPPRESS,
+                   help='long-form: join the chunks that share a "document" field of --ids into one <document>.wav')
+    p.add_argument("--gap-ms", type=float, default=argparse.SUPPRESS, metavar="F", help="silence between the chunks of a document (default 150)")
+    p.add_argument("--fade-ms", type=float, default=argparse.SUPPRESS, metavar="F", help="fade every chunk in and out over F ms (default 0: none)")
+    p.add_argument("--report", metavar="FILE.json", default=argparse.SUPPRESS, help="write the per-chunk health check of mels and audio")
     return p
 
 
@@ -98,6 +115,17 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
             p.error("--peak-db must be <= 0")
     elif args.peak_db != -1.0:
         p.error("--peak-db needs --loudness")
+    for flag in ("gap_ms", "fade_ms"):
+        v = getattr(args, flag, 0.0)
+        if not math.isfinite(v) or v < 0:
+            p.error(f"--{flag.replace('_', '-')} must be >= 0")
+    if getattr(args, "documents", False):
+        if not args.ids:
+            p.error('--documents needs --ids: the "document" field of its lines groups the chunks')
+        if not (args.vocoder or args.griffin_lim):
+            p.error("--documents needs --vocoder or --griffin-lim: it joins the waveforms")
+    elif hasattr(args, "gap_ms") or hasattr(args, "fade_ms"):
+        p.error("--gap-ms / --fade-ms need --documents")
     try:
         prosody_flags(args)
     except ValueError as e:
@@ -165,6 +193,42 @@ def read_prosody(path: str, flags: dict):
     return out if any_given else None
 
 
+def long_form(args) -> Tuple[bool, float, float, Optional[str]]:
+    """(--documents, --gap-ms, --fade-ms, --report) with their defaults where a flag was not given."""
+    return getattr(args, "documents", False), getattr(args, "gap_ms", 150.0), getattr(args, "fade_ms", 0.0), getattr(args, "report", None)
+
+
+def read_documents(path: str) -> Tuple[List[str], List[List[int]]]:
+    """(document names in order of first appearance, the line numbers of every document's chunks in file order; lines counted as
+    read_ids counts them) of a --ids file: a line's "document" field, or its "name" for a document of its own.  ValueError when a
+    document's name is also that of another document or of a chunk of another document (their files would be confused)."""
+    names, fields = [], []
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            rec = json.loads(line)
+            doc = rec.get("document")
+            if doc is not None and (not isinstance(doc, str) or not doc):
+                raise ValueError(f"{path}:{n}: 'document' must be a non-empty string, not {doc!r}")
+            names.append(str(rec["name"]))
+            fields.append(doc)
+    explicit = {d for d in fields if d is not None}
+    docs, members = [], {}
+    for i, (name, doc) in enumerate(zip(names, fields)):
+        if doc is None and name in explicit:
+            raise ValueError(f"{path}: document {name!r} is named both by a line of its own and by a 'document' field")
+        key = name if doc is None else doc
+        if key not in members:
+            docs.append(key)
+            members[key] = []
+        members[key].append(i)
+    for i, (name, doc) in enumerate(zip(names, fields)):
+        if name in members and i not in members[name]:
+            raise ValueError(f"{path}: {name!r} names a document and a chunk of document {doc!r}")
+    return docs, [members[d] for d in docs]
+
+
 def read_features(cache_dir: str, indices=None) -> Tuple[List[str], List[torch.Tensor], List[torch.Tensor]]:
     from kokoro.data.cached import CachedFeatureDataset
     ds = CachedFeatureDataset(cache_dir, indices=indices, memory_cache=False)
@@ -197,6 +261,42 @@ def level_and_write(args, names, audio, sample_rate: int, device) -> str:
     return note
 
 
+SILENT_PEAK = 1e-4        # the reference's near-silence warning (inference.py:639)
+
+
+def health_note(names, info) -> str:
+    """What the mel health check (inference.py:569-580) adds to the summary line: the chunks with NaNs and the flat ones, by name."""
+    if info is None:
+        return ""
+    note = ""
+    for what, bad in (("with NaNs", [n for n, i in zip(names, info) if i["nan"]]), ("flat", [n for n, i in zip(names, info) if i["flat"]])):
+        if bad:
+            note += f", {len(bad)} {what}: {' '.join(bad)}"
+    return note
+
+
+def vocode_all(args, engine, mels):
+    """(waveforms of the mels in input order, sample rate, what was done) with the vocoder the flags name, denoised with --denoise."""
+    from kokoro.inference.audio import vocode
+    if args.vocoder:
+        from kokoro_ruslan_amd.vocoder import HifiganVocoder
+        voc = HifiganVocoder.from_checkpoint(args.vocoder, args.vocoder_config, device=engine.device, math_mode=args.vocoder_math)
+        audio = vocode(voc, mels)
+        how = f"{args.vocoder_math} vocoder"
+        if args.denoise is not None:
+            from kokoro.inference.audio import denoise
+            from kokoro_ruslan_amd.denoise import SpectralDenoiser
+            den = SpectralDenoiser(device=engine.device)
+            den.bias_from_vocoder(voc)
+            audio = denoise(den, audio, args.denoise)
+            how += f", denoised at strength {args.denoise:g}"
+        return audio, voc.sampling_rate, how
+    from kokoro_ruslan_amd.griffinlim import GriffinLimVocoder
+    gen = torch.Generator().manual_seed(args.griffin_lim_seed) if args.griffin_lim_seed is not None else None
+    voc = GriffinLimVocoder(device=engine.device)
+    return vocode(voc, mels, n_iter=args.griffin_lim_iters, generator=gen), voc.sampling_rate, f"Griffin-Lim, {args.griffin_lim_iters} iterations"
+
+
 def main(argv=None) -> int:
     import numpy as np
     from kokoro.inference.synth import load_for_inference, synthesize, trim_trailing_silence
@@ -204,6 +304,7 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     check_args(parser, args)
     flags = prosody_flags(args)
+    by_document, gap_ms, fade_ms, report = long_form(args)
     if args.ids:
         names, ids, stress = read_ids(args.ids)
         prosody = read_prosody(args.ids, flags)
@@ -224,37 +325,49 @@ def main(argv=None) -> int:
     else:
         mels = synthesize(engine, ids, stress, batch_size=args.batch_size, **pkw, **controls.kwargs())
     os.makedirs(args.output, exist_ok=True)
+    finished, info = None, None
+    if by_document:
+        doc_names, documents = read_documents(args.ids)
+    if by_document or report:
+        from kokoro.inference.audio import finish_mels
+        from kokoro_ruslan_amd.longform import MelFinisher
+        finished, info = finish_mels(MelFinisher(device=engine.device, n_mels=engine.dims.mel), mels)
     saved = []
-    for name, mel in zip(names, mels):
-        mel = mel.float().cpu()
-        if args.trim:
+    for i, (name, mel) in enumerate(zip(names, mels)):
+        mel = finished[i].cpu() if by_document else mel.float().cpu()
+        if args.trim and not by_document:                   # (a finished mel is trimmed already)
             mel = trim_trailing_silence(mel)
         np.save(os.path.join(args.output, f"{name}.npy"), mel.t().contiguous().numpy().astype(np.float32))
         saved.append(mel)
-    print(f"kokoro-synth: {len(mels)} mels ({used} weights, {controls}) -> {args.output}")
-    if args.vocoder:
-        from kokoro.inference.audio import vocode
-        from kokoro_ruslan_amd.vocoder import HifiganVocoder
-        voc = HifiganVocoder.from_checkpoint(args.vocoder, args.vocoder_config, device=engine.device, math_mode=args.vocoder_math)
-        audio = vocode(voc, saved)
-        how = f"{args.vocoder_math} vocoder"
-        if args.denoise is not None:
-            from kokoro.inference.audio import denoise
-            from kokoro_ruslan_amd.denoise import SpectralDenoiser
-            den = SpectralDenoiser(device=engine.device)
-            den.bias_from_vocoder(voc)
-            audio = denoise(den, audio, args.denoise)
-            how += f", denoised at strength {args.denoise:g}"
-        how += level_and_write(args, names, audio, voc.sampling_rate, engine.device)
-        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({how}) -> {args.output}")
-    if args.griffin_lim:
-        from kokoro.inference.audio import vocode
-        from kokoro_ruslan_amd.griffinlim import GriffinLimVocoder
-        gen = torch.Generator().manual_seed(args.griffin_lim_seed) if args.griffin_lim_seed is not None else None
-        voc = GriffinLimVocoder(device=engine.device)
-        audio = vocode(voc, saved, n_iter=args.griffin_lim_iters, generator=gen)
-        how = f"Griffin-Lim, {args.griffin_lim_iters} iterations" + level_and_write(args, names, audio, voc.sampling_rate, engine.device)
-        print(f"kokoro-synth: {len(audio)} waveforms at {voc.sampling_rate} Hz ({how}) -> {args.output}")
+    print(f"kokoro-synth: {len(mels)} mels ({used} weights, {controls}{health_note(names, info)}) -> {args.output}")
+    peaks = None
+    if args.vocoder or args.griffin_lim:
+        audio, rate, how = vocode_all(args, engine, finished if by_document else saved)
+        if info is not None:
+            from kokoro.inference.audio import join_chunks
+            joined, peaks = join_chunks(audio, documents if by_document else [[i] for i in range(len(audio))], rate,
+                                        gap_ms, fade_ms)
+            peaks = peaks.cpu().tolist()
+            silent = [n for n, pk in zip(names, peaks) if pk < SILENT_PEAK]
+            if silent:
+                how += f", {len(silent)} nearly silent: {' '.join(silent)}"
+        if by_document:
+            how += f", {gap_ms:g} ms gaps" + (f", {fade_ms:g} ms fades" if fade_ms else "")
+            how += level_and_write(args, doc_names, joined, rate, engine.device)
+            print(f"kokoro-synth: {len(audio)} chunks in {len(doc_names)} documents at {rate} Hz ({how}) -> {args.output}")
+        else:
+            how += level_and_write(args, names, audio, rate, engine.device)
+            print(f"kokoro-synth: {len(audio)} waveforms at {rate} Hz ({how}) -> {args.output}")
+    if report:
+        of = {c: d for d, members in zip(doc_names, documents) for c in members} if by_document else {}
+        entries = []
+        for i, (name, rec) in enumerate(zip(names, info)):
+            entry = {"name": name, "document": of.get(i, name), **rec}
+            if peaks is not None:
+                entry.update(audio_peak=peaks[i], silent=bool(peaks[i] < SILENT_PEAK))
+            entries.append(entry)
+        with open(report, "w") as f:
+            json.dump(entries, f, indent=1)
     return 0
 
 
