@@ -322,28 +322,19 @@ class KokoroTrainer:
                 boundary = (acc + 1 >= G) or (bi == len(batches) - 1)
                 e.micro_in_cycle = acc
                 T = batch["mel_specs"].shape[1]
+                sync = self.sync if (self.world > 1 and self.sync is not None) else None
                 if self.strict_nonfinite_guard:
-                    flag = e.opt_state[kk.OS["MICRO_BAD"]]
-                    if acc == 0:
-                        e.zero_grad()
-                    e._exchange_now = boundary                # (in-step bucket exchange: only the boundary micro-batch communicates)
-                    out = e.forward_backward(batch, loss_scale=e.dp_loss_scale / div, adaptive=True,
-                                             expanded_len=expanded if expanded != T else None)["losses"]
-                    e._exchange_now = True
-                    if float(flag) != 0.0:                # (host sync) reset accumulation and skip, trainer.py:2304-2314
+                    out = e.micro_batch(batch, div, boundary, sync, expanded if expanded != T else None)
+                    if float(e.opt_state[kk.OS["MICRO_BAD"]]) != 0.0:      # (host sync) reset accumulation and skip, trainer.py:2304-2314
                         logger.error("batch %d: non-finite outputs or losses - accumulation reset, batch skipped", bi)
-                        flag.zero_()
-                        e.zero_grad()
+                        e.drop_cycle()
                         acc = 0
                         continue
                     losses += out
                     if boundary:
-                        if self.world > 1 and self.sync is not None:
-                            self.sync(e.arena.g)
-                        e.optimizer_step(int(e.global_mel_length or T))
-                        e.micro_in_cycle = 0
+                        e.finish_cycle(sync)
                 else:
-                    losses += step(batch, div, boundary, self.sync if (self.world > 1 and self.sync is not None) else None, expanded if expanded != T else None)
+                    losses += step(batch, div, boundary, sync, expanded if expanded != T else None)
                 acc = 0 if boundary else acc + 1
                 n += 1
                 if boundary:

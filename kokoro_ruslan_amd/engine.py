@@ -112,6 +112,33 @@ class _Step:
         self.deferred0 = []
 
 
+class _Micro(NamedTuple):
+    """The decisions of one micro-batch of an accumulation cycle, taken once (KokoroEngine._micro) however the step is run."""
+    first: bool                                     # opens the cycle: the gradient arena is zeroed for it
+    boundary: bool                                  # closes it: the only micro-batch that talks to the other ranks; finish_cycle follows
+    div: int                                        # the accumulation divisor
+    scale: float                                    # dp_loss_scale / div: the seed of the backward
+    mel_length: int                                 # canonical_mel_length: what the optimizer boundary and the graph keys take
+    external_sync: bool                             # the caller reduces arena.g itself at the boundary (grad_sync): no tile norms
+
+
+class _FbKey(NamedTuple):
+    """What a captured forward/backward graph depends on besides the batch shape (KokoroEngine._fb_graph)."""
+    div: int
+    first: bool
+    train_dropout: bool
+    spec_augment: bool
+    math: int
+    exchange: bool                                  # the in-step bucket exchange runs in this micro-batch (the boundary's, with dp_comm)
+    # kk_losses_finalize takes the GLOBAL mel length by value, so a graph captured under one value must not be replayed under another
+    # (ADVICE r3); canonical_mel_length keeps that to one capture per local shape up to 1400 frames.  0 without a loss exchange.
+    mel_length: int
+    loss_sync: bool                                 # a loss exchange is captured
+    self_cleaning_acc: bool
+    attn_keep_gen: Tuple[bool, float]               # (switch, rate): how many layers' keep bits are generated aside
+    tile_norms: bool                                # the grouped weight-gradient launches leave tile-norm records
+
+
 class Arena:
     """Flat fp32 slabs p / g / m / v / ema with one 1024-aligned, zero-padded segment per tensor."""
 
@@ -240,6 +267,7 @@ class KokoroEngine:
         self.losses = f32(6)
         self.loss_coef = f32(5)
         self.micro_in_cycle = 0
+        self._last_micro: Optional[_Micro] = None   # the record of the micro-batch last run: what finish_cycle closes the cycle by
         self.dp_loss_scale = 1.0                    # 1/world in data-parallel runs (dp.GradSync.loss_scale)
         # Data parallel with ragged shards: an object with .loss_sync(acc[12] f64, max_dur[1] i64) that SUM / MAX all-reduces
         # them in place between the loss forward and the loss backward; the losses are then re-finalised with the global
@@ -253,7 +281,7 @@ class KokoroEngine:
         # decoder / encoder layer's grouped weight gradients, the rest after the last launch — and the optimizer waits for
         # that stream.  The collectives are captured with the step, so they are one more branch of its hipGraph (no graph
         # split, nothing between the backward graph and the optimizer graph).  With gradient accumulation only the
-        # boundary micro-batch exchanges (_exchange_now).
+        # boundary micro-batch exchanges (_exchange_now: written by _micro_flags alone, True between steps).
         self.dp_comm = None
         self._comm_events = {}
         self._exchange_now = True
@@ -368,7 +396,7 @@ class KokoroEngine:
         self._defer_wgrads = None                   # a list while a caller collects grouped weight-gradient launches for later
         # The gradient arena was zeroed for THIS micro-batch (first of an accumulation cycle): a layer's grouped weight
         # gradients are each written exactly once per micro-batch, so they overwrite instead of read-modify-write (dW is
-        # 31 MB per decoder layer: a sixth of the grouped launch's traffic).  _first_micro: set by train_step around its call.
+        # 31 MB per decoder layer: a sixth of the grouped launch's traffic).  _first_micro, _external_sync: written by _micro_flags alone.
         self._grads_fresh = False
         self._first_micro = False
         # Text-encoder forward as one persistent launch (kk_encoder_stack_fwd): bf16 mode, phoneme sequences <= 128;
@@ -1918,13 +1946,15 @@ class KokoroEngine:
         self._buf(f"{ns}.kmask", 1, max_expected, dtype=torch.uint8).fill_(1)
         return mel_out, self._buf(f"{ns}.stop", max_expected, B), t_dev
 
-    def _capture_step(self, step) -> "torch.cuda.CUDAGraph":
-        """One hipGraph of step(), a decode step that has run eagerly once with the same buffers."""
+    def _capture(self, launches, *args) -> "torch.cuda.CUDAGraph":
+        """One hipGraph of launches(*args): a decode step, a training micro-batch or the optimizer boundary that has run eagerly before."""
         with self.capture_lock:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
+            # thread_local: with an RCCL process group alive, its watchdog thread polls events while we capture; only
+            # this thread's calls must be capture-safe
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                step()
+                launches(*args)
         return g
 
     def _decode_loop(self, step, stop, max_expected, check_every, decode_graph):
@@ -1939,7 +1969,7 @@ class KokoroEngine:
             else:
                 step()                                     # frame 0 eagerly: it sizes the workspaces a capture may not allocate
                 if decode_graph and max_expected > 1:
-                    step_graph = self._capture_step(step)
+                    step_graph = self._capture(step)
             if ((t + 1) % check_every == 0 or t + 1 == max_expected) and stop(t):
                 break
 
@@ -2278,7 +2308,7 @@ class KokoroEngine:
                     # no graph yet, or an admission regrew a workspace or evicted tables and its addresses are stale: this step
                     step()                                 # eagerly (it sizes the workspaces a capture may not allocate)
                     if decode_graph:
-                        graph, graph_at = self._capture_step(step), self.ws_generation
+                        graph, graph_at = self._capture(step), self.ws_generation
                 host = st["all"][1:3].cpu().tolist()       # done | frames: the one copy of a harvest
                 for s in range(S):
                     if owner[s] >= 0 and host[0][s]:
@@ -2338,7 +2368,7 @@ class KokoroEngine:
     def optimizer_step(self, mel_length: int, tile_norms=None) -> None:
         """Pre-clip → total norm → non-finite skip / explosion tracker / adaptive + global clip → fused AdamW+EMA →
         FFN weight-norm projection.  All decisions on the device (see csrc/kk_optim.hip).
-        tile_norms = (segments, records) from the micro-batch right in front (train_step passes _ss_ready; see grad_norm_from_wgrads):
+        tile_norms = (segments, records) from the micro-batch right in front (finish_cycle passes _ss_ready; see grad_norm_from_wgrads):
         the norm pass skips those segments — only for callers that have not touched the gradient arena in between."""
         a, hp = self.arena, self.hp
         cfg = self._opt_cfg(mel_length)
@@ -2371,30 +2401,73 @@ class KokoroEngine:
                    boundary: Optional[bool] = None, grad_sync=None, expanded_len: Optional[int] = None) -> torch.Tensor:
         """One micro-batch of training in the reference's order (trainer.py:2257-2477): zero grads at the start of an
         accumulation cycle, forward+backward with loss_scale = adaptive/divisor, optimizer boundary when the cycle
-        completes.  Returns the device tensor of 6 losses (no host sync)."""
+        completes.  Returns the device tensor of 6 losses (no host sync).  The cycle itself is micro_batch + finish_cycle."""
+        losses = self.micro_batch(batch, accumulation_divisor, boundary, grad_sync, expanded_len)
+        if self._last_micro.boundary:
+            self.finish_cycle(grad_sync)
+        return losses
+
+    # ------------------------------------------------------------------ the accumulation cycle
+    def _micro(self, T: int, accumulation_divisor, boundary, grad_sync) -> _Micro:
+        """Where the next micro-batch (T mel frames) stands in its accumulation cycle: the only copy of the defaults."""
         G = max(1, int(self.hp.gradient_accumulation_steps))
-        div = accumulation_divisor if accumulation_divisor is not None else G
-        if self.micro_in_cycle == 0:
-            self.zero_grad()
-        is_boundary = bool(boundary) if boundary is not None else self.micro_in_cycle + 1 >= G
-        self._exchange_now = is_boundary                 # (in-step bucket exchange: only the boundary micro-batch communicates)
-        self._first_micro = self.micro_in_cycle == 0          # (zeroed just above)
-        self._external_sync = grad_sync is not None
+        div = int(accumulation_divisor) if accumulation_divisor is not None else G
+        return _Micro(first=self.micro_in_cycle == 0, boundary=bool(boundary) if boundary is not None else self.micro_in_cycle + 1 >= G,
+                      div=div, scale=self.dp_loss_scale / div, mel_length=canonical_mel_length(self.global_mel_length, T),
+                      external_sync=grad_sync is not None)
+
+    @contextlib.contextmanager
+    def _micro_flags(self, m: _Micro):
+        """Around the launch sequence of a micro-batch, run or captured: the only writer of _exchange_now, _first_micro and
+        _external_sync besides __init__.  A sequence that raises leaves them as they are between steps too."""
+        self._exchange_now, self._first_micro, self._external_sync = m.boundary, m.first, m.external_sync
         try:
-            out = self.forward_backward(batch, loss_scale=self.dp_loss_scale / div, adaptive=True, expanded_len=expanded_len)
+            yield
         finally:
-            self._first_micro = False
-            self._external_sync = False
-        self._exchange_now = True
+            self._exchange_now, self._first_micro, self._external_sync = True, False, False
+
+    def micro_batch(self, batch: Dict[str, torch.Tensor], accumulation_divisor: Optional[int] = None, boundary: Optional[bool] = None,
+                    grad_sync=None, expanded_len: Optional[int] = None, _zero_in_step: bool = False, _graphs: Optional[Dict] = None) -> torch.Tensor:
+        """One micro-batch of an accumulation cycle.  Returns the 6 losses; at the boundary (_last_micro) the caller runs finish_cycle
+        with the same grad_sync.  For train_step_graphed: _zero_in_step = the fill of forward_backward(zero_grads=True) instead of
+        zero_grad() in front; _graphs = a shape's entry of the graph cache: the launches are replayed from it instead of issued."""
+        m = self._micro(batch["mel_specs"].shape[1], accumulation_divisor, boundary, grad_sync)
+        if _graphs is not None:
+            self._stage(_graphs["static"], batch)
+            with self._acc_guard():                    # (a replayed graph assumes the accumulators' zero state like an eager step)
+                graph, tile_norms = self._fb_graph(_graphs, m, expanded_len)
+                graph.replay()
+                self._ss_ready = tile_norms
+        else:
+            if m.first and not _zero_in_step:
+                self.zero_grad()
+            with self._micro_flags(m):
+                self._fb(batch, m.scale, True, True, m.first and _zero_in_step, expanded_len)
         self.micro_in_cycle += 1
-        if is_boundary:
-            if grad_sync is not None:
-                grad_sync(self.arena.g)              # data parallel: SUM over ranks (dp.GradSync)
-            self.optimizer_step(canonical_mel_length(self.global_mel_length, batch["mel_specs"].shape[1]),
-                                self._ss_ready if grad_sync is None else None)
-            self._ss_ready = None
-            self.micro_in_cycle = 0
-        return out["losses"]
+        self._last_micro = m
+        return self.losses
+
+    def finish_cycle(self, grad_sync=None, _graphs: Optional[Dict] = None) -> None:
+        """The boundary of an accumulation cycle: grad_sync(arena.g) if given (data parallel: SUM over ranks, dp.GradSync), the
+        optimizer pass (replayed from _graphs like micro_batch's launches) and the reset."""
+        m = self._last_micro
+        if m is None or m.external_sync != (grad_sync is not None):
+            raise RuntimeError("finish_cycle: no micro_batch since the last boundary, or not the grad_sync that micro_batch was given")
+        if grad_sync is not None:
+            grad_sync(self.arena.g)
+        tile_norms = None if m.external_sync else self._ss_ready       # (records of the unreduced gradient say nothing of the reduced one)
+        if _graphs is None:
+            self.optimizer_step(m.mel_length, tile_norms)
+        else:
+            with self._acc_guard():
+                self._opt_graph(_graphs, m.mel_length, tile_norms).replay()
+        self._ss_ready, self._last_micro, self.micro_in_cycle = None, None, 0
+
+    def drop_cycle(self) -> None:
+        """Give up the accumulation cycle in flight (the trainer's strict guard, on a flagged micro-batch): the next micro-batch opens a new one."""
+        self.opt_state[kk.OS["MICRO_BAD"]].zero_()
+        self.zero_grad()
+        self._ss_ready, self._last_micro, self.micro_in_cycle = None, None, 0
 
     def train_step_auto(self, batch: Dict[str, torch.Tensor], accumulation_divisor: Optional[int] = None,
                         boundary: Optional[bool] = None, grad_sync=None, expanded_len: Optional[int] = None) -> torch.Tensor:
@@ -2403,9 +2476,8 @@ class KokoroEngine:
         launches), a shape seen for the first time runs eagerly.  Large dynamic batches (max_frames 16384: 15-20 ms of
         GPU time per step) hide the eager launches anyway; small fixed shapes are where the graphs pay.  At most
         max_graphs shapes are kept (least recently used first out)."""
-        B, T = batch["mel_specs"].shape[:2]
-        key = (B, T, batch["phoneme_indices"].shape[1], T if expanded_len is None else int(expanded_len))
-        if self.loss_sync is None or getattr(self.loss_sync, "capturable", False):     # (a torch.distributed loss exchange is eager)
+        key = self._shape_key(batch, expanded_len)
+        if self._loss_sync_capturable():               # (a torch.distributed loss exchange is eager)
             if key in self._graphs:
                 return self.train_step_graphed(batch, grad_sync, accumulation_divisor, boundary, expanded_len)
             n = self._shape_seen.get(key, 0) + 1
@@ -2418,62 +2490,17 @@ class KokoroEngine:
         return self.train_step(batch, accumulation_divisor, boundary, grad_sync, expanded_len)
 
     # ------------------------------------------------------------------ hipGraph replay of a whole step
-    def _capture_fb(self, static, scale, first, expanded_len) -> "torch.cuda.CUDAGraph":
-        """Capture one micro-batch variant (forward + losses + backward) of a batch shape; called under capture_lock."""
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        # thread_local: with an RCCL process group alive, its watchdog thread polls events while we capture; only
-        # this thread's calls must be capture-safe
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self.forward_backward(static, loss_scale=scale, adaptive=True, zero_grads=first, expanded_len=expanded_len)
-        return g
-
-    def train_step_graphed(self, batch: Dict[str, torch.Tensor], grad_sync=None, accumulation_divisor: Optional[int] = None,
-                           boundary: Optional[bool] = None, expanded_len: Optional[int] = None) -> torch.Tensor:
-        """Same semantics as train_step (gradient accumulation included), but the kernel sequence of a micro-batch is
-        captured once per (batch shape, accumulation divisor, first-of-cycle) into hipGraphs and replayed (a step is ~700
-        launches; eager launch overhead would dominate), and the optimizer boundary once per (shape, mel length).
-        `grad_sync` (data parallel) runs between the backward graph and the optimizer graph.  The first call with a new
-        shape runs eagerly: it sizes the workspace and builds the descriptor tables, neither of which may happen inside
-        a capture."""
+    @staticmethod
+    def _shape_key(batch, expanded_len) -> Tuple[int, int, int, int]:
+        """What the graph cache and train_step_auto's first-sight count know a batch shape by: (B, T, phonemes, T')."""
         B, T = batch["mel_specs"].shape[:2]
-        Tp = T if expanded_len is None else int(expanded_len)
-        key = (B, T, batch["phoneme_indices"].shape[1], Tp)
-        if self.loss_sync is not None and not getattr(self.loss_sync, "capturable", False):
-            raise RuntimeError("train_step_graphed: this loss_sync exchanges the loss counts through torch.distributed between "
-                               "kernels of the step, which a hipGraph cannot hold; use train_step, or the RCCL exchange "
-                               "(dp.BucketedExchange, backend 'rccl'), whose collectives are captured with the step")
-        G = max(1, int(self.hp.gradient_accumulation_steps))
-        div = int(accumulation_divisor) if accumulation_divisor is not None else G
-        first = self.micro_in_cycle == 0
-        is_boundary = bool(boundary) if boundary is not None else self.micro_in_cycle + 1 >= G
-        scale = self.dp_loss_scale / div
-        mel_length = canonical_mel_length(self.global_mel_length, T)
-        ent = self._graphs.get(key)
-        self._exchange_now = is_boundary
-        if ent is None:                               # first sight of a shape: eager (allocates the workspaces and the
-            static = {k: v.clone() for k, v in batch.items()}      # reduction tables — host-to-device copies, illegal in a capture)
-            self._external_sync = grad_sync is not None
-            try:
-                self._fb(static, scale, True, True, first, expanded_len)
-            finally:
-                self._external_sync = False
-            self._exchange_now = True
-            # (registered only now: growing a buffer during the eager pass drops every graph entry)
-            if len(self._graphs) >= self.max_graphs:
-                torch.cuda.synchronize(self.device)   # a graph about to be destroyed may still be running
-                self._graphs.popitem(last=False)
-            self._graphs[key] = {"static": static, "fb": {}, "opt": {}}
-            self.micro_in_cycle += 1
-            if is_boundary:
-                if grad_sync is not None:
-                    grad_sync(self.arena.g)
-                self.optimizer_step(mel_length, self._ss_ready if grad_sync is None else None)
-                self._ss_ready = None
-                self.micro_in_cycle = 0
-            return self.losses
-        self._graphs.move_to_end(key)
-        static = ent["static"]
+        return (B, T, batch["phoneme_indices"].shape[1], T if expanded_len is None else int(expanded_len))
+
+    def _loss_sync_capturable(self) -> bool:
+        return self.loss_sync is None or getattr(self.loss_sync, "capturable", False)
+
+    def _stage(self, static: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor]) -> None:
+        """Copy a batch into the static tensors that the graphs of its shape read."""
         moved = []
         for k, v in batch.items():
             d = static[k]
@@ -2485,50 +2512,61 @@ class KokoroEngine:
                 d.copy_(v, non_blocking=True)
         if moved:
             kk.copy_many(moved)                        # one launch for the whole batch
-        # (kk_losses_finalize takes the GLOBAL mel length by value — the adaptive loss scale depends on it above 1400 frames — so a
-        # graph captured under one value must not be replayed under another: ADVICE r3; the CANONICAL value, so that a ragged
-        # data-parallel run replays one capture per local shape for every global length up to 1400: canonical_mel_length)
-        fkey = (div, first, self.train_dropout, self.spec_augment_active, self.math, self.dp_comm is not None and is_boundary,
-                mel_length if self.loss_sync is not None else 0, self.loss_sync is not None, self.self_cleaning_acc, (self.attn_keep_gen, self.attn_keep_gen_rate),
-                self.grad_norm_from_wgrads and grad_sync is None)
-        with self._acc_guard():                        # (a replayed graph assumes the accumulators' zero state like an eager step)
-            fbe = ent["fb"].get(fkey)
-            if fbe is None:
-                with self.capture_lock:
-                    self._external_sync = grad_sync is not None
-                    try:
-                        g_ = self._capture_fb(static, scale, first, expanded_len)
-                    finally:
-                        self._external_sync = False
-                    fbe = ent["fb"][fkey] = (g_, self._ss_ready)      # (the tile-norm records this launch sequence leaves: the same at every replay)
-            self._exchange_now = True
-            fbe[0].replay()
-            self._ss_ready = fbe[1]
-        self.micro_in_cycle += 1
-        if grad_sync is not None and is_boundary:
-            grad_sync(self.arena.g)
-        if is_boundary:
-            # (KkOptCfg travels by value: the legacy schedule's factor changes once per epoch -> one re-capture per epoch; the graphs of
-            #  earlier epochs are dropped then — they can never be replayed again and would otherwise pile up, epochs x shapes: ADVICE r5)
-            epoch = 0 if self.hp.use_onecycle_lr else self.lr_epoch
-            tn = self._ss_ready if grad_sync is None else None
-            self._ss_ready = None
-            if tn is not None and tn[0] not in self._ss_masks:       # (its skip table is built by an eager boundary only: no copies under capture)
-                tn = None
-            okey = (mel_length, epoch, self.self_cleaning_acc, tn)
-            for k in [k for k in ent["opt"] if k[1] != epoch]:
-                torch.cuda.synchronize(self.device)   # (a graph about to be destroyed may still be running)
-                del ent["opt"][k]
-            with self._acc_guard():
-                opt = ent["opt"].get(okey)
-                if opt is None:
-                    with self.capture_lock:
-                        torch.cuda.synchronize()
-                        opt = ent["opt"][okey] = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(opt, capture_error_mode="thread_local"):
-                            self.optimizer_step(mel_length, tn)
-                opt.replay()
-            self.micro_in_cycle = 0
+
+    def _fb_graph(self, ent: Dict, m: _Micro, expanded_len) -> Tuple["torch.cuda.CUDAGraph", Optional[Tuple]]:
+        """(graph, tile-norm records its launches leave: the same at every replay) of micro-batch m for the shape's cache entry ent."""
+        key = _FbKey(m.div, m.first, self.train_dropout, self.spec_augment_active, self.math, self.dp_comm is not None and m.boundary,
+                     m.mel_length if self.loss_sync is not None else 0, self.loss_sync is not None, self.self_cleaning_acc,
+                     (self.attn_keep_gen, self.attn_keep_gen_rate), self.grad_norm_from_wgrads and not m.external_sync)
+        fbe = ent["fb"].get(key)
+        if fbe is None:
+            with self._micro_flags(m):
+                g = self._capture(self._fb, ent["static"], m.scale, True, True, m.first, expanded_len)
+            fbe = ent["fb"][key] = (g, self._ss_ready)
+        return fbe
+
+    def _opt_graph(self, ent: Dict, mel_length: int, tile_norms) -> "torch.cuda.CUDAGraph":
+        """The optimizer-boundary graph for the shape whose cache entry is ent, captured at first use."""
+        # (KkOptCfg travels by value: the legacy schedule's factor changes once per epoch -> one re-capture per epoch; the graphs of
+        #  earlier epochs are dropped then — they can never be replayed again and would otherwise pile up, epochs x shapes: ADVICE r5)
+        epoch = 0 if self.hp.use_onecycle_lr else self.lr_epoch
+        for k in [k for k in ent["opt"] if k[1] != epoch]:
+            torch.cuda.synchronize(self.device)       # (a graph about to be destroyed may still be running)
+            del ent["opt"][k]
+        if tile_norms is not None and tile_norms[0] not in self._ss_masks:       # (its skip table is built by an eager boundary only: no copies under capture)
+            tile_norms = None
+        key = (mel_length, epoch, self.self_cleaning_acc, tile_norms)
+        if key not in ent["opt"]:
+            ent["opt"][key] = self._capture(self.optimizer_step, mel_length, tile_norms)
+        return ent["opt"][key]
+
+    def train_step_graphed(self, batch: Dict[str, torch.Tensor], grad_sync=None, accumulation_divisor: Optional[int] = None,
+                           boundary: Optional[bool] = None, expanded_len: Optional[int] = None) -> torch.Tensor:
+        """Same semantics as train_step (gradient accumulation included), but the kernel sequence of a micro-batch is
+        captured once per (batch shape, accumulation divisor, first-of-cycle) into hipGraphs and replayed (a step is ~700
+        launches; eager launch overhead would dominate), and the optimizer boundary once per (shape, mel length).
+        `grad_sync` (data parallel) runs between the backward graph and the optimizer graph.  The first call with a new
+        shape runs eagerly: it sizes the workspace and builds the descriptor tables, neither of which may happen inside
+        a capture: micro_batch + finish_cycle like train_step.  A replay takes the same _micro record and the same finish_cycle."""
+        if not self._loss_sync_capturable():
+            raise RuntimeError("train_step_graphed: this loss_sync exchanges the loss counts through torch.distributed between "
+                               "kernels of the step, which a hipGraph cannot hold; use train_step, or the RCCL exchange "
+                               "(dp.BucketedExchange, backend 'rccl'), whose collectives are captured with the step")
+        key = self._shape_key(batch, expanded_len)
+        ent = self._graphs.get(key)
+        if ent is None:                               # first sight of a shape: eager (allocates the workspaces and the
+            static = {k: v.clone() for k, v in batch.items()}      # reduction tables — host-to-device copies, illegal in a capture)
+            self.micro_batch(static, accumulation_divisor, boundary, grad_sync, expanded_len, _zero_in_step=True)
+            # (registered only now: growing a buffer during the eager pass drops every graph entry)
+            if len(self._graphs) >= self.max_graphs:
+                torch.cuda.synchronize(self.device)   # a graph about to be destroyed may still be running
+                self._graphs.popitem(last=False)
+            self._graphs[key] = {"static": static, "fb": {}, "opt": {}}
+        else:
+            self._graphs.move_to_end(key)
+            self.micro_batch(batch, accumulation_divisor, boundary, grad_sync, expanded_len, _graphs=ent)
+        if self._last_micro.boundary:
+            self.finish_cycle(grad_sync, _graphs=ent)      # (ent is None on first sight: the boundary runs eagerly too)
         return self.losses
 
     def encoder_stack_error(self) -> int:

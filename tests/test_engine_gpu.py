@@ -927,7 +927,7 @@ def test_in_graph_bucket_exchange_over_rccl_one_rank(eng_mod, golden_dir):
         torch.cuda.synchronize()
         assert e.opt_stats()["attempt"] == 4 and e.opt_stats()["skipped"] == 0
         if graphed:
-            assert len(e._graphs) == 1 and any(k[7] for ent in e._graphs.values() for k in ent["fb"]), "the ragged step must replay from a graph (key field 7: a loss exchange is captured)"
+            assert len(e._graphs) == 1 and any(k.loss_sync for ent in e._graphs.values() for k in ent["fb"]), "the ragged step must replay from a graph (a loss exchange is captured)"
         return e.arena.p.clone()
     got_e, got_g = run_ragged(False), run_ragged(True)
     assert float((got_e - ref1).abs().max()) <= 2e-5 * float(ref1.abs().max())
@@ -1188,6 +1188,99 @@ def test_accumulators_survive_an_aborted_step(eng_mod, golden_dir):
     torch.testing.assert_close(e.losses, want_l2, rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(e2.losses, want_l2, rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(e2.arena.p, want_p2, rtol=0, atol=6e-6)
+
+
+def _cycle_batches(d, n, seed):
+    """The smallest fixture the accumulation cycle needs (its logic has no shape dependence): two ragged rows, 40 frames, 6 phonemes."""
+    return [_cuda(O.synthetic_batch(2, 40, 6, d, seed=seed + i, ragged=True)) for i in range(n)]
+
+
+@pytest.mark.parametrize("math_mode", ["f32", "bf16"])
+def test_micro_batch_plus_finish_cycle_is_train_step(eng_mod, golden_dir, math_mode):
+    """The split form of the accumulation cycle (what the trainer's strict guard drives) is train_step: two cycles of G = 2 through
+    train_step and through micro_batch + finish_cycle at the boundary issue the same launches, so they differ as two runs of one
+    sequence do — by the fp32 atomics of the phoneme-embedding gradient: 3e-6 per optimizer step in fp32
+    (test_accumulators_survive_an_aborted_step), 2e-5 of max|p| in bf16 with dropout (test_graphed_accumulation_matches_eager)."""
+    fx, d, _, P = _load(golden_dir, "tiny_full")
+    batches = _cycle_batches(d, 4, 700)
+    res = []
+    for split in (False, True):
+        e = _engine(eng_mod, d, P, math_mode=math_mode, gradient_accumulation_steps=2)
+        e.train_dropout = math_mode == "bf16"
+        for i, b in enumerate(batches):
+            if not split:
+                e.train_step(b)
+                continue
+            e.micro_batch(b)
+            if i % 2 == 1:
+                e.finish_cycle()
+        torch.cuda.synchronize()
+        st = e.opt_stats()
+        assert e.micro_in_cycle == 0
+        res.append((e.arena.p.clone(), st["attempt"], st["skipped"]))
+    assert res[0][1:] == res[1][1:] and res[0][1] == 2, (res[0][1:], res[1][1:])
+    err = float((res[0][0] - res[1][0]).abs().max())
+    print(f"{math_mode}: max|p(train_step) - p(micro_batch + finish_cycle)| = {err:.3e}, max|p| = {float(res[0][0].abs().max()):.3e}")
+    assert err <= (2 * 3e-6 if math_mode == "f32" else 2e-5 * float(res[0][0].abs().max()))
+
+
+class _Boom:
+    """A loss exchange whose collective fails: a host-side exception between kk_losses_fwd and kk_losses_finalize."""
+
+    def __init__(self, capturable):
+        self.capturable = capturable
+
+    def loss_sync(self, acc, max_dur):
+        raise RuntimeError("collective failed")
+
+
+@pytest.mark.parametrize("graphed", [False, True])
+def test_step_flags_come_back_after_a_step_that_raises(eng_mod, golden_dir, graphed):
+    """A step that raises in the FIRST micro-batch of a G = 2 cycle (not the boundary: the in-step exchange is off for it) must leave
+    the flags the launch sequence reads as they are between steps — else the next forward_backward of a data-parallel run would skip
+    dp_comm.begin_step() and every bucket — through train_step and through train_step_graphed's first-sight pass; the cycle after it
+    is a fresh engine's first cycle."""
+    fx, d, _, P = _load(golden_dir, "tiny_full")
+    batches = _cycle_batches(d, 2, 720)
+    ref = _engine(eng_mod, d, P, gradient_accumulation_steps=2)
+    e = _engine(eng_mod, d, P, gradient_accumulation_steps=2)
+    e.loss_sync = _Boom(capturable=graphed)
+    with pytest.raises(RuntimeError, match="collective failed"):
+        (e.train_step_graphed if graphed else e.train_step)(batches[0])
+    assert e._exchange_now is True and e._first_micro is False and e._external_sync is False
+    assert not e._graphs, "a first-sight pass that raised registers nothing"
+    e.loss_sync, e.micro_in_cycle = None, 0
+    for b in batches:
+        for eng in (ref, e):
+            (eng.train_step_graphed if graphed else eng.train_step)(b)
+    torch.cuda.synchronize()
+    assert e.micro_in_cycle == 0 and e.opt_stats()["attempt"] == ref.opt_stats()["attempt"] == 1
+    torch.testing.assert_close(e.arena.p, ref.arena.p, rtol=0, atol=3e-6)
+
+
+def test_drop_cycle_leaves_no_trace_of_the_cycle(eng_mod, golden_dir):
+    """drop_cycle (the trainer's strict guard on a flagged micro-batch): gradients, the cycle position, the tile-norm records and the
+    device's flag word are as before the cycle, the optimizer has not run; the cycle after it steps."""
+    from kokoro_ruslan_amd import lib as kk
+    fx, d, _, P = _load(golden_dir, "tiny_full")
+    batches = _cycle_batches(d, 3, 740)
+    e = _engine(eng_mod, d, P, gradient_accumulation_steps=2)
+    before, attempt = e.arena.p.clone(), e.opt_stats()["attempt"]
+    e.micro_batch(batches[0])
+    assert e.micro_in_cycle == 1 and float(e.arena.g.abs().max()) > 0
+    e.opt_state[kk.OS["MICRO_BAD"]] = 1.0                     # (as the finite guard of a bad micro-batch leaves it)
+    e.drop_cycle()
+    torch.cuda.synchronize()
+    assert float(e.arena.g.abs().max()) == 0 and e.micro_in_cycle == 0 and e._ss_ready is None
+    assert float(e.opt_state[kk.OS["MICRO_BAD"]]) == 0
+    assert e.opt_stats()["attempt"] == attempt and torch.equal(e.arena.p, before)
+    with pytest.raises(RuntimeError, match="finish_cycle"):   # (a host-side check in front of any launch: no cycle is open)
+        e.finish_cycle()
+    e.micro_batch(batches[1])
+    e.micro_batch(batches[2])
+    e.finish_cycle()
+    torch.cuda.synchronize()
+    assert e.opt_stats()["attempt"] == attempt + 1 and e.micro_in_cycle == 0 and not torch.equal(e.arena.p, before)
 
 
 def test_gradient_norms_from_the_weight_gradient_epilogues(eng_mod):

@@ -33,9 +33,13 @@ def _fake_cache(root, n=12, tmin=40, tmax=120, pmin=4, pmax=14, extra_frames=())
                     "_cache_version": 7}, d / f"utt{i:03d}.pt")
 
 
-def test_kokoro_train_cli_end_to_end(tmp_path):
+@pytest.mark.parametrize("strict_guard", [False, True])
+def test_kokoro_train_cli_end_to_end(tmp_path, monkeypatch, strict_guard):
+    """strict_guard: the per-micro-batch host check (KK_STRICT_NONFINITE=1), which drives the engine's micro_batch / finish_cycle
+    itself instead of train_step_auto; everything below holds for both."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
+    monkeypatch.setenv("KK_STRICT_NONFINITE", "1" if strict_guard else "0")
     from kokoro.cli.training import main
     from kokoro.training import checkpoint as ckpt
     from kokoro_ruslan_amd import spec
