@@ -577,6 +577,15 @@ int kk_dtw_backtrack(const uint32_t *dir, const int64_t *doff, const int *aoff, 
 int kk_dtw_path_stats(const float *ca, int64_t Ta_total, const float *cb, int64_t Tb_total, int K, const float *xa, const float *xb,
                       int M, const int *aoff, const int *boff, const int *path, const int64_t *poff, const int *steps, int B,
                       double *mcd_sum, double *l1_sum, void *stream);
+/* per pair, over its path, on two scalar tracks per side packed like the mels (pa, ea: [Ta_total]; pb, eb: [Tb_total]): p is the
+ * normalised pitch, a frame is voiced iff p > 0 and its frequency is f = f_lo + f_span p; e is the energy.  counts: int32 [5][B] =
+ * n_vv, n_vu (a voiced, b not), n_uv, n_uu, n_gpe (both voiced and |fa - fb| > gpe_ratio fb).  sums: fp64 [3][B] = sum c, sum c^2 over
+ * the steps voiced on both sides, c = 1200 log2(fa / fb), and sum |ea[i] - eb[j]| over all steps.  f, the differences and the
+ * comparisons are fp64 with every +, -, x rounded on its own, so the counts are exact.  The reduction is kk_dtw_path_stats's: every
+ * 256th step per thread, a fixed tree.  A pair with steps = 0 or outside the DP's limits is skipped (its outputs are not written) */
+int kk_dtw_track_stats(const float *pa, const float *ea, const float *pb, const float *eb, const int *aoff, const int *boff,
+                       const int *path, const int64_t *poff, const int *steps, int B, double f_lo, double f_span, double gpe_ratio,
+                       int *counts, double *sums, void *stream);
 
 /* ---- flat-start forced alignment of phoneme tokens to mel frames (kokoro_ruslan_amd/align.py; kk_align.hip) ----
  * A ragged batch of B utterances: frames packed back to back, foff: int32 [B + 1]; tokens packed back to back, poff: int32 [B + 1].

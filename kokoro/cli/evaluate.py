@@ -4,6 +4,8 @@
                 [--weights auto|ema|model] [--math bf16|f32] [--no-stream] [--slots N] [--batch-size N] [--mcep K]
                 [--stop-threshold X] [--max-len N] [--min-len-ratio R] [--min-len-floor N] [--output REPORT.json]
                 [--oracle-durations]
+                [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
+                [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]] [--gpe-ratio F]
 
 Synthesizes every selected utterance with the stop rule deciding its length (continuous batching in a pool of --slots rows, or with
 --no-stream in batches of --batch-size), aligns each mel with the cached ground truth by dynamic time warping on K mel cepstra and
@@ -14,11 +16,19 @@ utterances `kokoro-train --validation-split` holds out (the same draw: kokoro.da
 of the cache's length-sorted order instead.  --output writes records, summary, controls and the weights used as JSON.
 --oracle-durations forces the cache's phoneme_durations on every utterance (kokoro_ruslan_amd.prosody): dur_abs_err is then 0 and
 len_ratio, mcd_dtw and mel_l1_dtw show the decoder alone, without the duration predictor's errors.  An utterance whose cache entry
-holds no durations for its phonemes is an error that names it."""
+holds no durations for its phonemes is an error that names it.
+--vocoder / --griffin-lim (kokoro-synth's flags and loaders; --denoise with --vocoder) judge the audio too: every mel is vocoded, the
+pitch and energy of the waveforms are extracted on the device (kokoro_ruslan_amd.features) and compared with the cache entry's own
+pitch and energy along the same alignment.  The report then also carries f0_rmse_cents and f0_bias_cents (root mean square and mean
+of 1200 log2(f_syn / f_true) over the steps voiced on both sides), gpe (the share of those steps whose F0 is more than --gpe-ratio,
+default 0.2, off the true one), vuv_err (the share of steps voiced on one side only) and energy_l1_dtw (mean |difference| of the
+normalised energies).  An utterance whose cached pitch and energy are all zero (a cache written with --no-variance) gets none of them
+and is counted in the summary line."""
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 from typing import List, Optional
@@ -45,6 +55,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min-len-floor", type=int, default=None)
     p.add_argument("--output", metavar="REPORT.json", default=None)
     p.add_argument("--oracle-durations", action="store_true", help="synthesize on the cache's phoneme_durations instead of the predicted ones")
+    from kokoro.cli.synth import add_vocoder_flags
+    add_vocoder_flags(p)
+    p.add_argument("--gpe-ratio", type=float, default=0.2, metavar="F",
+                   help="a gross pitch error: F0 more than F times the true one off it (default 0.2; needs --vocoder or --griffin-lim)")
     return p
 
 
@@ -65,6 +79,12 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--batch-size must be >= 1")
     if not (1 <= args.mcep <= 32):
         p.error("--mcep must be in 1..32")
+    from kokoro.cli.synth import check_vocoder_flags
+    check_vocoder_flags(p, args)
+    if args.gpe_ratio != 0.2 and not (args.vocoder or args.griffin_lim):
+        p.error("--gpe-ratio needs --vocoder or --griffin-lim: it bears on the audio's F0")
+    if not math.isfinite(args.gpe_ratio) or args.gpe_ratio < 0:
+        p.error("--gpe-ratio must be >= 0")
 
 
 def select_indices(n: int, split: Optional[str], validation_split: float, indices: Optional[List[int]]) -> List[int]:
@@ -79,12 +99,12 @@ def select_indices(n: int, split: Optional[str], validation_split: float, indice
 
 
 def read_features(cache_dir: str, split: Optional[str], validation_split: float, indices: Optional[List[int]]):
-    """(names, ids, stress, mels [T, M], durations) of the selected utterances."""
+    """(names, ids, stress, mels [T, M], durations, pitch [T], energy [T]) of the selected utterances."""
     from kokoro.data.cached import CachedFeatureDataset, scan_cache
     metas = scan_cache(cache_dir)
     sel = select_indices(len(metas), split or "val", validation_split, indices)
     ds = CachedFeatureDataset(cache_dir, indices=sel, memory_cache=False, metas=metas)
-    names, ids, stress, mels, durs = [], [], [], [], []
+    names, ids, stress, mels, durs, pitch, energy = [], [], [], [], [], [], []
     for i in range(len(ds)):
         it = ds[i]
         names.append(os.path.splitext(ds.samples[i]["file"].name)[0])
@@ -92,7 +112,9 @@ def read_features(cache_dir: str, split: Optional[str], validation_split: float,
         stress.append(it["stress_indices"].to(torch.int64))
         mels.append(it["mel_spec"].t().contiguous().float())
         durs.append(it["phoneme_durations"].to(torch.int64))
-    return names, ids, stress, mels, durs
+        pitch.append(it["pitch"].float().reshape(-1))
+        energy.append(it["energy"].float().reshape(-1))
+    return names, ids, stress, mels, durs, pitch, energy
 
 
 def oracle_prosody(names, ids, durs):
@@ -112,7 +134,8 @@ def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
     check_args(parser, args)
-    names, ids, stress, mels, durs = read_features(args.features, args.split, args.validation_split, args.indices)
+    audio = bool(args.vocoder or args.griffin_lim)
+    names, ids, stress, mels, durs, pitch, energy = read_features(args.features, args.split, args.validation_split, args.indices)
     if not names:
         parser.error("the selection is empty: nothing to evaluate")
     engine, controls, used = S.load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,
@@ -126,11 +149,22 @@ def main(argv=None) -> int:
             pkw["prosody"] = oracle_prosody(names, ids, durs)
         except ValueError as e:
             parser.error(str(e))
+    how = ""
+    if audio:
+        from kokoro.cli.synth import check_vocoder_model, load_vocoder
+        from kokoro_ruslan_amd.dtw import MelAligner
+        check_vocoder_model(parser, args, engine.dims.mel)
+        voc, vkw, den, how = load_vocoder(args, engine.device)
+        pkw.update(vocoder=voc, vocoder_kwargs=vkw, ref_pitch=pitch, ref_energy=energy,
+                   aligner=MelAligner(device=engine.device, K=args.mcep, gpe_ratio=args.gpe_ratio))
+        if den is not None:
+            pkw.update(denoiser=den, denoise_strength=args.denoise)
     records, summary = E.evaluate(engine, ids, stress, mels, stream=not args.no_stream, slots=32 if args.slots is None else args.slots,
                                   batch_size=32 if args.batch_size is None else args.batch_size, durations=durs, names=names,
                                   mcep=args.mcep, **pkw, **controls.kwargs())
     print(f"kokoro-eval: {summary['utterances']} utterances ({used} weights, {controls}), "
-          f"{100.0 * summary['hit_bound_share']:.1f} % ended at their generation bound")
+          f"{100.0 * summary['hit_bound_share']:.1f} % ended at their generation bound"
+          + (f"; audio: {how}, {summary['no_variance']} without pitch and energy in the cache" if audio else ""))
     for k in E.METRICS:
         if k in summary:
             s = summary[k]
@@ -139,7 +173,8 @@ def main(argv=None) -> int:
         with open(args.output, "w") as f:
             json.dump({"records": records, "summary": summary, "controls": controls.kwargs(), "weights": used, "mcep": args.mcep,
                        "split": "indices" if args.indices is not None else (args.split or "val"), "checkpoint": args.checkpoint,
-                       **({"oracle_durations": True} if args.oracle_durations else {})}, f, indent=1)
+                       **({"oracle_durations": True} if args.oracle_durations else {}),
+                       **({"audio": how, "gpe_ratio": args.gpe_ratio} if audio else {})}, f, indent=1)
         print(f"kokoro-eval: report -> {args.output}")
     return 0
 

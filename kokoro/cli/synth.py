@@ -50,6 +50,18 @@ from typing import List, Optional, Tuple
 import torch
 
 
+def add_vocoder_flags(p: argparse.ArgumentParser) -> None:
+    """The flags that name a vocoder (kokoro-synth and kokoro-eval spell them alike; check_vocoder_flags, load_vocoder)."""
+    p.add_argument("--vocoder", metavar="PATH", default=None, help="HiFi-GAN generator: directory or checkpoint file")
+    p.add_argument("--vocoder-config", metavar="JSON", default=None, help="HiFi-GAN config (default: the checkpoint's config.json)")
+    p.add_argument("--vocoder-math", choices=("bf16", "f32"), default="bf16")
+    p.add_argument("--denoise", type=float, nargs="?", const=0.005, default=None, metavar="S",
+                   help="subtract S (default 0.005) times the vocoder's bias spectrum from every waveform (needs --vocoder)")
+    p.add_argument("--griffin-lim", action="store_true", help="vocode with Griffin-Lim (no checkpoint; not with --vocoder)")
+    p.add_argument("--griffin-lim-iters", type=int, default=60, metavar="N")
+    p.add_argument("--griffin-lim-seed", type=int, default=None, metavar="S", help="seed of the initial random phases")
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Batched mel synthesis from a Kokoro checkpoint (MI355X engine)")
     p.add_argument("--checkpoint", required=True)
@@ -68,14 +80,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--math", choices=("bf16", "f32"), default="bf16")
     p.add_argument("--stream", action="store_true", help="continuous batching: refill finished rows instead of fixed batches")
     p.add_argument("--slots", type=int, default=None, metavar="N", help="rows of the --stream pool (default 32)")
-    p.add_argument("--vocoder", metavar="PATH", default=None, help="HiFi-GAN generator: directory or checkpoint file")
-    p.add_argument("--vocoder-config", metavar="JSON", default=None, help="HiFi-GAN config (default: the checkpoint's config.json)")
-    p.add_argument("--vocoder-math", choices=("bf16", "f32"), default="bf16")
-    p.add_argument("--denoise", type=float, nargs="?", const=0.005, default=None, metavar="S",
-                   help="subtract S (default 0.005) times the vocoder's bias spectrum from every waveform (needs --vocoder)")
-    p.add_argument("--griffin-lim", action="store_true", help="vocode with Griffin-Lim (no checkpoint; not with --vocoder)")
-    p.add_argument("--griffin-lim-iters", type=int, default=60, metavar="N")
-    p.add_argument("--griffin-lim-seed", type=int, default=None, metavar="S", help="seed of the initial random phases")
+    add_vocoder_flags(p)
     p.add_argument("--loudness", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS",
                    help="bring every waveform to LUFS (default -23) integrated loudness (needs --vocoder or --griffin-lim)")
     p.add_argument("--peak-db", type=float, default=-1.0, metavar="DB", help="peak ceiling of --loudness in dB of full scale (default -1)")
@@ -94,7 +99,7 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def check_args(p: argparse.ArgumentParser, args) -> None:
+def check_vocoder_flags(p: argparse.ArgumentParser, args) -> None:
     if args.griffin_lim and args.vocoder:
         p.error("--griffin-lim and --vocoder are alternatives: give one")
     if not args.griffin_lim and (args.griffin_lim_iters != 60 or args.griffin_lim_seed is not None):
@@ -106,6 +111,10 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
             p.error("--denoise needs --vocoder: the bias it subtracts is a HiFi-GAN generator's (not with --griffin-lim)")
         if not math.isfinite(args.denoise) or args.denoise < 0:
             p.error("--denoise must be >= 0")
+
+
+def check_args(p: argparse.ArgumentParser, args) -> None:
+    check_vocoder_flags(p, args)
     if args.loudness is not None:
         if not (args.vocoder or args.griffin_lim):
             p.error("--loudness needs --vocoder or --griffin-lim: it works on the waveforms")
@@ -275,26 +284,39 @@ def health_note(names, info) -> str:
     return note
 
 
-def vocode_all(args, engine, mels):
-    """(waveforms of the mels in input order, sample rate, what was done) with the vocoder the flags name, denoised with --denoise."""
-    from kokoro.inference.audio import vocode
+def check_vocoder_model(p: argparse.ArgumentParser, args, n_mels: int) -> None:
+    """What the vocoder the flags name asks of the checkpoint, once it is loaded."""
+    if args.griffin_lim and n_mels != 80:
+        p.error(f"--griffin-lim needs an 80-mel model; this checkpoint makes {n_mels} mel channels")
+
+
+def load_vocoder(args, device):
+    """(vocoder, the keyword arguments of its vocode(), denoiser or None, what they do) for the vocoder the flags name: a HiFi-GAN
+    generator (with --denoise: a SpectralDenoiser holding its bias) or Griffin-Lim with its iterations and seeded phases."""
     if args.vocoder:
         from kokoro_ruslan_amd.vocoder import HifiganVocoder
-        voc = HifiganVocoder.from_checkpoint(args.vocoder, args.vocoder_config, device=engine.device, math_mode=args.vocoder_math)
-        audio = vocode(voc, mels)
-        how = f"{args.vocoder_math} vocoder"
+        voc = HifiganVocoder.from_checkpoint(args.vocoder, args.vocoder_config, device=device, math_mode=args.vocoder_math)
+        den, how = None, f"{args.vocoder_math} vocoder"
         if args.denoise is not None:
-            from kokoro.inference.audio import denoise
             from kokoro_ruslan_amd.denoise import SpectralDenoiser
-            den = SpectralDenoiser(device=engine.device)
+            den = SpectralDenoiser(device=device)
             den.bias_from_vocoder(voc)
-            audio = denoise(den, audio, args.denoise)
             how += f", denoised at strength {args.denoise:g}"
-        return audio, voc.sampling_rate, how
+        return voc, {}, den, how
     from kokoro_ruslan_amd.griffinlim import GriffinLimVocoder
     gen = torch.Generator().manual_seed(args.griffin_lim_seed) if args.griffin_lim_seed is not None else None
-    voc = GriffinLimVocoder(device=engine.device)
-    return vocode(voc, mels, n_iter=args.griffin_lim_iters, generator=gen), voc.sampling_rate, f"Griffin-Lim, {args.griffin_lim_iters} iterations"
+    return (GriffinLimVocoder(device=device), dict(n_iter=args.griffin_lim_iters, generator=gen), None,
+            f"Griffin-Lim, {args.griffin_lim_iters} iterations")
+
+
+def vocode_all(args, engine, mels):
+    """(waveforms of the mels in input order, sample rate, what was done) with the vocoder the flags name, denoised with --denoise."""
+    from kokoro.inference.audio import denoise, vocode
+    voc, kwargs, den, how = load_vocoder(args, engine.device)
+    audio = vocode(voc, mels, **kwargs)
+    if den is not None:
+        audio = denoise(den, audio, args.denoise)
+    return audio, voc.sampling_rate, how
 
 
 def main(argv=None) -> int:
@@ -317,8 +339,7 @@ def main(argv=None) -> int:
     engine, controls, used = load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,
                                                 stop_threshold=args.stop_threshold, min_len_ratio=args.min_len_ratio,
                                                 min_len_floor=args.min_len_floor)
-    if args.griffin_lim and engine.dims.mel != 80:
-        parser.error(f"--griffin-lim needs an 80-mel model; this checkpoint makes {engine.dims.mel} mel channels")
+    check_vocoder_model(parser, args, engine.dims.mel)
     pkw = {} if prosody is None else {"prosody": prosody}
     if args.stream:
         mels = synthesize(engine, ids, stress, stream=True, slots=32 if args.slots is None else args.slots, **pkw, **controls.kwargs())

@@ -1,14 +1,20 @@
 """Free-running evaluation of a checkpoint: synthesize a set of utterances with the stop rule deciding, align every mel with its
 ground truth by dynamic time warping on the device (kokoro_ruslan_amd.dtw) and report what teacher-forced validation cannot see:
 MCD-DTW, the aligned mel L1, the length ratio, rows that ran into their generation bound, and the duration predictor's total error.
+With a vocoder the judgement goes on to the audio: every mel is vocoded (and denoised), the pitch and energy tracks of the waveforms
+are extracted on the device (kokoro_ruslan_amd.features) and compared with the ground truth's along the same alignment: the F0 error
+in cents, the voicing decision error, the gross pitch errors and the energy error.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+import math
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
-METRICS = ("mcd_dtw", "mel_l1_dtw", "len_ratio", "dur_abs_err")
+TRACK_METRICS = ("f0_rmse_cents", "f0_bias_cents", "gpe", "vuv_err", "energy_l1_dtw")
+TRACK_COUNTS = ("n_vv", "n_vu", "n_uv", "n_uu", "n_gpe")
+METRICS = ("mcd_dtw", "mel_l1_dtw", "len_ratio", "dur_abs_err") + TRACK_METRICS
 
 
 def _generate(engine, ids, stress, stream: bool, slots: int, batch_size: int, controls: Dict[str, Any], prosody=None):
@@ -39,35 +45,70 @@ def _generate(engine, ids, stress, stream: bool, slots: int, batch_size: int, co
 
 
 def summarize(records: Sequence[Dict]) -> Dict[str, Any]:
-    """{"utterances", "hit_bound_share", metric: {"mean", "median", "p95"}} over the records (a metric no record has is left out)."""
+    """{"utterances", "hit_bound_share", metric: {"mean", "median", "p95"}} over the records (a metric no record has is left out, a
+    record whose value is None does not count: an F0 error without a step voiced on both sides).  Records of an evaluation with a
+    vocoder carry "no_variance"; the summary then counts those that are (a cache written without pitch and energy)."""
     out: Dict[str, Any] = {"utterances": len(records),
                            "hit_bound_share": sum(bool(r["hit_bound"]) for r in records) / len(records) if records else 0.0}
     for k in METRICS:
-        v = [float(r[k]) for r in records if k in r]
+        v = [float(r[k]) for r in records if r.get(k) is not None]
         if v:
             t = torch.tensor(v, dtype=torch.float64)
             out[k] = {"mean": float(t.mean()), "median": float(torch.quantile(t, 0.5)), "p95": float(torch.quantile(t, 0.95))}
+    if any("no_variance" in r for r in records):
+        out["no_variance"] = sum(bool(r.get("no_variance")) for r in records)
     return out
+
+
+def _check_audio_args(N: int, vocoder, vocoder_kwargs, denoiser, denoise_strength, extractor, ref_pitch, ref_energy, want_audio) -> None:
+    if vocoder is None:
+        for what, v in (("vocoder_kwargs", vocoder_kwargs), ("denoiser", denoiser), ("extractor", extractor), ("ref_pitch", ref_pitch),
+                        ("ref_energy", ref_energy)):
+            if v is not None:
+                raise ValueError(f"{what} needs a vocoder: it bears on the audio metrics alone")
+        if want_audio:
+            raise ValueError("want_audio needs a vocoder")
+        return
+    if ref_pitch is None or ref_energy is None:
+        raise ValueError("a vocoder needs ref_pitch and ref_energy: the audio metrics compare against the ground truth's tracks")
+    for what, v in (("ref_pitch", ref_pitch), ("ref_energy", ref_energy)):
+        if len(v) != N:
+            raise ValueError(f"{what}: {len(v)} entries for {N} utterances")
+    if vocoder_kwargs is not None and not isinstance(vocoder_kwargs, dict):
+        raise ValueError("vocoder_kwargs must be a dict of keyword arguments for the vocoder's vocode()")
+    if denoiser is not None and not (isinstance(denoise_strength, (int, float)) and math.isfinite(denoise_strength) and denoise_strength >= 0):
+        raise ValueError(f"denoise_strength must be a finite number >= 0, not {denoise_strength!r}")
 
 
 def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]], ref_mels: Sequence[torch.Tensor], *,
              stream: bool = True, slots: int = 32, batch_size: int = 32, durations: Optional[Sequence[torch.Tensor]] = None,
-             names: Optional[Sequence[str]] = None, mcep: int = 13, aligner=None, prosody=None,
-             **controls) -> Tuple[List[Dict], Dict[str, Any]]:
+             names: Optional[Sequence[str]] = None, mcep: int = 13, aligner=None, prosody=None, vocoder=None,
+             vocoder_kwargs: Optional[Dict[str, Any]] = None, denoiser=None, denoise_strength: float = 0.005, extractor=None,
+             ref_pitch: Optional[Sequence[torch.Tensor]] = None, ref_energy: Optional[Sequence[torch.Tensor]] = None,
+             want_audio: bool = False,
+             **controls) -> Union[Tuple[List[Dict], Dict[str, Any]], Tuple[List[Dict], Dict[str, Any], List[torch.Tensor]]]:
     """Synthesize every utterance free-running (generate_stream with `slots` rows, or generate_batch `batch_size` at a time) and
     compare it with ref_mels[i] [frames, n_mels].  controls: the stop controls of generate_batch.  Returns (records, summary):
     per utterance {"name", "frames", "ref_frames", "len_ratio", "mcd_dtw" (dB), "mel_l1_dtw", "hit_bound" (the row ended at its
     generation bound, not by the stop rule)} and, with ground-truth `durations`, "dur_abs_err" = |sum predicted - sum true| frames;
     summarize() of them.  prosody: one kokoro_ruslan_amd.prosody.Prosody for every utterance or one per utterance (None: no controls):
-    with the ground-truth durations forced, dur_abs_err is 0 and the other metrics are the decoder's alone."""
+    with the ground-truth durations forced, dur_abs_err is 0 and the other metrics are the decoder's alone.
+    vocoder (a HifiganVocoder or GriffinLimVocoder; vocoder_kwargs go to its vocode()) adds the audio metrics: all mels are vocoded in
+    one call, denoised by `denoiser` at denoise_strength if one is given (its bias set), their pitch and energy extracted by
+    `extractor` (default: a FeatureExtractor on the engine's device) and compared with ref_pitch[i] / ref_energy[i] [ref frames] (the
+    cache's normalised tracks; both required) along the mel's alignment.  Records gain "f0_rmse_cents", "f0_bias_cents", "gpe" (None
+    when no step is voiced on both sides), "vuv_err", "energy_l1_dtw", the counts n_vv, n_vu, n_uv, n_uu, n_gpe
+    (MelAligner.align(tracks=)) and "no_variance": an utterance whose reference pitch and energy are all zero comes from a cache
+    written without them; it is marked and gets no track metrics.  want_audio=True returns (records, summary, waveforms)."""
     N = len(ids)
     if len(ref_mels) != N:
         raise ValueError(f"{len(ref_mels)} reference mels for {N} utterances")
     for what, v in (("stress", stress), ("durations", durations), ("names", names)):
         if v is not None and len(v) != N:
             raise ValueError(f"{what}: {len(v)} entries for {N} utterances")
+    _check_audio_args(N, vocoder, vocoder_kwargs, denoiser, denoise_strength, extractor, ref_pitch, ref_energy, want_audio)
     if N == 0:
-        return [], summarize([])
+        return ([], summarize([]), []) if want_audio else ([], summarize([]))
     if prosody is not None:
         from kokoro_ruslan_amd.prosody import as_list
         prosody = as_list(prosody, N)
@@ -75,7 +116,24 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
     if aligner is None:
         from kokoro_ruslan_amd.dtw import MelAligner
         aligner = MelAligner(device=engine.device, K=mcep)
-    aligned = aligner.align(mels, ref_mels)
+    audio, bare = None, None
+    if vocoder is None:
+        aligned = aligner.align(mels, ref_mels)
+    else:
+        from kokoro.inference.audio import denoise, vocode
+        from kokoro_ruslan_amd.dtw import MAX_FRAMES
+        audio = vocode(vocoder, mels, **(vocoder_kwargs or {}))
+        if denoiser is not None:
+            audio = denoise(denoiser, audio, denoise_strength)
+        if extractor is None:
+            from kokoro_ruslan_amd.features import FeatureExtractor
+            extractor = FeatureExtractor(device=engine.device)
+        feats = extractor.extract(audio, max_seq_length=MAX_FRAMES + 1)      # (T or T + 1 frames of a T-frame mel: never cut short)
+        aligned = aligner.align(mels, ref_mels, tracks={"pitch": ([f["pitch"] for f in feats], list(ref_pitch)),
+                                                        "energy": ([f["energy"] for f in feats], list(ref_energy))})
+        where = torch.as_tensor(ref_pitch[0]).device                             # (one read for all utterances, wherever the tracks lie)
+        bare = [n == 0 for n in torch.stack([(torch.count_nonzero(p) + torch.count_nonzero(e)).to(where)
+                                             for p, e in zip(ref_pitch, ref_energy)]).tolist()]
     records = []
     for i, (mel, al) in enumerate(zip(mels, aligned)):
         rec = {"name": names[i] if names is not None else i, "frames": int(mel.shape[0]), "ref_frames": int(ref_mels[i].shape[0]),
@@ -83,5 +141,9 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
                "hit_bound": int(mel.shape[0]) >= int(info["bounds"][i][2])}
         if durations is not None:
             rec["dur_abs_err"] = abs(float(info["durations"][i].sum()) - float(durations[i].sum()))
+        if bare is not None:
+            rec["no_variance"] = bare[i]
+            if not bare[i]:
+                rec.update({k: al[k] for k in TRACK_METRICS + TRACK_COUNTS})
         records.append(rec)
-    return records, summarize(records)
+    return (records, summarize(records), audio) if want_audio else (records, summarize(records))

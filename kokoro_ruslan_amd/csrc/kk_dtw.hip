@@ -19,6 +19,11 @@
 //   path_stats  one workgroup per pair: thread t takes the steps t, t + 256, ... of the path and the workgroup reduces the partial
 //               sums as a fixed tree.  These two sums are formed in fp64 from the fp32 cepstra / log-mels: a 13-term fp32 sum of
 //               squares alone can miss the one-ulp-per-step accuracy asked of them on a one-step path, and the launch is O(steps).
+//   track_stats the same walk over two scalar tracks per side (pitch and energy of the audio, kokoro.inference.evaluate): the voicing
+//               counts, the gross pitch errors, the sums of the F0 difference in cents and of its square over the steps voiced on
+//               both sides, the sum of |energy difference| over all steps.  Frequencies, differences and the comparisons are fp64
+//               with every operation rounded on its own (no contraction into fma), so the counts are those of any IEEE evaluation of
+//               the same expressions; only log2 is not correctly rounded, and it feeds the two cent sums alone.
 // Nothing a pair computes depends on the other pairs: every output is bit for bit what the pair gives alone.
 #include "kk_common.h"
 
@@ -196,6 +201,61 @@ __global__ __launch_bounds__(STATS_THREADS) void dtw_path_stats_kernel(const Sta
     }
 }
 
+struct TrackArgs {
+    const float *pa, *ea, *pb, *eb;           // normalised pitch and energy, [Ta_total] and [Tb_total]
+    const int *aoff, *boff;
+    const int *path;
+    const int64_t *poff;
+    const int *steps;
+    double f_lo, f_span, gpe_ratio;
+    int *counts;                              // [5][B]: n_vv, n_vu, n_uv, n_uu, n_gpe
+    double *sums;                             // [3][B]: sum c, sum c^2 (both voiced), sum |ea - eb| (all steps)
+    int B;
+};
+
+__global__ __launch_bounds__(STATS_THREADS) void dtw_track_stats_kernel(const TrackArgs a) {
+#pragma clang fp contract(off)                // f_lo + f_span p and gpe_ratio fb are a product rounded, then a sum / a comparison
+    __shared__ double red[3][STATS_THREADS];
+    __shared__ int cnt[5][STATS_THREADS];
+    const int b = blockIdx.x, n = a.steps[b];
+    const int a0 = a.aoff[b], Ta = a.aoff[b + 1] - a0, b0 = a.boff[b], Tb = a.boff[b + 1] - b0;
+    if (Ta < 1 || Tb < 1 || Ta > DTW_MAX || Tb > DTW_MAX || n < 1 || n > Ta + Tb - 1) return;      // (uniform: before any barrier)
+    const int *path = a.path + 2 * a.poff[b];
+    double sc = 0.0, sc2 = 0.0, se = 0.0;
+    int vv = 0, vu = 0, uv = 0, uu = 0, gpe = 0;
+    for (int s = threadIdx.x; s < n; s += STATS_THREADS) {
+        const int i = path[2 * s], j = path[2 * s + 1];
+        if ((unsigned)i >= (unsigned)Ta || (unsigned)j >= (unsigned)Tb) continue;                  // (nothing is read outside the pair)
+        const float p = a.pa[a0 + i], q = a.pb[b0 + j];
+        se += fabs((double)a.ea[a0 + i] - (double)a.eb[b0 + j]);
+        const bool va = p > 0.f, vb = q > 0.f;
+        if (va && vb) {
+            const double fa = a.f_lo + a.f_span * (double)p, fb = a.f_lo + a.f_span * (double)q;
+            const double c = 1200.0 * log2(fa / fb);
+            sc += c, sc2 += c * c;
+            ++vv;
+            if (fabs(fa - fb) > a.gpe_ratio * fb) ++gpe;
+        } else if (va) ++vu;
+        else if (vb) ++uv;
+        else ++uu;
+    }
+    const int t = threadIdx.x;
+    red[0][t] = sc, red[1][t] = sc2, red[2][t] = se;
+    cnt[0][t] = vv, cnt[1][t] = vu, cnt[2][t] = uv, cnt[3][t] = uu, cnt[4][t] = gpe;
+    __syncthreads();
+    for (int h = STATS_THREADS / 2; h > 0; h >>= 1) {
+        if (t < h) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) red[q][t] += red[q][t + h];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) cnt[q][t] += cnt[q][t + h];
+        }
+        __syncthreads();
+    }
+    if (t < 3) a.sums[(int64_t)t * a.B + b] = red[t][0];
+    if (t < 5) a.counts[(int64_t)t * a.B + b] = cnt[t][0];
+}
+
 }  // namespace
 
 extern "C" int kk_dtw_tile(void) { return DTW_W; }
@@ -240,5 +300,18 @@ extern "C" int kk_dtw_path_stats(const float *ca, int64_t Ta_total, const float 
     kk_note_kernel("dtw_path_stats");
     hipLaunchKernelGGL(dtw_path_stats_kernel, dim3(B), dim3(STATS_THREADS), 0, (hipStream_t)stream, r);
     KK_LAUNCH_CHECK("kk_dtw_path_stats");
+    return 0;
+}
+
+extern "C" int kk_dtw_track_stats(const float *pa, const float *ea, const float *pb, const float *eb, const int *aoff, const int *boff,
+                                  const int *path, const int64_t *poff, const int *steps, int B, double f_lo, double f_span,
+                                  double gpe_ratio, int *counts, double *sums, void *stream) {
+    KK_REQUIRE(pa && ea && pb && eb && aoff && boff && path && poff && steps && counts && sums && B > 0, "kk_dtw_track_stats: bad args");
+    KK_REQUIRE(f_span > 0.0 && f_lo > 0.0 && gpe_ratio >= 0.0, "kk_dtw_track_stats: f_lo = %g, f_span = %g, gpe_ratio = %g; needs f_lo, f_span > 0 and gpe_ratio >= 0",
+               f_lo, f_span, gpe_ratio);
+    TrackArgs r{pa, ea, pb, eb, aoff, boff, path, poff, steps, f_lo, f_span, gpe_ratio, counts, sums, B};
+    kk_note_kernel("dtw_track_stats");
+    hipLaunchKernelGGL(dtw_track_stats_kernel, dim3(B), dim3(STATS_THREADS), 0, (hipStream_t)stream, r);
+    KK_LAUNCH_CHECK("kk_dtw_track_stats");
     return 0;
 }

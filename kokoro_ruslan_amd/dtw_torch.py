@@ -6,11 +6,13 @@ Written from the definitions (DESIGN §5 "Alignment and free-running evaluation"
     D(0, 0) = d(0, 0),  D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1))    steps (1,1), (1,0), (0,1), unit weights, no band
 with the kernel's tie-break: the diagonal first, then (i-1, j), then (i, j-1), a later one only when strictly smaller.  The DP is
 vectorised along anti-diagonals, the cells of which are independent.  Cepstra are [T, K] here ([K][T] on the device).
+track_stats / track_metrics: the sums of two scalar tracks per side (normalised pitch, energy) along a path and the record fields made
+of them: voicing counts, gross pitch errors, the F0 difference in cents, the energy difference.
 """
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import Dict, Tuple
 
 import numpy as np
 
@@ -97,3 +99,37 @@ def path_stats(ca, cb, xa, xb, path) -> Tuple[float, float]:
     log-mels [T, M]; divided by the path's length they are MCD-DTW in dB and the aligned mel L1."""
     xa, xb, p = _f64(xa), _f64(xb), np.asarray(path, dtype=np.int64)
     return MCD_SCALE * path_cost(ca, cb, p), float(np.abs(xa[p[:, 0]] - xb[p[:, 1]]).mean(1).sum())
+
+
+F_LO, F_SPAN = 50.0, 800.0 - 50.0 + 1e-8          # features_torch.pitch_finish: p = (f - 50) / (800 - 50 + 1e-8), 0 when unvoiced
+GPE_RATIO = 0.2                                   # a gross pitch error: more than 20 % off the reference's F0
+TRACK_COUNTS = ("n_vv", "n_vu", "n_uv", "n_uu", "n_gpe")
+TRACK_SUMS = ("cents_sum", "cents_sq_sum", "energy_l1_sum")
+
+
+def track_stats(path, pa, pb, ea, eb, f_lo: float = F_LO, f_span: float = F_SPAN, gpe_ratio: float = GPE_RATIO) -> Dict[str, float]:
+    """The sums of kk_dtw_track_stats for one pair, along path [steps, 2], on the normalised pitch tracks pa [Ta], pb [Tb] and the
+    energy tracks ea, eb.  A frame is voiced iff p > 0, its frequency is f = f_lo + f_span p.  Returns the int counts n_vv (both
+    voiced), n_vu (a voiced, b not), n_uv, n_uu, n_gpe (both voiced and |fa - fb| > gpe_ratio fb) and the fp64 sums cents_sum,
+    cents_sq_sum of c = 1200 log2(fa / fb) over the steps voiced on both sides and energy_l1_sum of |ea[i] - eb[j]| over all steps."""
+    p = np.asarray(path, dtype=np.int64).reshape(-1, 2)
+    pa, pb, ea, eb = _f64(pa)[p[:, 0]], _f64(pb)[p[:, 1]], _f64(ea)[p[:, 0]], _f64(eb)[p[:, 1]]
+    va, vb = pa > 0.0, pb > 0.0
+    vv = va & vb
+    fa, fb = f_lo + f_span * pa[vv], f_lo + f_span * pb[vv]
+    c = 1200.0 * np.log2(fa / fb)
+    return {"n_vv": int(vv.sum()), "n_vu": int((va & ~vb).sum()), "n_uv": int((~va & vb).sum()), "n_uu": int((~va & ~vb).sum()),
+            "n_gpe": int((np.abs(fa - fb) > gpe_ratio * fb).sum()), "cents_sum": float(c.sum()), "cents_sq_sum": float((c * c).sum()),
+            "energy_l1_sum": float(np.abs(ea - eb).sum())}
+
+
+def track_metrics(stats: Dict[str, float], steps: int) -> Dict[str, object]:
+    """What a record carries of track_stats' sums over a path of `steps` cells: f0_rmse_cents = sqrt(mean c^2), f0_bias_cents =
+    mean c and gpe = n_gpe / n_vv over the steps voiced on both sides (None when there is none), vuv_err = (n_vu + n_uv) / steps,
+    energy_l1_dtw = mean |ea - eb|, and the counts themselves."""
+    n = int(stats["n_vv"])
+    out = {"f0_rmse_cents": math.sqrt(stats["cents_sq_sum"] / n) if n else None, "f0_bias_cents": stats["cents_sum"] / n if n else None,
+           "gpe": int(stats["n_gpe"]) / n if n else None, "vuv_err": (int(stats["n_vu"]) + int(stats["n_uv"])) / steps,
+           "energy_l1_dtw": stats["energy_l1_sum"] / steps}
+    out.update({k: int(stats[k]) for k in TRACK_COUNTS})
+    return out
