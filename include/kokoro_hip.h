@@ -295,7 +295,8 @@ int kk_frame_mask(const int64_t *lens, uint8_t *mask, int B, int T, void *stream
 int kk_im2col3_fwd(const float *x, float *col, int B, int L, int C, int chunk, int col_bf16, void *stream);
 int kk_im2col3_bwd(const float *dcol, float *dx, int B, int L, int C, int chunk, int dcol_bf16, void *stream);
 /* GroupNorm(1,C) over (C x chunk frames) per sample per chunk + ReLU; chunks with < 2 frames yield zeros.
- * stats [B*nchunks, 2] = (mean, rstd). */
+ * stats [B*nchunks, 2] = (mean, rstd).  scratch: 2*B*nchunks doubles, shared by the forward and the backward: each zeroes it when it
+ * starts and hands it back zeroed. */
 int kk_groupnorm_relu_fwd(const float *x, const float *gamma, const float *beta, float *y, float *stats,
                           double *scratch, int B, int L, int C, int chunk, const uint32_t *seed, uint32_t site,
                           float p, void *stream);

@@ -405,13 +405,16 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float *__restrict
     }
 }
 
-__global__ void gn_finalize_kernel(const double *__restrict__ scratch, float *__restrict__ stats, int L, int C, int chunk,
+// The only reader of the forward's sums: it hands the scratch back zeroed (the forward and the backward share the buffer).
+__global__ void gn_finalize_kernel(double *__restrict__ scratch, float *__restrict__ stats, int L, int C, int chunk,
                                    int nch, int total) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const double n = (double)chunk_frames(L, chunk, i % nch) * C;
     const double mean = scratch[i * 2] / n;
     double var = scratch[i * 2 + 1] / n - mean * mean;
+    scratch[i * 2] = 0.0;
+    scratch[i * 2 + 1] = 0.0;
     if (var < 0) var = 0;
     stats[i * 2] = (float)mean;
     stats[i * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
@@ -753,5 +756,5 @@ extern "C" int kk_groupnorm_relu_bwd(const float *dy, const float *x, const floa
         hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, dim3(blocks), dim3(256), 0, s, dy, x, y, gamma, stats, scratch, dx, total4, L, C,
                            chunk, nch, inv_keep);
     KK_LAUNCH_CHECK("kk_groupnorm_relu_bwd");
-    return 0;
+    return kk_zero_async(scratch, sizeof(double) * 2 * total, s);     // every thread of the apply pass read it: zeroed again behind it
 }
