@@ -420,12 +420,26 @@ int kk_slot_admit(const void *kv_src, void *kv_pool, const uint8_t *fm_src, uint
  * prosody_variance: pitch, energy [B, T] = the predictors' outputs; idx [B, T], lens [B] (int64) as kk_length_regulate_index wrote
  *   them.  c = clamp(pred, 0, 1).  Frame t < lens[b] of phoneme j = idx[b, t]: pitch_out = fp[b, j] when that is not NaN, else
  *   clamp(c * ps[b, j] + pb[b, j], 0, 1) when c > 0, else c (an unvoiced frame stays unvoiced); energy_out = fe[b, j] when that is not
- *   NaN, else clamp(c * es[b, j] + eb[b, j], 0, 1).  The product and the sum round separately (no fma).  Frames t >= lens[b] get c. */
+ *   NaN, else clamp(c * es[b, j] + eb[b, j], 0, 1).  The product and the sum round separately (no fma).  Frames t >= lens[b] get c.
+ * prosody_contour: prosody_variance with a frame-level source track per row on top.  dur int64 [B, Pn] = the durations
+ *   kk_length_regulate_index saw; sd int32 [B, Pn] >= 0 = the source frames of each phoneme; pc, ec fp32 [B, Sn] = the pitch / energy
+ *   source tracks in [0, 1], NaN = not given at this frame (either pointer may be NULL: no such track in the batch).  With cs_t, cs_s
+ *   the exclusive prefix sums of the row's dur and sd, frame t < lens[b] of phoneme j = idx[b, t] has n = dur[b, j], m = sd[b, j],
+ *   k = t - cs_t[j] and, when m > 0, the source frame s = cs_s[j] + floor((2k + 1) m / (2n)) (int64): the centre-aligned nearest one,
+ *   the identity when n == m.  Pitch: when m > 0 and v = pc[b, s] is not NaN, pitch_out = v > 0 ? clamp(v * ps[b, j] + pb[b, j], 0, 1)
+ *   : v (an unvoiced source frame stays unvoiced; product and sum round separately); otherwise prosody_variance's value.  Energy: when
+ *   m > 0 and v = ec[b, s] is not NaN, energy_out = clamp(v * es[b, j] + eb[b, j], 0, 1); otherwise prosody_variance's value.  Frames
+ *   t >= lens[b] get c.  Precedence: contour, per-phoneme forced value, the model.  A row with sd all 0 (or NaN tracks) gives the bits
+ *   of prosody_variance; a row's output depends on its own row only.  One workgroup per row with both prefix sums in LDS: Pn <= 4096
+ *   and Sn <= 4096; beyond either every row gets c and the call returns KK_EINVAL.  s outside [0, Sn) counts as not given. */
 int kk_prosody_durations(const float *d, const float *speed, const int *forced, const int *plens, int64_t *dur_out, int64_t *sums_out,
                          int B, int Pn, void *stream);
 int kk_prosody_variance(const float *pitch, const float *energy, const int64_t *idx, const int64_t *lens, const float *ps, const float *pb,
                         const float *es, const float *eb, const float *fp, const float *fe, float *pitch_out, float *energy_out, int B,
                         int Pn, int T, void *stream);
+int kk_prosody_contour(const float *pitch, const float *energy, const int64_t *idx, const int64_t *lens, const float *ps, const float *pb,
+                       const float *es, const float *eb, const float *fp, const float *fe, const int64_t *dur, const int *sd,
+                       const float *pc, const float *ec, float *pitch_out, float *energy_out, int B, int Pn, int T, int Sn, void *stream);
 
 /* ---- HiFi-GAN vocoder (kokoro_ruslan_amd/vocoder.py; kk_vocoder.hip): mels -> waveforms for a packed batch ----
  * Activations are channels-last fp32 [rows, C]; the utterances are packed back to back along time and seg[0..nseg] holds their

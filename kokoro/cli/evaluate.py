@@ -3,7 +3,7 @@
     kokoro-eval --checkpoint CKPT --features CACHE_DIR [--indices ...] [--split val|train|all] [--validation-split 0.1]
                 [--weights auto|ema|model] [--math bf16|f32] [--no-stream] [--slots N] [--batch-size N] [--mcep K]
                 [--stop-threshold X] [--max-len N] [--min-len-ratio R] [--min-len-floor N] [--output REPORT.json]
-                [--oracle-durations]
+                [--oracle-durations] [--oracle-prosody]
                 [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
                 [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]] [--gpe-ratio F]
 
@@ -15,8 +15,13 @@ durations - sum of true ones|, frames); plus the share of utterances that ran in
 utterances `kokoro-train --validation-split` holds out (the same draw: kokoro.data.cached.split_indices), --indices names utterances
 of the cache's length-sorted order instead.  --output writes records, summary, controls and the weights used as JSON.
 --oracle-durations forces the cache's phoneme_durations on every utterance (kokoro_ruslan_amd.prosody): dur_abs_err is then 0 and
-len_ratio, mcd_dtw and mel_l1_dtw show the decoder alone, without the duration predictor's errors.  An utterance whose cache entry
-holds no durations for its phonemes is an error that names it.
+len_ratio, mcd_dtw and mel_l1_dtw are free of the duration predictor's errors; the pitch and energy predictors still run.  An
+utterance whose cache entry holds no durations for its phonemes is an error that names it.
+--oracle-prosody (implies --oracle-durations) also forces the cache entry's frame-level pitch and energy on every frame
+(Prosody.from_tracks: the condition the decoder was trained on), so that the three numbers show the decoder alone; the differences
+none -> --oracle-durations -> --oracle-prosody split the error into the duration predictor's share, the pitch and energy predictors'
+share and the decoder's.  An utterance without durations, or whose cached pitch and energy are all zero (a --no-variance cache), is an
+error that names it.
 --vocoder / --griffin-lim (kokoro-synth's flags and loaders; --denoise with --vocoder) judge the audio too: every mel is vocoded, the
 pitch and energy of the waveforms are extracted on the device (kokoro_ruslan_amd.features) and compared with the cache entry's own
 pitch and energy along the same alignment.  The report then also carries f0_rmse_cents and f0_bias_cents (root mean square and mean
@@ -55,6 +60,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--min-len-floor", type=int, default=None)
     p.add_argument("--output", metavar="REPORT.json", default=None)
     p.add_argument("--oracle-durations", action="store_true", help="synthesize on the cache's phoneme_durations instead of the predicted ones")
+    # (leaves no attribute behind when it is not given: an invocation without it parses as it always did)
+    p.add_argument("--oracle-prosody", action="store_true", default=argparse.SUPPRESS,
+                   help="also force the cache's frame-level pitch and energy (implies --oracle-durations)")
     from kokoro.cli.synth import add_vocoder_flags
     add_vocoder_flags(p)
     p.add_argument("--gpe-ratio", type=float, default=0.2, metavar="F",
@@ -85,6 +93,8 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--gpe-ratio needs --vocoder or --griffin-lim: it bears on the audio's F0")
     if not math.isfinite(args.gpe_ratio) or args.gpe_ratio < 0:
         p.error("--gpe-ratio must be >= 0")
+    if getattr(args, "oracle_prosody", False):
+        args.oracle_durations = True
 
 
 def select_indices(n: int, split: Optional[str], validation_split: float, indices: Optional[List[int]]) -> List[int]:
@@ -117,14 +127,22 @@ def read_features(cache_dir: str, split: Optional[str], validation_split: float,
     return names, ids, stress, mels, durs, pitch, energy
 
 
-def oracle_prosody(names, ids, durs):
-    """One Prosody per utterance that forces the cache's durations; ValueError names an utterance that has none for its phonemes."""
+def oracle_prosody(names, ids, durs, pitch=None, energy=None):
+    """One Prosody per utterance that forces the cache's durations; ValueError names an utterance that has none for its phonemes.
+    With pitch and energy (--oracle-prosody: the cache's frame-level tracks) they are forced too, frame by frame; ValueError names
+    an utterance whose tracks are all zero (a cache written with --no-variance)."""
     from kokoro_ruslan_amd.prosody import Prosody
+    flag = "--oracle-durations" if pitch is None else "--oracle-prosody"
     out = []
-    for name, u, dur in zip(names, ids, durs):
+    for i, (name, u, dur) in enumerate(zip(names, ids, durs)):
         if dur is None or dur.numel() != u.numel() or dur.numel() == 0 or bool((dur < 0).any()):
-            raise ValueError(f"--oracle-durations: utterance {name} has no durations for its {int(u.numel())} phonemes in the cache")
-        out.append(Prosody(durations=dur.to(torch.int64)).validate(int(u.numel())))
+            raise ValueError(f"{flag}: utterance {name} has no durations for its {int(u.numel())} phonemes in the cache")
+        if pitch is None:
+            out.append(Prosody(durations=dur.to(torch.int64)).validate(int(u.numel())))
+            continue
+        if not bool((pitch[i] != 0).any()) and not bool((energy[i] != 0).any()):
+            raise ValueError(f"{flag}: utterance {name} has no pitch and energy in the cache (written with --no-variance)")
+        out.append(Prosody.from_tracks(dur, pitch[i].clamp(0.0, 1.0), energy[i].clamp(0.0, 1.0)).validate(int(u.numel())))
     return out
 
 
@@ -146,7 +164,7 @@ def main(argv=None) -> int:
     pkw = {}
     if args.oracle_durations:
         try:
-            pkw["prosody"] = oracle_prosody(names, ids, durs)
+            pkw["prosody"] = oracle_prosody(names, ids, durs, *((pitch, energy) if getattr(args, "oracle_prosody", False) else ()))
         except ValueError as e:
             parser.error(str(e))
     how = ""
@@ -174,6 +192,7 @@ def main(argv=None) -> int:
             json.dump({"records": records, "summary": summary, "controls": controls.kwargs(), "weights": used, "mcep": args.mcep,
                        "split": "indices" if args.indices is not None else (args.split or "val"), "checkpoint": args.checkpoint,
                        **({"oracle_durations": True} if args.oracle_durations else {}),
+                       **({"oracle_prosody": True} if getattr(args, "oracle_prosody", False) else {}),
                        **({"audio": how, "gpe_ratio": args.gpe_ratio} if audio else {})}, f, indent=1)
         print(f"kokoro-eval: report -> {args.output}")
     return 0

@@ -7,6 +7,7 @@
                  [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]]
                  [--loudness [LUFS] [--peak-db DB]]
                  [--speed F] [--pitch-scale F] [--pitch-shift F] [--energy-scale F] [--energy-shift F]
+                 [--copy-prosody [durations|pitch|energy ...]]
                  [--documents [--gap-ms F] [--fade-ms F]] [--report FILE.json]
 
 Writes <name>.npy per utterance: float32 [n_mels, frames], the vocoder's layout (reference inference/inference.py:623-631).
@@ -27,7 +28,13 @@ written; the .wav then keeps that level instead of being peak-normalised.  A wav
 --speed / --pitch-scale / --pitch-shift / --energy-scale / --energy-shift steer every utterance (kokoro_ruslan_amd.prosody.Prosody:
 frames per phoneme divided by the speed, in [0.25, 4]; scale and shift on the normalised pitch of voiced frames and on the normalised
 energy).  A line of --ids may carry "prosody": {...} with the fields of Prosody.from_json (also per-phoneme lists and forced
-"durations" / "pitch" / "energy"); its fields override the flags for that line.
+"durations" / "pitch" / "energy", and the frame-level "pitch_contour" / "energy_contour" / "contour_durations"); its fields override
+the flags for that line.
+--copy-prosody (with --features) synthesizes every cache utterance with its recording's prosody (Prosody.from_tracks): the cache
+entry's phoneme durations forced and its frame-level pitch and energy put on every frame; named parts (durations, pitch, energy)
+copy only those, e.g. `--copy-prosody pitch` carries the recording's intonation onto the model's own durations.  The other prosody
+flags apply on top (--pitch-shift transposes the copied contour).  An utterance without durations in the cache, or asked for a track
+the cache holds only zeros of (--no-variance), is an error that names it.
 --documents (with --ids and --vocoder or --griffin-lim) is long-form synthesis, the last stretch of the reference's text_to_speech
 (:566-648): a line of --ids may carry "document": "NAME"; the lines of one document are its chunks, played in file order, and a line
 without the field is a document of its own named by its "name".  All chunks of all documents are synthesized in the one call, every mel
@@ -90,6 +97,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pitch-shift", type=float, default=argparse.SUPPRESS, metavar="F", help="added to the normalised pitch of voiced frames")
     p.add_argument("--energy-scale", type=float, default=argparse.SUPPRESS, metavar="F", help="factor on the normalised energy (>= 0)")
     p.add_argument("--energy-shift", type=float, default=argparse.SUPPRESS, metavar="F", help="added to the normalised energy")
+    p.add_argument("--copy-prosody", nargs="*", choices=COPY_PARTS, default=argparse.SUPPRESS, metavar="PART",
+                   help="with --features: force the recording's durations, pitch and energy (default all three) on every utterance")
     # (the long-form flags too leave no attribute behind when they are not given: long_form() reads them)
     p.add_argument("--documents", action="store_true", default=argparse.SUPPRESS,
                    help='long-form: join the chunks that share a "document" field of --ids into one <document>.wav')
@@ -97,6 +106,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--fade-ms", type=float, default=argparse.SUPPRESS, metavar="F", help="fade every chunk in and out over F ms (default 0: none)")
     p.add_argument("--report", metavar="FILE.json", default=argparse.SUPPRESS, help="write the per-chunk health check of mels and audio")
     return p
+
+
+COPY_PARTS = ("durations", "pitch", "energy")
 
 
 def check_vocoder_flags(p: argparse.ArgumentParser, args) -> None:
@@ -139,6 +151,8 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         prosody_flags(args)
     except ValueError as e:
         p.error(str(e))
+    if hasattr(args, "copy_prosody") and not args.features:
+        p.error("--copy-prosody needs --features: the recorded prosody is the cache's")
     if args.slots is not None and not args.stream:
         p.error("--slots needs --stream")
     if args.slots is not None and args.slots < 1:
@@ -202,6 +216,35 @@ def read_prosody(path: str, flags: dict):
     return out if any_given else None
 
 
+def copy_parts(args) -> Tuple[str, ...]:
+    """The parts --copy-prosody names (all three when it names none), () when the flag is not given."""
+    if not hasattr(args, "copy_prosody"):
+        return ()
+    return tuple(k for k in COPY_PARTS if k in args.copy_prosody) or COPY_PARTS
+
+
+def copied_prosody(names, ids, durs, pitch, energy, parts, flags: dict):
+    """One Prosody per cache utterance that carries the recorded `parts` (Prosody.from_tracks) under the command line's flags;
+    ValueError names an utterance whose cache entry lacks what is asked for."""
+    from kokoro_ruslan_amd.prosody import Prosody
+    out = []
+    for name, u, dur, f0, en in zip(names, ids, durs, pitch, energy):
+        if dur is None or dur.numel() != u.numel() or dur.numel() == 0 or bool((dur < 0).any()):
+            raise ValueError(f"--copy-prosody: utterance {name} has no durations for its {int(u.numel())} phonemes in the cache")
+        tracks = {}
+        for part, t in (("pitch", f0), ("energy", en)):
+            if part in parts:
+                if not bool((t != 0).any()):
+                    raise ValueError(f"--copy-prosody: utterance {name} has no {part} in the cache (written with --no-variance)")
+                tracks[part] = t.float().reshape(-1).clamp(0.0, 1.0)
+        try:
+            out.append(Prosody.from_tracks(dur, tracks.get("pitch"), tracks.get("energy"), force_durations="durations" in parts,
+                                           **flags).validate(int(u.numel())))
+        except ValueError as e:
+            raise ValueError(f"--copy-prosody: utterance {name}: {e}") from None
+    return out
+
+
 def long_form(args) -> Tuple[bool, float, float, Optional[str]]:
     """(--documents, --gap-ms, --fade-ms, --report) with their defaults where a flag was not given."""
     return getattr(args, "documents", False), getattr(args, "gap_ms", 150.0), getattr(args, "fade_ms", 0.0), getattr(args, "report", None)
@@ -238,16 +281,21 @@ def read_documents(path: str) -> Tuple[List[str], List[List[int]]]:
     return docs, [members[d] for d in docs]
 
 
-def read_features(cache_dir: str, indices=None) -> Tuple[List[str], List[torch.Tensor], List[torch.Tensor]]:
+def read_features(cache_dir: str, indices=None, tracks: bool = False):
+    """(names, ids, stress) of the cache's utterances; with tracks also (durations, pitch [T], energy [T]) of every one."""
     from kokoro.data.cached import CachedFeatureDataset
     ds = CachedFeatureDataset(cache_dir, indices=indices, memory_cache=False)
-    names, ids, stress = [], [], []
+    names, ids, stress, durs, pitch, energy = [], [], [], [], [], []
     for i in range(len(ds)):
         it = ds[i]
         names.append(os.path.splitext(ds.samples[i]["file"].name)[0])
         ids.append(it["phoneme_indices"].to(torch.int64))
         stress.append(it["stress_indices"].to(torch.int64))
-    return names, ids, stress
+        if tracks:
+            durs.append(it["phoneme_durations"].to(torch.int64))
+            pitch.append(it["pitch"].float().reshape(-1))
+            energy.append(it["energy"].float().reshape(-1))
+    return (names, ids, stress, durs, pitch, energy) if tracks else (names, ids, stress)
 
 
 def level_and_write(args, names, audio, sample_rate: int, device) -> str:
@@ -331,9 +379,17 @@ def main(argv=None) -> int:
         names, ids, stress = read_ids(args.ids)
         prosody = read_prosody(args.ids, flags)
     else:
-        names, ids, stress = read_features(args.features, args.indices)
-        prosody = None
-        if flags:
+        parts = copy_parts(args)
+        if parts:
+            names, ids, stress, durs, pitch, energy = read_features(args.features, args.indices, tracks=True)
+            try:
+                prosody = copied_prosody(names, ids, durs, pitch, energy, parts, flags)
+            except ValueError as e:
+                parser.error(str(e))
+        else:
+            names, ids, stress = read_features(args.features, args.indices)
+            prosody = None
+        if flags and not parts:
             from kokoro_ruslan_amd.prosody import Prosody
             prosody = Prosody.from_json(flags, 1)              # (scalars only: one entry serves every utterance)
     engine, controls, used = load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,

@@ -33,6 +33,7 @@ from . import lib as kk
 from . import spec
 from .prosody import as_list as prosody_list
 from .prosody import pack as pack_prosody
+from .prosody import pack_contours
 from .spec import VA, ModelDims, StepHyper
 
 CHUNK = 512   # variance_predictor.py:77
@@ -1871,13 +1872,15 @@ class KokoroEngine:
         y1 = self._ln_fwd(lay0.key + ".ln1", x, lay0.prefix + ".norm1", edt)
         return self._encoder_layers_fwd(ns, 0, x, y1, B, Pn, text_mask)[1]
 
-    def _expand_fwd(self, ns, enc, dur, B, Pn, T, flens=None, controls=None):
+    def _expand_fwd(self, ns, enc, dur, B, Pn, T, flens=None, controls=None, contours=None):
         """The variance adaptor behind the durations, without targets (variance_predictor.py:338-439): repeat phoneme p of
         each row dur[b, p] times up to T frames, predict pitch and energy, add the bucket embeddings of the clamped predictions,
         and project the result to the cross-attention K|V of every decoder layer (_cross_kv_fwd_all under `ns`).  flens (int32
         [B]) makes the predictors see row b as a sequence of flens[b] frames; None = the padded batch as one.  Workspace keys
         `ns` + "lr.* / va.* / vp.* / out.*".  controls (prosody.PackedProsody, or None: none): kk_prosody_variance puts the
-        per-phoneme pitch / energy controls on the clamped predictions in front of the bucket embeddings.
+        per-phoneme pitch / energy controls on the clamped predictions in front of the bucket embeddings.  contours
+        (prosody.PackedContours, or None: no row has one; needs controls): kk_prosody_contour in its place, which also puts the rows'
+        frame-level source tracks on the frames that `dur` gave their phonemes.
         Returns (memory [B*T, H], fm2 = the frame mask [B, T])."""
         d, P, H, ddt = self.dims, self.arena.P, self.dims.hidden, self.dec_dt
         Nd = B * T
@@ -1905,8 +1908,13 @@ class KokoroEngine:
                     pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
         else:
             c, pc, ec = controls, torch.empty_like(pitch), torch.empty_like(energy)
-            kk.call("kk_prosody_variance", pitch, energy, idx, lens, c.pitch_ss[0], c.pitch_ss[1], c.energy_ss[0], c.energy_ss[1],
-                    c.pitch, c.energy, pc, ec, B, Pn, T)
+            if contours is None:
+                kk.call("kk_prosody_variance", pitch, energy, idx, lens, c.pitch_ss[0], c.pitch_ss[1], c.energy_ss[0], c.energy_ss[1],
+                        c.pitch, c.energy, pc, ec, B, Pn, T)
+            else:
+                src = contours.pitch if contours.pitch is not None else contours.energy
+                kk.call("kk_prosody_contour", pitch, energy, idx, lens, c.pitch_ss[0], c.pitch_ss[1], c.energy_ss[0], c.energy_ss[1],
+                        c.pitch, c.energy, dur, contours.src_dur, contours.pitch, contours.energy, pc, ec, B, Pn, T, src.shape[1])
             kk.call("kk_bucket_embed_add_fwd", xf, pc, ec, P[f"{VA}.pitch_bins"],
                     P[f"{VA}.energy_bins"], P[f"{VA}.pitch_embedding.weight"], P[f"{VA}.energy_embedding.weight"], lens, memory,
                     pidx, eidx, fm2, B, T, H, d.var_bins, _b16(memory))
@@ -2003,7 +2011,9 @@ class KokoroEngine:
         ids = ids.to(self.device, torch.int64).contiguous()
         stress = stress.to(self.device, torch.int64).contiguous() if stress is not None else None
         B, Pn = ids.shape
-        controls = None if prosody is None else pack_prosody(prosody_list(prosody, B, "rows"), [Pn] * B, Pn, self.device)
+        prosody = prosody_list(prosody, B, "rows")
+        controls = None if prosody is None else pack_prosody(prosody, [Pn] * B, Pn, self.device)
+        contours = pack_contours(prosody, [Pn] * B, Pn, self.device)
         with self._no_dropout():
             text_mask = self._buf("gen.text_mask", B, Pn, dtype=torch.uint8)
             enc = self._encode_text_fwd("", ids, stress, B, Pn, text_mask)
@@ -2020,7 +2030,7 @@ class KokoroEngine:
             expected = T = max(int(sums.max()), 3)                 # (host sync: the expanded length sizes everything below)
             if T > d.max_len:
                 raise ValueError(f"predicted length {T} exceeds the positional table ({d.max_len})")
-            memory, fm2 = self._expand_fwd("", enc, dur, B, Pn, T, controls=controls)
+            memory, fm2 = self._expand_fwd("", enc, dur, B, Pn, T, controls=controls, contours=contours)
             min_expected, _, max_expected = self._generation_bounds(expected, max_len, min_len_ratio, min_len_floor, max_len_ratio,
                                                                     max_len_cap)
             mel_out, stop_logit, t_dev = self._decode_state_init("gen", B, max_expected)
@@ -2070,11 +2080,13 @@ class KokoroEngine:
         """Everything of a ragged batch in front of the decode loop, on the workspace keys under `ns`: pad, encode, the duration
         predictor over each row's own phonemes, the expansion with each row's own frame count (_expand_fwd(flens=...)).  Error
         messages name utterance `first` + row; frame_limit: a row predicted longer raises before anything is expanded.
-        prosody: one Prosody or None per row, or None for no controls at all (then neither prosody kernel is launched).
+        prosody: one Prosody or None per row, or None for no controls at all (then no prosody kernel is launched); a row's
+        frame-level contour is packed with the rows it is prefilled with (pack_contours) and so goes wherever the row goes.
         Returns (dur [B, Pn], T_b, T = max(T_b), memory, fm2)."""
         d, H = self.dims, self.dims.hidden
         B, Pn = len(utterances), max(lens_p)
         controls = None if prosody is None else pack_prosody(prosody, lens_p, Pn, self.device)
+        contours = pack_contours(prosody, lens_p, Pn, self.device)       # (None unless a row carries a frame-level contour)
         ids_h = torch.zeros(B, Pn, dtype=torch.int64)
         st_h = torch.zeros(B, Pn, dtype=torch.int64) if stress is not None else None
         for b, u in enumerate(utterances):
@@ -2107,7 +2119,7 @@ class KokoroEngine:
                 raise ValueError(f"utterance {first + b}: predicted length {tb} exceeds slot_frames ({frame_limit})")
         T = max(Tb)
         memory, fm2 = self._expand_fwd(ns, enc, dur, B, Pn, T, flens=torch.tensor(Tb, dtype=torch.int32).to(self.device),
-                                       controls=controls)
+                                       controls=controls, contours=contours)
         return dur, Tb, T, memory, fm2
 
     @torch.no_grad()
@@ -2132,7 +2144,9 @@ class KokoroEngine:
 
         prosody: one prosody.Prosody for every utterance or one per utterance (None entries: neutral); None: no controls, the
         launches issued without this argument.  The controls act in the prefill only (durations, then pitch / energy per frame), so a row still equals what it
-        gets alone under the same controls, and "durations" of want_info are the ones used."""
+        gets alone under the same controls, and "durations" of want_info are the ones used.  A Prosody with a frame-level contour
+        (pitch_contour / energy_contour) makes the prefill launch kk_prosody_contour in place of kk_prosody_variance; without one in
+        the batch the launches are those of per-phoneme controls."""
         d, H, M = self.dims, self.dims.hidden, self.dims.mel
         B = len(utterances)
         if B == 0:

@@ -240,6 +240,7 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_slot_admit": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _I, _P],
     "kk_prosody_durations": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
     "kk_prosody_variance": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "kk_prosody_contour": [_P] * 16 + [_I, _I, _I, _I, _P],
     "kk_voc_conv1d": [_P, _L, _I, _P, _I, _I, _P, _P, _I, _I, _I, _F, _P, _I, _P, _P, _I, _I, _P],
     "kk_voc_convt1d": [_P, _L, _I, _P, _I, _I, _P, _P, _I, _I, _I, _F, _P, _I, _I, _P],
     "kk_voc_convt_taps": [_I, _I, _P],
