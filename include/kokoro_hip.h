@@ -602,6 +602,25 @@ int kk_dtw_track_stats(const float *pa, const float *ea, const float *pb, const 
                        const int *path, const int64_t *poff, const int *steps, int B, double f_lo, double f_span, double gpe_ratio,
                        int *counts, double *sums, void *stream);
 
+/* ---- spectral distance of waveform pairs along their DTW paths (kokoro_ruslan_amd/spectral.py; kk_spectral.hip) ----
+ * Side a (synthesized) and side b (the recording): fp32 waveforms packed back to back, woffa / woffb int64 [B + 1] sample offsets,
+ * every waveform 1024 .. 2^31 - 1025 samples, read as x / (peak + 1e-9) with peaka / peakb [B] = max |x| (kk_feat_peak).  path, poff,
+ * steps, aoff, boff: kk_dtw_backtrack's; frame i is centred on sample 256 i with reflect padding by index.  A step is skipped when i is
+ * outside [0, Ta), j outside [0, Tb), or 256 i > samples of a (256 j > samples of b): nothing is read for it, whatever the path holds.
+ * win: fp64 [3][1024], a periodic Hann of 256, 512, 1024 centred in the frame; tw: fp64 [1024][2], exp(-2 pi i j / 1024).  At each counted
+ * step and window, over the 513 bins of A = |STFT(a)|[i], B = |STFT(b)|[j] (samples, transforms and sums all fp64): sums fp64 [15][B], row 5 w + {0: sum A B, 1: sum A^2,
+ * 2: sum B^2, 3: sum d, 4: sum d^2}, d = 10 log10((A^2 + 1e-9) / (B^2 + 1e-9)); counts int32 [2][B] = counted steps, skipped steps.
+ * tiles: int32 [ntiles][2] = {pair, first step (a multiple of kk_dtw_spectral_tile())}, pair-major and ascending, covering the
+ * poff[b + 1] - poff[b] entries each pair has room for; toff: int32 [B + 1], the first tile of each pair.  part (fp64 [ntiles][15]) and
+ * part_counts (int32 [ntiles][2]) hold the tiles' partial sums, which a second launch adds per pair in ascending tile order.  Every
+ * sum is formed in fp64 in an order fixed by the pair's own step count: no output of a pair depends on the batch. */
+/* path steps of one tile */
+int kk_dtw_spectral_tile(void);
+int kk_dtw_spectral_stats(const float *wa, const int64_t *woffa, const float *peaka, const float *wb, const int64_t *woffb,
+                          const float *peakb, const int *aoff, const int *boff, const int *path, const int64_t *poff, const int *steps,
+                          int B, const int *tiles, int ntiles, const int *toff, const double *win, const void *tw, double *part,
+                          int *part_counts, double *sums, int *counts, void *stream);
+
 /* ---- flat-start forced alignment of phoneme tokens to mel frames (kokoro_ruslan_amd/align.py; kk_align.hip) ----
  * A ragged batch of B utterances: frames packed back to back, foff: int32 [B + 1]; tokens packed back to back, poff: int32 [B + 1].
  * 1 <= P <= kk_align_max_tokens(), 1 <= T <= 4096 (the caller checks; an utterance outside is skipped).  feats, viterbi and backtrack

@@ -6,6 +6,7 @@
                 [--oracle-durations] [--oracle-prosody]
                 [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
                 [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]] [--gpe-ratio F]
+                [--wavs DIR [--copy-synthesis]]
 
 Synthesizes every selected utterance with the stop rule deciding its length (continuous batching in a pool of --slots rows, or with
 --no-stream in batches of --batch-size), aligns each mel with the cached ground truth by dynamic time warping on K mel cepstra and
@@ -28,7 +29,16 @@ pitch and energy along the same alignment.  The report then also carries f0_rmse
 of 1200 log2(f_syn / f_true) over the steps voiced on both sides), gpe (the share of those steps whose F0 is more than --gpe-ratio,
 default 0.2, off the true one), vuv_err (the share of steps voiced on one side only) and energy_l1_dtw (mean |difference| of the
 normalised energies).  An utterance whose cached pitch and energy are all zero (a cache written with --no-variance) gets none of them
-and is counted in the summary line."""
+and is counted in the summary line.
+--wavs DIR (with --vocoder or --griffin-lim) names the speaker's recordings, DIR/<name>.wav as kokoro-precompute --wavs finds them
+(22050 Hz mono; a missing file or another rate is named and the exit status is 1).  Every waveform is then also held against its
+recording along the same alignment (kokoro_ruslan_amd.spectral): sc_dtw_W (spectral convergence at the least-squares gain),
+level_db_W (how much louder the synthesized spectrum sits, dB) and lsd_dtw_W (log-spectral distance with that offset taken out, dB) at
+analysis windows W = 256, 512, 1024, and their means mr_sc_dtw and mr_lsd_dtw: the numbers that move with the vocoder, --denoise and
+--griffin-lim-iters.  A corpus conditioned with kokoro-precompute --trim-silence / --loudness must be compared against its
+--conditioned-wavs directory, not the raw recordings: the cache's frames count the conditioned audio.
+--copy-synthesis (needs --wavs and a vocoder; --checkpoint is optional with it and ignored) leaves the acoustic model out: the cache's
+own mels are vocoded and judged against the recordings, the audio stage's share of the error and the last step of the split."""
 from __future__ import annotations
 
 import argparse
@@ -43,7 +53,7 @@ import torch
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Free-running evaluation of a Kokoro checkpoint: MCD-DTW against a feature cache")
-    p.add_argument("--checkpoint", required=True)
+    p.add_argument("--checkpoint", required=True)      # (parse(): optional with --copy-synthesis, and only with it)
     p.add_argument("--features", metavar="CACHE_DIR", required=True, help="precomputed feature cache (*.pt)")
     p.add_argument("--indices", type=int, nargs="*", default=None, help="utterances of the feature cache (its length-sorted order)")
     p.add_argument("--split", choices=("val", "train", "all"), default=None, help="default: val (all with --indices)")
@@ -67,7 +77,25 @@ def build_parser() -> argparse.ArgumentParser:
     add_vocoder_flags(p)
     p.add_argument("--gpe-ratio", type=float, default=0.2, metavar="F",
                    help="a gross pitch error: F0 more than F times the true one off it (default 0.2; needs --vocoder or --griffin-lim)")
+    # (like --oracle-prosody these leave no attribute behind when they are not given)
+    p.add_argument("--wavs", metavar="DIR", default=argparse.SUPPRESS,
+                   help="the recordings, DIR/<name>.wav at 22050 Hz: adds the spectral distance of the vocoded audio to them (needs "
+                        "--vocoder or --griffin-lim).  For a cache made with kokoro-precompute --trim-silence / --loudness give its "
+                        "--conditioned-wavs directory")
+    p.add_argument("--copy-synthesis", action="store_true", default=argparse.SUPPRESS,
+                   help="vocode the cache's own mels instead of synthesized ones: the vocoder and denoiser alone (needs --wavs and a "
+                        "vocoder; --checkpoint is optional)")
     return p
+
+
+def parse(argv=None):
+    """(parser, args): --checkpoint is required unless --copy-synthesis is given."""
+    p = build_parser()
+    if "--copy-synthesis" in (sys.argv[1:] if argv is None else list(argv)):
+        for a in p._actions:
+            if a.dest == "checkpoint":
+                a.required, a.default = False, None
+    return p, p.parse_args(argv)
 
 
 def check_args(p: argparse.ArgumentParser, args) -> None:
@@ -95,6 +123,56 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--gpe-ratio must be >= 0")
     if getattr(args, "oracle_prosody", False):
         args.oracle_durations = True
+    if hasattr(args, "wavs") and not (args.vocoder or args.griffin_lim):
+        p.error("--wavs needs --vocoder or --griffin-lim: the recordings are compared with the vocoded audio")
+    if getattr(args, "copy_synthesis", False):
+        if not hasattr(args, "wavs"):
+            p.error("--copy-synthesis needs --wavs: the vocoded mels are judged against the recordings")
+        if args.oracle_durations:
+            p.error("--copy-synthesis synthesizes nothing: not with --oracle-durations / --oracle-prosody")
+    elif args.checkpoint is None:
+        p.error("the following arguments are required: --checkpoint")
+
+
+def read_wavs(wav_dir: str, names: List[str]) -> List[torch.Tensor]:
+    """DIR/<name>.wav of every utterance, mono fp32 at 22050 Hz; ValueError names a missing file or another rate."""
+    from kokoro.data.features import load_wav
+    out = []
+    for name in names:
+        path = os.path.join(wav_dir, name + ".wav")
+        if not os.path.isfile(path):
+            raise ValueError(f"{path}: no such recording (--wavs expects <name>.wav for every utterance of the selection)")
+        out.append(load_wav(path))
+    return out
+
+
+def _print_metrics(E, summary) -> None:
+    for k in E.METRICS:
+        if k in summary:
+            s = summary[k]
+            print(f"{k:12s} mean {s['mean']:.4f}  median {s['median']:.4f}  p95 {s['p95']:.4f}")
+
+
+def copy_synthesis(parser, args, names, mels, pitch, energy, ref_waves) -> int:
+    """--copy-synthesis: the cache's mels through the vocoder the flags name, against the recordings."""
+    from kokoro.cli.synth import check_vocoder_model, load_vocoder
+    from kokoro.inference import evaluate as E
+    from kokoro_ruslan_amd.dtw import MelAligner
+    device = torch.device("cuda")
+    check_vocoder_model(parser, args, mels[0].shape[1])
+    voc, vkw, den, how = load_vocoder(args, device)
+    kw = dict(denoiser=den, denoise_strength=args.denoise) if den is not None else {}
+    records, summary = E.evaluate_vocoder(voc, mels, ref_waves, pitch, energy, vocoder_kwargs=vkw, names=names, device=device,
+                                          aligner=MelAligner(device=device, K=args.mcep, gpe_ratio=args.gpe_ratio), **kw)
+    print(f"kokoro-eval: {summary['utterances']} utterances, copy synthesis; audio: {how}, {summary['no_variance']} without pitch and "
+          f"energy in the cache")
+    _print_metrics(E, summary)
+    if args.output:
+        with open(args.output, "w") as f:
+            json.dump({"records": records, "summary": summary, "copy_synthesis": True, "audio": how, "gpe_ratio": args.gpe_ratio,
+                       "wavs": args.wavs, "split": "indices" if args.indices is not None else (args.split or "val")}, f, indent=1)
+        print(f"kokoro-eval: report -> {args.output}")
+    return 0
 
 
 def select_indices(n: int, split: Optional[str], validation_split: float, indices: Optional[List[int]]) -> List[int]:
@@ -149,13 +227,21 @@ def oracle_prosody(names, ids, durs, pitch=None, energy=None):
 def main(argv=None) -> int:
     from kokoro.inference import evaluate as E
     from kokoro.inference import synth as S
-    parser = build_parser()
-    args = parser.parse_args(argv)
+    parser, args = parse(argv)
     check_args(parser, args)
     audio = bool(args.vocoder or args.griffin_lim)
     names, ids, stress, mels, durs, pitch, energy = read_features(args.features, args.split, args.validation_split, args.indices)
     if not names:
         parser.error("the selection is empty: nothing to evaluate")
+    ref_waves = None
+    if hasattr(args, "wavs"):
+        try:
+            ref_waves = read_wavs(args.wavs, names)
+        except ValueError as e:
+            print(f"kokoro-eval: {e}", file=sys.stderr)
+            return 1
+    if getattr(args, "copy_synthesis", False):
+        return copy_synthesis(parser, args, names, mels, pitch, energy, ref_waves)
     engine, controls, used = S.load_for_inference(args.checkpoint, weights=args.weights, math_mode=args.math, max_len=args.max_len,
                                                   stop_threshold=args.stop_threshold, min_len_ratio=args.min_len_ratio,
                                                   min_len_floor=args.min_len_floor)
@@ -177,23 +263,23 @@ def main(argv=None) -> int:
                    aligner=MelAligner(device=engine.device, K=args.mcep, gpe_ratio=args.gpe_ratio))
         if den is not None:
             pkw.update(denoiser=den, denoise_strength=args.denoise)
+        if ref_waves is not None:
+            pkw.update(ref_waves=ref_waves)
     records, summary = E.evaluate(engine, ids, stress, mels, stream=not args.no_stream, slots=32 if args.slots is None else args.slots,
                                   batch_size=32 if args.batch_size is None else args.batch_size, durations=durs, names=names,
                                   mcep=args.mcep, **pkw, **controls.kwargs())
     print(f"kokoro-eval: {summary['utterances']} utterances ({used} weights, {controls}), "
           f"{100.0 * summary['hit_bound_share']:.1f} % ended at their generation bound"
           + (f"; audio: {how}, {summary['no_variance']} without pitch and energy in the cache" if audio else ""))
-    for k in E.METRICS:
-        if k in summary:
-            s = summary[k]
-            print(f"{k:12s} mean {s['mean']:.4f}  median {s['median']:.4f}  p95 {s['p95']:.4f}")
+    _print_metrics(E, summary)
     if args.output:
         with open(args.output, "w") as f:
             json.dump({"records": records, "summary": summary, "controls": controls.kwargs(), "weights": used, "mcep": args.mcep,
                        "split": "indices" if args.indices is not None else (args.split or "val"), "checkpoint": args.checkpoint,
                        **({"oracle_durations": True} if args.oracle_durations else {}),
                        **({"oracle_prosody": True} if getattr(args, "oracle_prosody", False) else {}),
-                       **({"audio": how, "gpe_ratio": args.gpe_ratio} if audio else {})}, f, indent=1)
+                       **({"audio": how, "gpe_ratio": args.gpe_ratio} if audio else {}),
+                       **({"wavs": args.wavs} if ref_waves is not None else {})}, f, indent=1)
         print(f"kokoro-eval: report -> {args.output}")
     return 0
 

@@ -3,7 +3,10 @@ ground truth by dynamic time warping on the device (kokoro_ruslan_amd.dtw) and r
 MCD-DTW, the aligned mel L1, the length ratio, rows that ran into their generation bound, and the duration predictor's total error.
 With a vocoder the judgement goes on to the audio: every mel is vocoded (and denoised), the pitch and energy tracks of the waveforms
 are extracted on the device (kokoro_ruslan_amd.features) and compared with the ground truth's along the same alignment: the F0 error
-in cents, the voicing decision error, the gross pitch errors and the energy error.
+in cents, the voicing decision error, the gross pitch errors and the energy error.  With the speaker's recordings (ref_waves) the
+waveforms are also held against them along that alignment (kokoro_ruslan_amd.spectral): spectral convergence, level offset and
+log-spectral distance at three analysis windows, the numbers that move with the vocoder, the denoiser and Griffin-Lim's iterations.
+evaluate_vocoder is the same judgement of the audio stage alone: the cache's own mels vocoded and compared with the recordings.
 """
 from __future__ import annotations
 
@@ -14,7 +17,9 @@ import torch
 
 TRACK_METRICS = ("f0_rmse_cents", "f0_bias_cents", "gpe", "vuv_err", "energy_l1_dtw")
 TRACK_COUNTS = ("n_vv", "n_vu", "n_uv", "n_uu", "n_gpe")
-METRICS = ("mcd_dtw", "mel_l1_dtw", "len_ratio", "dur_abs_err") + TRACK_METRICS
+SPECTRAL_METRICS = ("mr_sc_dtw", "mr_lsd_dtw") + tuple(f"{k}_{w}" for w in (256, 512, 1024) for k in ("sc_dtw", "lsd_dtw", "level_db"))
+SPECTRAL_COUNTS = ("spec_steps", "spec_skipped")
+METRICS = ("mcd_dtw", "mel_l1_dtw", "len_ratio", "dur_abs_err") + TRACK_METRICS + SPECTRAL_METRICS
 
 
 def _generate(engine, ids, stress, stream: bool, slots: int, batch_size: int, controls: Dict[str, Any], prosody=None):
@@ -49,7 +54,7 @@ def summarize(records: Sequence[Dict]) -> Dict[str, Any]:
     record whose value is None does not count: an F0 error without a step voiced on both sides).  Records of an evaluation with a
     vocoder carry "no_variance"; the summary then counts those that are (a cache written without pitch and energy)."""
     out: Dict[str, Any] = {"utterances": len(records),
-                           "hit_bound_share": sum(bool(r["hit_bound"]) for r in records) / len(records) if records else 0.0}
+                           "hit_bound_share": sum(bool(r.get("hit_bound")) for r in records) / len(records) if records else 0.0}
     for k in METRICS:
         v = [float(r[k]) for r in records if r.get(k) is not None]
         if v:
@@ -60,10 +65,11 @@ def summarize(records: Sequence[Dict]) -> Dict[str, Any]:
     return out
 
 
-def _check_audio_args(N: int, vocoder, vocoder_kwargs, denoiser, denoise_strength, extractor, ref_pitch, ref_energy, want_audio) -> None:
+def _check_audio_args(N: int, vocoder, vocoder_kwargs, denoiser, denoise_strength, extractor, ref_pitch, ref_energy, want_audio,
+                      ref_waves=None, spectral=None) -> None:
     if vocoder is None:
         for what, v in (("vocoder_kwargs", vocoder_kwargs), ("denoiser", denoiser), ("extractor", extractor), ("ref_pitch", ref_pitch),
-                        ("ref_energy", ref_energy)):
+                        ("ref_energy", ref_energy), ("ref_waves", ref_waves), ("spectral", spectral)):
             if v is not None:
                 raise ValueError(f"{what} needs a vocoder: it bears on the audio metrics alone")
         if want_audio:
@@ -78,6 +84,28 @@ def _check_audio_args(N: int, vocoder, vocoder_kwargs, denoiser, denoise_strengt
         raise ValueError("vocoder_kwargs must be a dict of keyword arguments for the vocoder's vocode()")
     if denoiser is not None and not (isinstance(denoise_strength, (int, float)) and math.isfinite(denoise_strength) and denoise_strength >= 0):
         raise ValueError(f"denoise_strength must be a finite number >= 0, not {denoise_strength!r}")
+    _check_ref_waves(N, ref_waves, spectral)
+
+
+def _check_ref_waves(N: int, ref_waves, spectral) -> None:
+    if ref_waves is None:
+        if spectral is not None:
+            raise ValueError("spectral needs ref_waves: it measures the audio against the recordings")
+        return
+    if len(ref_waves) != N:
+        raise ValueError(f"ref_waves: {len(ref_waves)} entries for {N} utterances")
+    for i, w in enumerate(ref_waves):
+        if not isinstance(w, torch.Tensor) or w.dim() != 1 or not w.is_floating_point():
+            raise ValueError(f"ref_waves[{i}] must be a 1-D float tensor of samples")
+
+
+def _spectral_records(spectral, device, audio, ref_waves, aligned, frames, ref_frames) -> List[Dict]:
+    """The spectral fields of every utterance: the waveforms against the recordings along the aligner's paths."""
+    if spectral is None:
+        from kokoro_ruslan_amd.spectral import SpectralDistance
+        spectral = SpectralDistance(device=device)
+    got = spectral.measure(audio, list(ref_waves), [al["path"] for al in aligned], frames, ref_frames)
+    return [{k: g[k] for k in SPECTRAL_METRICS + SPECTRAL_COUNTS} for g in got]
 
 
 def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torch.Tensor]], ref_mels: Sequence[torch.Tensor], *,
@@ -85,7 +113,7 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
              names: Optional[Sequence[str]] = None, mcep: int = 13, aligner=None, prosody=None, vocoder=None,
              vocoder_kwargs: Optional[Dict[str, Any]] = None, denoiser=None, denoise_strength: float = 0.005, extractor=None,
              ref_pitch: Optional[Sequence[torch.Tensor]] = None, ref_energy: Optional[Sequence[torch.Tensor]] = None,
-             want_audio: bool = False,
+             want_audio: bool = False, ref_waves: Optional[Sequence[torch.Tensor]] = None, spectral=None,
              **controls) -> Union[Tuple[List[Dict], Dict[str, Any]], Tuple[List[Dict], Dict[str, Any], List[torch.Tensor]]]:
     """Synthesize every utterance free-running (generate_stream with `slots` rows, or generate_batch `batch_size` at a time) and
     compare it with ref_mels[i] [frames, n_mels].  controls: the stop controls of generate_batch.  Returns (records, summary):
@@ -99,14 +127,20 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
     cache's normalised tracks; both required) along the mel's alignment.  Records gain "f0_rmse_cents", "f0_bias_cents", "gpe" (None
     when no step is voiced on both sides), "vuv_err", "energy_l1_dtw", the counts n_vv, n_vu, n_uv, n_uu, n_gpe
     (MelAligner.align(tracks=)) and "no_variance": an utterance whose reference pitch and energy are all zero comes from a cache
-    written without them; it is marked and gets no track metrics.  want_audio=True returns (records, summary, waveforms)."""
+    written without them; it is marked and gets no track metrics.  want_audio=True returns (records, summary, waveforms).
+    ref_waves (needs a vocoder): the recording of every utterance, 1-D float samples at 22050 Hz (of a corpus conditioned by
+    kokoro-precompute --trim-silence / --loudness: its --conditioned-wavs).  The aligner is then asked for its paths and the (denoised)
+    waveforms are measured against the recordings along them by `spectral` (default: a kokoro_ruslan_amd.spectral.SpectralDistance on
+    the engine's device); every record gains sc_dtw_W, lsd_dtw_W, level_db_W for W in 256, 512, 1024, mr_sc_dtw, mr_lsd_dtw (None when
+    a side is silent), spec_steps and spec_skipped."""
     N = len(ids)
     if len(ref_mels) != N:
         raise ValueError(f"{len(ref_mels)} reference mels for {N} utterances")
     for what, v in (("stress", stress), ("durations", durations), ("names", names)):
         if v is not None and len(v) != N:
             raise ValueError(f"{what}: {len(v)} entries for {N} utterances")
-    _check_audio_args(N, vocoder, vocoder_kwargs, denoiser, denoise_strength, extractor, ref_pitch, ref_energy, want_audio)
+    _check_audio_args(N, vocoder, vocoder_kwargs, denoiser, denoise_strength, extractor, ref_pitch, ref_energy, want_audio, ref_waves,
+                      spectral)
     if N == 0:
         return ([], summarize([]), []) if want_audio else ([], summarize([]))
     if prosody is not None:
@@ -116,7 +150,7 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
     if aligner is None:
         from kokoro_ruslan_amd.dtw import MelAligner
         aligner = MelAligner(device=engine.device, K=mcep)
-    audio, bare = None, None
+    audio, bare, spec = None, None, None
     if vocoder is None:
         aligned = aligner.align(mels, ref_mels)
     else:
@@ -129,8 +163,13 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
             from kokoro_ruslan_amd.features import FeatureExtractor
             extractor = FeatureExtractor(device=engine.device)
         feats = extractor.extract(audio, max_seq_length=MAX_FRAMES + 1)      # (T or T + 1 frames of a T-frame mel: never cut short)
-        aligned = aligner.align(mels, ref_mels, tracks={"pitch": ([f["pitch"] for f in feats], list(ref_pitch)),
-                                                        "energy": ([f["energy"] for f in feats], list(ref_energy))})
+        tracks = {"pitch": ([f["pitch"] for f in feats], list(ref_pitch)), "energy": ([f["energy"] for f in feats], list(ref_energy))}
+        if ref_waves is None:
+            aligned = aligner.align(mels, ref_mels, tracks=tracks)
+        else:
+            aligned = aligner.align(mels, ref_mels, want_path=True, tracks=tracks)
+            spec = _spectral_records(spectral, engine.device, audio, ref_waves, aligned, [int(m.shape[0]) for m in mels],
+                                     [int(r.shape[0]) for r in ref_mels])
         where = torch.as_tensor(ref_pitch[0]).device                             # (one read for all utterances, wherever the tracks lie)
         bare = [n == 0 for n in torch.stack([(torch.count_nonzero(p) + torch.count_nonzero(e)).to(where)
                                              for p, e in zip(ref_pitch, ref_energy)]).tolist()]
@@ -145,5 +184,69 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
             rec["no_variance"] = bare[i]
             if not bare[i]:
                 rec.update({k: al[k] for k in TRACK_METRICS + TRACK_COUNTS})
+        if spec is not None:
+            rec.update(spec[i])
         records.append(rec)
     return (records, summarize(records), audio) if want_audio else (records, summarize(records))
+
+
+def evaluate_vocoder(vocoder, ref_mels: Sequence[torch.Tensor], ref_waves: Sequence[torch.Tensor],
+                     ref_pitch: Optional[Sequence[torch.Tensor]] = None, ref_energy: Optional[Sequence[torch.Tensor]] = None, *,
+                     denoiser=None, denoise_strength: float = 0.005, vocoder_kwargs: Optional[Dict[str, Any]] = None, extractor=None,
+                     aligner=None, spectral=None, names: Optional[Sequence[str]] = None, device="cuda", want_audio: bool = False):
+    """Copy synthesis: the audio stage alone, with no acoustic model in the loop.  The cache's own mels ref_mels[i] [frames, n_mels] are
+    vocoded (and denoised), aligned with themselves (the path is the diagonal) and the waveforms judged against the recordings
+    ref_waves[i] like evaluate()'s: the fourth step of the error split none -> oracle durations -> oracle prosody -> copy synthesis.
+    Returns (records, summary): per utterance {"name", "frames", the spectral fields} and, with ref_pitch and ref_energy (both or
+    neither), "no_variance" and the track metrics of evaluate().  want_audio=True returns (records, summary, waveforms)."""
+    N = len(ref_mels)
+    if vocoder is None:
+        raise ValueError("evaluate_vocoder needs a vocoder")
+    if ref_waves is None:
+        raise ValueError("evaluate_vocoder needs ref_waves: the recordings the audio is judged against")
+    if (ref_pitch is None) != (ref_energy is None):
+        raise ValueError("ref_pitch and ref_energy come together: both or neither")
+    for what, v in (("ref_pitch", ref_pitch), ("ref_energy", ref_energy), ("names", names)):
+        if v is not None and len(v) != N:
+            raise ValueError(f"{what}: {len(v)} entries for {N} utterances")
+    if vocoder_kwargs is not None and not isinstance(vocoder_kwargs, dict):
+        raise ValueError("vocoder_kwargs must be a dict of keyword arguments for the vocoder's vocode()")
+    if denoiser is not None and not (isinstance(denoise_strength, (int, float)) and math.isfinite(denoise_strength) and denoise_strength >= 0):
+        raise ValueError(f"denoise_strength must be a finite number >= 0, not {denoise_strength!r}")
+    _check_ref_waves(N, ref_waves, spectral)
+    if N == 0:
+        return ([], summarize([]), []) if want_audio else ([], summarize([]))
+    from kokoro.inference.audio import denoise, vocode
+    mels = list(ref_mels)
+    audio = vocode(vocoder, mels, **(vocoder_kwargs or {}))
+    if denoiser is not None:
+        audio = denoise(denoiser, audio, denoise_strength)
+    if aligner is None:
+        from kokoro_ruslan_amd.dtw import MelAligner
+        aligner = MelAligner(device=device)
+    tracks, bare = None, None
+    if ref_pitch is not None:
+        from kokoro_ruslan_amd.dtw import MAX_FRAMES
+        if extractor is None:
+            from kokoro_ruslan_amd.features import FeatureExtractor
+            extractor = FeatureExtractor(device=device)
+        feats = extractor.extract(audio, max_seq_length=MAX_FRAMES + 1)
+        tracks = {"pitch": ([f["pitch"] for f in feats], list(ref_pitch)), "energy": ([f["energy"] for f in feats], list(ref_energy))}
+        where = torch.as_tensor(ref_pitch[0]).device
+        bare = [n == 0 for n in torch.stack([(torch.count_nonzero(p) + torch.count_nonzero(e)).to(where)
+                                             for p, e in zip(ref_pitch, ref_energy)]).tolist()]
+    aligned = aligner.align(mels, mels, want_path=True, tracks=tracks)
+    frames = [int(m.shape[0]) for m in mels]
+    spec = _spectral_records(spectral, device, audio, ref_waves, aligned, frames, frames)
+    records = []
+    for i, al in enumerate(aligned):
+        rec = {"name": names[i] if names is not None else i, "frames": frames[i]}
+        if bare is not None:
+            rec["no_variance"] = bare[i]
+            if not bare[i]:
+                rec.update({k: al[k] for k in TRACK_METRICS + TRACK_COUNTS})
+        rec.update(spec[i])
+        records.append(rec)
+    summary = summarize(records)
+    del summary["hit_bound_share"]                                            # (nothing was generated: no row has a bound)
+    return (records, summary, audio) if want_audio else (records, summary)

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libkokoro_hip.so")
-SOURCES = ["kk_core.hip", "kk_gemm.hip", "kk_gemm16.hip", "kk_gemm16x.hip", "kk_attn.hip", "kk_attn_fwd.hip", "kk_attn_bwd.hip", "kk_norm.hip", "kk_elem.hip", "kk_loss.hip", "kk_optim.hip", "kk_dropout.hip", "kk_comm.hip", "kk_encstack.hip", "kk_chain.hip", "kk_synth.hip", "kk_stream.hip", "kk_prosody.hip", "kk_vocoder.hip", "kk_griffinlim.hip", "kk_denoise.hip", "kk_loudness.hip", "kk_features.hip", "kk_resample.hip", "kk_dtw.hip", "kk_align.hip", "kk_longform.hip"]
+SOURCES = ["kk_core.hip", "kk_gemm.hip", "kk_gemm16.hip", "kk_gemm16x.hip", "kk_attn.hip", "kk_attn_fwd.hip", "kk_attn_bwd.hip", "kk_norm.hip", "kk_elem.hip", "kk_loss.hip", "kk_optim.hip", "kk_dropout.hip", "kk_comm.hip", "kk_encstack.hip", "kk_chain.hip", "kk_synth.hip", "kk_stream.hip", "kk_prosody.hip", "kk_vocoder.hip", "kk_griffinlim.hip", "kk_denoise.hip", "kk_loudness.hip", "kk_features.hip", "kk_resample.hip", "kk_dtw.hip", "kk_spectral.hip", "kk_align.hip", "kk_longform.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
 
 
@@ -75,6 +75,7 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         "kk_features.hip": ["kk_fft.h"],      # the 1024-point real STFT of one wave, shared by the three audio sources
         "kk_griffinlim.hip": ["kk_fft.h"],
         "kk_denoise.hip": ["kk_fft.h"],
+        "kk_spectral.hip": ["kk_fft.h"],
         # bodies compiled into kk_chain.hip: the GEMM and attention forward bodies from their device headers, kk_dropout.hip under KK_BODIES_ONLY
         "kk_chain.hip": gemm_dev + ["kk_gemm16x_body.h", "kk_gemm16_body.h", "kk_dropout.hip", "kk_attn.h", "kk_attn_fwd3.h"],
     }

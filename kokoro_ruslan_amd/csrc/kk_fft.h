@@ -11,46 +11,53 @@
 //               stft_ola (one padded position: the frames that cover it summed in ascending order, over the window-square envelope)
 //
 // Where a sample comes from, which frames a tile owns and what is done to a bin stay with each kernel.  Everything here inlines.
+// The forward half is written for a complex type C: those three kernels use float2, the spectral distance (kk_spectral.hip) double2.
 #pragma once
 #include "kk_common.h"
 
 namespace {
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-template <int SIGN> __device__ __forceinline__ float2 dirw(float2 w) { return SIGN < 0 ? w : make_float2(w.x, -w.y); }
-template <int SIGN> __device__ __forceinline__ float2 mul_i(float2 a) {      // a . (SIGN i)
-    return SIGN < 0 ? make_float2(a.y, -a.x) : make_float2(-a.y, a.x);
+// The transform is written once for a complex type C: float2 (every kernel but one) or double2 (kk_spectral.hip, whose sums are held
+// to fp64).  cx(x, y) makes a C from two scalars of its precision.
+__device__ __forceinline__ float2 cx(float x, float y) { return make_float2(x, y); }
+__device__ __forceinline__ double2 cx(double x, double y) { return make_double2(x, y); }
+
+template <class C> __device__ __forceinline__ C cmul(C a, C b) { return cx(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+template <int SIGN, class C> __device__ __forceinline__ C dirw(C w) { return SIGN < 0 ? w : cx(w.x, -w.y); }
+template <int SIGN, class C> __device__ __forceinline__ C mul_i(C a) {      // a . (SIGN i)
+    return SIGN < 0 ? cx(a.y, -a.x) : cx(-a.y, a.x);
 }
 
 // In-place 8-point DFT, natural order in and out: X[k] = sum_n v[n] exp(SIGN 2 pi i n k / 8).
-template <int SIGN> __device__ __forceinline__ void dft8(float2 *v) {
-    constexpr float R = 0.70710678118654752f;
-    float2 e[4], o[4];
+template <int SIGN, class C> __device__ __forceinline__ void dft8(C *v) {
+    using S = decltype(v[0].x);
+    constexpr S R = (S)0.70710678118654752440;
+    C e[4], o[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                            // DFT4 of the even (h = 0) and odd (h = 1) samples
-        const float2 a = v[h], b = v[h + 2], c = v[h + 4], d = v[h + 6];
-        const float2 s0 = make_float2(a.x + c.x, a.y + c.y), s1 = make_float2(a.x - c.x, a.y - c.y);
-        const float2 s2 = make_float2(b.x + d.x, b.y + d.y), s3 = mul_i<SIGN>(make_float2(b.x - d.x, b.y - d.y));
-        float2 *y = h ? o : e;
-        y[0] = make_float2(s0.x + s2.x, s0.y + s2.y);
-        y[2] = make_float2(s0.x - s2.x, s0.y - s2.y);
-        y[1] = make_float2(s1.x + s3.x, s1.y + s3.y);
-        y[3] = make_float2(s1.x - s3.x, s1.y - s3.y);
+        const C a = v[h], b = v[h + 2], c = v[h + 4], d = v[h + 6];
+        const C s0 = cx(a.x + c.x, a.y + c.y), s1 = cx(a.x - c.x, a.y - c.y);
+        const C s2 = cx(b.x + d.x, b.y + d.y), s3 = mul_i<SIGN>(cx(b.x - d.x, b.y - d.y));
+        C *y = h ? o : e;
+        y[0] = cx(s0.x + s2.x, s0.y + s2.y);
+        y[2] = cx(s0.x - s2.x, s0.y - s2.y);
+        y[1] = cx(s1.x + s3.x, s1.y + s3.y);
+        y[3] = cx(s1.x - s3.x, s1.y - s3.y);
     }
-    o[1] = cmul(o[1], make_float2(R, SIGN * R));
+    o[1] = cmul(o[1], cx(R, SIGN * R));
     o[2] = mul_i<SIGN>(o[2]);
-    o[3] = cmul(o[3], make_float2(-R, SIGN * R));
+    o[3] = cmul(o[3], cx(-R, SIGN * R));
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        v[k] = make_float2(e[k].x + o[k].x, e[k].y + o[k].y);
-        v[k + 4] = make_float2(e[k].x - o[k].x, e[k].y - o[k].y);
+        v[k] = cx(e[k].x + o[k].x, e[k].y + o[k].y);
+        v[k + 4] = cx(e[k].x - o[k].x, e[k].y - o[k].y);
     }
 }
 
 // 512-point complex DFT of one wave: lane l holds v[m] = z[l + 64 m]; on return lane q holds v[k2] = Z[(q >> 3) + 8 (q & 7) + 64 k2].
 // Z[k0 + 8 k1 + 64 k2] = sum_{l0} w8^(l0 k2) w64^(l0 k1) sum_{l1} w8^(l1 k1) w512^(l k0) sum_m w8^(m k0) z[l + 64 m], l = l0 + 8 l1.
-// sl: this wave's 512-float2 LDS exchange slot.  tw1[j] = w512^(lane j), tw2[j] = w512^(8 (lane & 7) j) (forward sign).
-template <int SIGN> __device__ __forceinline__ void fft512(float2 *v, float2 *sl, const float2 *tw1, const float2 *tw2, int lane) {
+// sl: this wave's 512-element LDS exchange slot.  tw1[j] = w512^(lane j), tw2[j] = w512^(8 (lane & 7) j) (forward sign).
+template <int SIGN, class C> __device__ __forceinline__ void fft512(C *v, C *sl, const C *tw1, const C *tw2, int lane) {
     dft8<SIGN>(v);
 #pragma unroll
     for (int j = 1; j < 8; ++j) v[j] = cmul(v[j], dirw<SIGN>(tw1[j]));
@@ -75,9 +82,10 @@ template <int SIGN> __device__ __forceinline__ void fft512(float2 *v, float2 *sl
 
 constexpr int STFT_N = 1024, STFT_HOP = 256, STFT_BINS = STFT_N / 2 + 1;
 
-struct StftTw { float2 tw1[8], tw2[8], twk[8]; };             // of one lane, from the table tw[j] = exp(-2 pi i j / 1024)
+template <class C> struct StftTwT { C tw1[8], tw2[8], twk[8]; };   // of one lane, from the table tw[j] = exp(-2 pi i j / 1024)
+using StftTw = StftTwT<float2>;
 
-__device__ __forceinline__ void stft_twiddles(const float2 *tw, int lane, StftTw &t) {
+template <class C> __device__ __forceinline__ void stft_twiddles(const C *tw, int lane, StftTwT<C> &t) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         t.tw1[j] = tw[(2 * lane * j) & (STFT_N - 1)];
@@ -93,18 +101,18 @@ __device__ __forceinline__ int reflect(int j, int n) { return j < 0 ? -j : (j >=
 __device__ __forceinline__ int stft_nat(int lane, int k2) { return (lane >> 3) + 8 * (lane & 7) + 64 * k2; }
 
 // Frame t of a signal of n samples (n > 512, t <= n / 256), windowed, through the 512-point complex transform: Z in natural order in the
-// wave's slot sl.  load(j): sample j, 0 <= j < n.
-template <class Load> __device__ __forceinline__ void stft_frame_fwd(Load load, int t, int n, const float *__restrict__ win, float2 *sl,
-                                                                     const StftTw &tw, int lane) {
-    float2 v[8];
+// wave's slot sl.  load(j): sample j, 0 <= j < n, in the window's precision S.
+template <class Load, class S, class C> __device__ __forceinline__ void stft_frame_fwd(Load load, int t, int n, const S *__restrict__ win,
+                                                                                      C *sl, const StftTwT<C> &tw, int lane) {
+    C v[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int i = lane + 64 * m;
-        float s[2];
+        S s[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) s[h] = load(reflect(STFT_HOP * t - STFT_N / 2 + 2 * i + h, n));
-        const float2 w = *reinterpret_cast<const float2 *>(win + 2 * i);
-        v[m] = make_float2(s[0] * w.x, s[1] * w.y);
+        const C w = *reinterpret_cast<const C *>(win + 2 * i);
+        v[m] = cx(s[0] * w.x, s[1] * w.y);
     }
     fft512<-1>(v, sl, tw.tw1, tw.tw2, lane);
     __syncwarp();
@@ -115,30 +123,31 @@ template <class Load> __device__ __forceinline__ void stft_frame_fwd(Load load, 
 
 // The split step for bin k < 512 from Z in sl: X[k] = fe + c, X[512 - k] = conj(fe - c), with c = w^k fo,
 // fe = (Z[k] + conj Z[512-k]) / 2, fo = (Z[k] - conj Z[512-k]) / 2i.
-__device__ __forceinline__ void stft_split_parts(const float2 *sl, float2 twk, int k, float2 &fe, float2 &c) {
-    const float2 zk = sl[k], zm = sl[(STFT_N / 2 - k) & (STFT_N / 2 - 1)];
-    fe = make_float2((zk.x + zm.x) * 0.5f, (zk.y - zm.y) * 0.5f);
-    const float2 fo = make_float2((zk.y + zm.y) * 0.5f, (zm.x - zk.x) * 0.5f);
+template <class C> __device__ __forceinline__ void stft_split_parts(const C *sl, C twk, int k, C &fe, C &c) {
+    using S = decltype(twk.x);
+    const C zk = sl[k], zm = sl[(STFT_N / 2 - k) & (STFT_N / 2 - 1)];
+    fe = cx((zk.x + zm.x) * (S)0.5, (zk.y - zm.y) * (S)0.5);
+    const C fo = cx((zk.y + zm.y) * (S)0.5, (zm.x - zk.x) * (S)0.5);
     c = cmul(twk, fo);
 }
 
 // X = bin k, Xm = bin 512 - k (k = 0: bins 0 and 512).
-__device__ __forceinline__ void stft_split_pair(const float2 *sl, float2 twk, int k, float2 &X, float2 &Xm) {
-    float2 fe, c;
+template <class C> __device__ __forceinline__ void stft_split_pair(const C *sl, C twk, int k, C &X, C &Xm) {
+    C fe, c;
     stft_split_parts(sl, twk, k, fe, c);
-    X = make_float2(fe.x + c.x, fe.y + c.y);
-    Xm = make_float2(fe.x - c.x, c.y - fe.y);
+    X = cx(fe.x + c.x, fe.y + c.y);
+    Xm = cx(fe.x - c.x, c.y - fe.y);
 }
 
 // Bin k alone; bin 512 is then stft_bin512 on lane 0: even sum minus odd sum.
-__device__ __forceinline__ float2 stft_split(const float2 *sl, float2 twk, int k) {
-    float2 fe, c;
+template <class C> __device__ __forceinline__ C stft_split(const C *sl, C twk, int k) {
+    C fe, c;
     stft_split_parts(sl, twk, k, fe, c);
-    return make_float2(fe.x + c.x, fe.y + c.y);
+    return cx(fe.x + c.x, fe.y + c.y);
 }
-__device__ __forceinline__ float2 stft_bin512(const float2 *sl) {
-    const float2 z0 = sl[0];
-    return make_float2(z0.x - z0.y, 0.f);
+template <class C> __device__ __forceinline__ C stft_bin512(const C *sl) {
+    const C z0 = sl[0];
+    return cx(z0.x - z0.y, (decltype(z0.x))0);
 }
 
 // The inverse transform's input: Z'[k] = Y[k] + conj Y[512-k] + i w^-k (Y[k] - conj Y[512-k]), yk = Y[k], ym = Y[512 - k].

@@ -272,6 +272,8 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_dtw_backtrack": [_P, _P, _P, _P, _P, _I, _P, _P, _P],
     "kk_dtw_path_stats": [_P, _L, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "kk_dtw_track_stats": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _P, _P, _P],
+    "kk_dtw_spectral_tile": [],
+    "kk_dtw_spectral_stats": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "kk_align_max_tokens": [],
     "kk_align_feats": [_P, _P, _L, _I, _I, _P, _I, _P, _P],
     "kk_align_loglik": [_P, _L, _I, _I, _P, _P, _P, _P, _P],

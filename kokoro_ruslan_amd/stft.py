@@ -18,6 +18,20 @@ def hann_window(dtype: torch.dtype = torch.float64) -> torch.Tensor:
     return torch.hann_window(N_FFT, periodic=True, dtype=dtype)
 
 
+ANALYSIS_WIDTHS = (256, 512, 1024)      # the windows of the multi-resolution spectral distance (spectral.py); 1024 is hann_window
+
+
+def centred_hann_windows(dtype: torch.dtype = torch.float64, widths=ANALYSIS_WIDTHS) -> torch.Tensor:
+    """[len(widths), 1024]: a periodic Hann of each width w centred in the 1024-sample frame (entries 512 - w / 2 .. 512 + w / 2 - 1,
+    zeros elsewhere): what torch.stft(n_fft=1024, win_length=w) makes of hann_window(w), so one 1024-point transform serves them all."""
+    out = torch.zeros(len(widths), N_FFT, dtype=dtype)
+    for r, w in enumerate(widths):
+        if w % 2 or not (2 <= w <= N_FFT):
+            raise ValueError(f"window width {w}: expected an even number in 2..{N_FFT}")
+        out[r, N_FFT // 2 - w // 2:N_FFT // 2 + w // 2] = torch.hann_window(w, periodic=True, dtype=dtype)
+    return out
+
+
 def twiddles() -> torch.Tensor:
     """exp(-2 pi i j / 1024) for j < 1024, computed in fp64, as complex64."""
     ang = -2.0 * math.pi * torch.arange(N_FFT, dtype=torch.float64) / N_FFT
