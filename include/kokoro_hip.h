@@ -652,6 +652,16 @@ int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *fo
  * fixed-order partial sums and a fixed tree (no atomics: two runs give the same bits) */
 int kk_align_accumulate(const float *feat, const int *label, int64_t T_total, int D, int V, int64_t *count, double *sum,
                         double *sumsq, void *stream);
+/* pronunciation scores of an alignment (align_torch.scores), two launches.  Per frame t with class label[t] (scratch, all [T_total]):
+ * amax = the lowest v with L[v][t] = fmax = max_v L[v][t]; margin = L[label][t] - fmax and lpost = margin - log sum_v exp(L[v][t] -
+ * fmax) in fp64 (0 and 0 where label is outside 0..V-1).  Per token p with durations[p] frames ([P_total]): gop_sum and lpost_sum, the
+ * fp64 sums of margin and lpost over its frames in ascending order from 0.0, and hits, the frames with amax == ids[p].  Per utterance
+ * ([B]): the sums of its tokens' values in ascending token order.  An utterance outside the limits above, or whose durations are not
+ * all in 0..T with the sum T (an infeasible one has zeros), gets zeros; every element of the nine outputs is written.  L is read once;
+ * an utterance's results do not depend on the batch.  V <= 256 */
+int kk_align_scores(const float *L, int64_t T_total, int V, const int *label, const int *durations, const int *ids, const int *foff,
+                    const int *poff, int B, double *margin, double *lpost, int *amax, double *gop_sum, double *lpost_sum, int *hits,
+                    double *utt_gop, double *utt_lpost, int *utt_hits, void *stream);
 
 /* ---- dropout / DropPath / SpecAugment (p > 0 training paths; masks from an in-kernel counter RNG) ----
  * out = (res ? res[row % res_mod (0: row)] : 0) + x * m1 * m2 * droppath(sample(row)), m_i in {0, 1/(1-p_i)}

@@ -1,7 +1,7 @@
 """`kokoro-align`: phoneme durations for a feature cache by flat-start forced alignment on the device (no external aligner).
 
     kokoro-align --cache-dir DIR [--iters N] [--optional-id ID ...] [--batch-size N] [--var-floor F] [--mcep K] [--n-classes V]
-                 [--model-in FILE | --model-out FILE] [--output FILE.jsonl] [--write-cache]
+                 [--model-in FILE | --model-out FILE] [--output FILE.jsonl] [--write-cache] [--scores [--worst N]]
 
 Reads the schema-v7 entries of a feature cache (mel_spec, phoneme_indices), fits one diagonal Gaussian per phoneme id by Viterbi
 training from the even split (kokoro_ruslan_amd.align.PhoneAligner.fit) -- or, with --model-in, loads a fitted model and only aligns --
@@ -10,6 +10,12 @@ whose tokens may get no frame (a silence the speaker did not make; there is no d
 --output writes one {"name", "phoneme_durations"} line per utterance, the field kokoro-precompute --ids accepts; --write-cache replaces
 phoneme_durations in every entry, atomically.  An utterance that cannot be aligned (more mandatory tokens than frames, or longer than
 the kernels take) keeps the durations it has, is reported on stderr and makes the exit status 1.
+--scores (after a fit or with --model-in) also scores every utterance against its own transcript with the model
+(PhoneAligner.score): gop, the mean over the frames of log-likelihood(forced phoneme) - log-likelihood(best phoneme); logpost, the mean
+log posterior of the forced phoneme; phone_acc, the share of frames whose best phoneme is the forced one; gop_min and gop_min_token,
+the worst token and where it is.  The five fields join every --output line (null for an utterance that was not aligned) and the
+--worst N (default 10) utterances by gop are printed, lowest first: where a transcript does not match its audio, the scores fall.  They
+rank; no threshold says "wrong".
 """
 from __future__ import annotations
 
@@ -18,6 +24,9 @@ import json
 import os
 import sys
 from typing import Dict, List
+
+
+SCORE_FIELDS = ("gop", "logpost", "phone_acc", "gop_min", "gop_min_token")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -34,6 +43,10 @@ def build_parser() -> argparse.ArgumentParser:
     m.add_argument("--model-out", metavar="FILE", help="save the fitted model")
     p.add_argument("--output", metavar="FILE.jsonl", default=None)
     p.add_argument("--write-cache", action="store_true", help="replace phoneme_durations in the cache entries")
+    # (these leave no attribute behind when they are not given: an invocation without them parses as it always did)
+    p.add_argument("--scores", action="store_true", default=argparse.SUPPRESS,
+                   help="score every utterance against its transcript: gop, logpost, phone_acc, gop_min, gop_min_token")
+    p.add_argument("--worst", type=int, default=argparse.SUPPRESS, metavar="N", help="with --scores: print the N utterances of lowest gop (default 10)")
     return p
 
 
@@ -50,6 +63,10 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--n-classes must be in 1..256")
     if any(not (0 <= o < args.n_classes) for o in args.optional_id):
         p.error("--optional-id must be a phoneme id below --n-classes")
+    if hasattr(args, "worst") and not getattr(args, "scores", False):
+        p.error("--worst needs --scores")
+    if getattr(args, "worst", 10) < 0:
+        p.error("--worst must be >= 0")
 
 
 def read_cache(cache_dir: str) -> List[Dict]:
@@ -101,11 +118,14 @@ def main(argv=None) -> int:
     if not todo:
         p.error("no utterance of the cache can be aligned")
     mels, ids = [entries[n]["mel"] for n in todo], [entries[n]["ids"] for n in todo]
+    want_scores = getattr(args, "scores", False)
+
+    def batches(fn):
+        return [r for s in range(0, len(todo), args.batch_size)
+                for r in fn(mels[s:s + args.batch_size], ids[s:s + args.batch_size], args.optional_id, model)]
     if args.model_in:
         model = al.load(args.model_in)
-        recs = []
-        for s in range(0, len(todo), args.batch_size):
-            recs += al.align(mels[s:s + args.batch_size], ids[s:s + args.batch_size], args.optional_id, model)
+        recs = batches(al.score if want_scores else al.align)
         durs, how = [r["durations"] for r in recs], f"model {args.model_in}"
         score = sum(r["score"] for r in recs if r["feasible"])
     else:
@@ -113,6 +133,10 @@ def main(argv=None) -> int:
         how, score = f"{len(scores)} passes", scores[-1]
         if args.model_out:
             al.save(model, args.model_out)
+        recs = batches(al.score) if want_scores else None
+    if want_scores:
+        for n, r in zip(todo, recs):
+            entries[n]["scores"] = {k: r[k] for k in SCORE_FIELDS}
     aligned = 0
     for n, d in zip(todo, durs):
         e = entries[n]
@@ -128,10 +152,17 @@ def main(argv=None) -> int:
     if args.output:
         with open(args.output, "w") as f:
             for e in entries:
-                f.write(json.dumps({"name": e["name"], "phoneme_durations": [int(v) for v in e["durations"]]}) + "\n")
+                f.write(json.dumps({"name": e["name"], "phoneme_durations": [int(v) for v in e["durations"]],
+                                    **(e.get("scores", dict.fromkeys(SCORE_FIELDS)) if want_scores else {})}) + "\n")
     frames = sum(int(entries[n]["mel"].shape[0]) for n, d in zip(todo, durs) if d is not None)
     print(f"kokoro-align: {aligned} aligned, {failed} infeasible ({len(entries)} utterances), {how}, "
           f"log-likelihood per frame {score / max(frames, 1):.4f}" + (" -> " + args.cache_dir if args.write_cache else ""))
+    if want_scores:
+        ranked = sorted((e for e in entries if e.get("scores", {}).get("gop") is not None), key=lambda e: e["scores"]["gop"])
+        for e in ranked[:getattr(args, "worst", 10)]:
+            s = e["scores"]
+            print(f"kokoro-align: {e['name']}: gop {s['gop']:.4f}  logpost {s['logpost']:.4f}  phone_acc {s['phone_acc']:.3f}  "
+                  f"gop_min {s['gop_min']:.4f} at token {s['gop_min_token']}")
     return 0 if failed == 0 else 1
 
 

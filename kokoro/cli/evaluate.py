@@ -7,6 +7,7 @@
                 [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
                 [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]] [--gpe-ratio F]
                 [--wavs DIR [--copy-synthesis]]
+                [--pronunciation [MODEL] [--align-iters N] [--optional-id ID ...] [--pronunciation-tokens]]
 
 Synthesizes every selected utterance with the stop rule deciding its length (continuous batching in a pool of --slots rows, or with
 --no-stream in batches of --batch-size), aligns each mel with the cached ground truth by dynamic time warping on K mel cepstra and
@@ -38,7 +39,16 @@ analysis windows W = 256, 512, 1024, and their means mr_sc_dtw and mr_lsd_dtw: t
 --griffin-lim-iters.  A corpus conditioned with kokoro-precompute --trim-silence / --loudness must be compared against its
 --conditioned-wavs directory, not the raw recordings: the cache's frames count the conditioned audio.
 --copy-synthesis (needs --wavs and a vocoder; --checkpoint is optional with it and ignored) leaves the acoustic model out: the cache's
-own mels are vocoded and judged against the recordings, the audio stage's share of the error and the last step of the split."""
+own mels are vocoded and judged against the recordings, the audio stage's share of the error and the last step of the split.
+--pronunciation [MODEL] asks what no warp can: whether the mel holds the phonemes that were requested.  The synthesized mels and the
+cache's own are force-aligned to the phoneme ids with a phone model (kokoro_ruslan_amd.align.PhoneAligner.score) -- the file saved by
+kokoro-align --model-out (another K or class count is named and the exit status is 1), or, without a file, one fitted on the selection's
+cached mels (--align-iters N passes, default 6); --optional-id names phoneme ids whose tokens may get no frame.  The report gains gop
+(mean over the frames of log-likelihood(forced phoneme) - log-likelihood(best phoneme)), logpost (mean log posterior of the forced
+phoneme), phone_acc (share of frames whose best phoneme is the forced one), gop_min / gop_min_token (the worst token), ref_gop,
+ref_logpost, ref_phone_acc (the recording) and gop_gap, phone_acc_gap (synthesis - recording); an utterance a side of which cannot be
+aligned has null there and is counted.  The model was fitted on recordings, so the recording's score is the ceiling: read the gap.
+--pronunciation-tokens adds the per-token lists (pron_tokens, ref_pron_tokens) to the records of --output."""
 from __future__ import annotations
 
 import argparse
@@ -85,6 +95,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--copy-synthesis", action="store_true", default=argparse.SUPPRESS,
                    help="vocode the cache's own mels instead of synthesized ones: the vocoder and denoiser alone (needs --wavs and a "
                         "vocoder; --checkpoint is optional)")
+    p.add_argument("--pronunciation", nargs="?", const="", default=argparse.SUPPRESS, metavar="MODEL",
+                   help="score every mel against its phonemes with a phone model: MODEL saved by kokoro-align --model-out, or, without "
+                        "a file, one fitted on the cached mels of the selection")
+    p.add_argument("--align-iters", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="passes of Viterbi training when --pronunciation fits its model (default 6)")
+    p.add_argument("--optional-id", type=int, action="append", default=argparse.SUPPRESS, metavar="ID",
+                   help="a phoneme id whose tokens may get no frame (with --pronunciation; may be repeated)")
+    p.add_argument("--pronunciation-tokens", action="store_true", default=argparse.SUPPRESS,
+                   help="add the per-token scores to the records of --output (with --pronunciation)")
     return p
 
 
@@ -132,6 +151,19 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
             p.error("--copy-synthesis synthesizes nothing: not with --oracle-durations / --oracle-prosody")
     elif args.checkpoint is None:
         p.error("the following arguments are required: --checkpoint")
+    if not hasattr(args, "pronunciation"):
+        for flag in ("align_iters", "optional_id", "pronunciation_tokens"):
+            if hasattr(args, flag):
+                p.error(f"--{flag.replace('_', '-')} needs --pronunciation")
+        return
+    if getattr(args, "copy_synthesis", False):
+        p.error("--pronunciation scores synthesized mels: not with --copy-synthesis")
+    if hasattr(args, "align_iters") and args.pronunciation:
+        p.error("--align-iters is for fitting a model: not with --pronunciation MODEL")
+    if getattr(args, "align_iters", 6) < 1:
+        p.error("--align-iters must be >= 1")
+    if any(o < 0 for o in getattr(args, "optional_id", [])):
+        p.error("--optional-id must be a phoneme id >= 0")
 
 
 def read_wavs(wav_dir: str, names: List[str]) -> List[torch.Tensor]:
@@ -224,6 +256,43 @@ def oracle_prosody(names, ids, durs, pitch=None, energy=None):
     return out
 
 
+class KeptScores:
+    """A PhoneAligner's score() whose results stay for --pronunciation-tokens: evaluate() scores the synthesis first, then the recordings."""
+
+    def __init__(self, aligner):
+        self.aligner, self.calls = aligner, []
+
+    def score(self, *args, **kwargs):
+        self.calls.append(self.aligner.score(*args, **kwargs))
+        return self.calls[-1]
+
+
+def phone_scoring(args, device, n_classes: int, mels, ids):
+    """(evaluate()'s phone_model / phone_aligner / optional_ids, how the model came about) for --pronunciation: the model of the file,
+    or one fitted on the selection's cached mels.  ValueError names a model of another K or class count, or a phoneme id out of range."""
+    from kokoro_ruslan_amd.align import PhoneAligner
+    opt = list(getattr(args, "optional_id", []))
+    if any(o >= n_classes for o in opt):
+        raise ValueError(f"--optional-id must be a phoneme id below the checkpoint's {n_classes}")
+    al = PhoneAligner(device=device, n_classes=n_classes)
+    if args.pronunciation:
+        model, how = al.load(args.pronunciation), f"model {args.pronunciation}"
+    else:
+        model, _, scores = al.fit(mels, ids, opt, iters=getattr(args, "align_iters", 6))
+        how = f"fitted on the selection in {len(scores)} passes"
+    return dict(phone_model=model, phone_aligner=KeptScores(al), optional_ids=opt), how
+
+
+def token_lists(rec) -> Optional[dict]:
+    """The per-token tensors of a PhoneAligner.score record as JSON lists (None for a token without frames, or an infeasible utterance)."""
+    if rec["tokens"] is None:
+        return None
+    t = rec["tokens"]
+    return {"frames": t["frames"].tolist(), "hits": t["hits"].tolist(),
+            "gop": [None if math.isnan(v) else v for v in t["gop"].tolist()],
+            "logpost": [None if math.isnan(v) else v for v in t["logpost"].tolist()]}
+
+
 def main(argv=None) -> int:
     from kokoro.inference import evaluate as E
     from kokoro.inference import synth as S
@@ -265,13 +334,26 @@ def main(argv=None) -> int:
             pkw.update(denoiser=den, denoise_strength=args.denoise)
         if ref_waves is not None:
             pkw.update(ref_waves=ref_waves)
+    pron = None
+    if hasattr(args, "pronunciation"):
+        try:
+            phone, pron = phone_scoring(args, engine.device, engine.dims.vocab, mels, ids)
+        except (ValueError, OSError) as e:
+            print(f"kokoro-eval: --pronunciation: {e}", file=sys.stderr)
+            return 1
+        pkw.update(phone)
     records, summary = E.evaluate(engine, ids, stress, mels, stream=not args.no_stream, slots=32 if args.slots is None else args.slots,
                                   batch_size=32 if args.batch_size is None else args.batch_size, durations=durs, names=names,
                                   mcep=args.mcep, **pkw, **controls.kwargs())
     print(f"kokoro-eval: {summary['utterances']} utterances ({used} weights, {controls}), "
           f"{100.0 * summary['hit_bound_share']:.1f} % ended at their generation bound"
-          + (f"; audio: {how}, {summary['no_variance']} without pitch and energy in the cache" if audio else ""))
+          + (f"; audio: {how}, {summary['no_variance']} without pitch and energy in the cache" if audio else "")
+          + (f"; pronunciation: {pron}, {summary['pron_infeasible']} that cannot be aligned" if pron else ""))
     _print_metrics(E, summary)
+    if getattr(args, "pronunciation_tokens", False):
+        syn, ref = pkw["phone_aligner"].calls
+        for rec, s, r in zip(records, syn, ref):
+            rec["pron_tokens"], rec["ref_pron_tokens"] = token_lists(s), token_lists(r)
     if args.output:
         with open(args.output, "w") as f:
             json.dump({"records": records, "summary": summary, "controls": controls.kwargs(), "weights": used, "mcep": args.mcep,
@@ -279,7 +361,8 @@ def main(argv=None) -> int:
                        **({"oracle_durations": True} if args.oracle_durations else {}),
                        **({"oracle_prosody": True} if getattr(args, "oracle_prosody", False) else {}),
                        **({"audio": how, "gpe_ratio": args.gpe_ratio} if audio else {}),
-                       **({"wavs": args.wavs} if ref_waves is not None else {})}, f, indent=1)
+                       **({"wavs": args.wavs} if ref_waves is not None else {}),
+                       **({"pronunciation": pron, "optional_ids": pkw["optional_ids"]} if pron else {})}, f, indent=1)
         print(f"kokoro-eval: report -> {args.output}")
     return 0
 

@@ -7,6 +7,8 @@ in cents, the voicing decision error, the gross pitch errors and the energy erro
 waveforms are also held against them along that alignment (kokoro_ruslan_amd.spectral): spectral convergence, level offset and
 log-spectral distance at three analysis windows, the numbers that move with the vocoder, the denoiser and Griffin-Lim's iterations.
 evaluate_vocoder is the same judgement of the audio stage alone: the cache's own mels vocoded and compared with the recordings.
+With a phone model (kokoro_ruslan_amd.align) the mels are also scored against the phonemes that were requested: goodness of
+pronunciation, log posterior and frame accuracy of the synthesis, of the recording, and the gap between them.
 """
 from __future__ import annotations
 
@@ -19,7 +21,9 @@ TRACK_METRICS = ("f0_rmse_cents", "f0_bias_cents", "gpe", "vuv_err", "energy_l1_
 TRACK_COUNTS = ("n_vv", "n_vu", "n_uv", "n_uu", "n_gpe")
 SPECTRAL_METRICS = ("mr_sc_dtw", "mr_lsd_dtw") + tuple(f"{k}_{w}" for w in (256, 512, 1024) for k in ("sc_dtw", "lsd_dtw", "level_db"))
 SPECTRAL_COUNTS = ("spec_steps", "spec_skipped")
-METRICS = ("mcd_dtw", "mel_l1_dtw", "len_ratio", "dur_abs_err") + TRACK_METRICS + SPECTRAL_METRICS
+PRON_FIELDS = ("gop", "logpost", "phone_acc", "gop_min", "gop_min_token")     # of a PhoneAligner.score record
+PRON_METRICS = ("gop", "logpost", "phone_acc", "gop_min", "ref_gop", "ref_logpost", "ref_phone_acc", "gop_gap", "phone_acc_gap")
+METRICS = ("mcd_dtw", "mel_l1_dtw", "len_ratio", "dur_abs_err") + TRACK_METRICS + SPECTRAL_METRICS + PRON_METRICS
 
 
 def _generate(engine, ids, stress, stream: bool, slots: int, batch_size: int, controls: Dict[str, Any], prosody=None):
@@ -62,6 +66,26 @@ def summarize(records: Sequence[Dict]) -> Dict[str, Any]:
             out[k] = {"mean": float(t.mean()), "median": float(torch.quantile(t, 0.5)), "p95": float(torch.quantile(t, 0.95))}
     if any("no_variance" in r for r in records):
         out["no_variance"] = sum(bool(r.get("no_variance")) for r in records)
+    if any("gop_gap" in r for r in records):
+        out["pron_infeasible"] = sum(r.get("gop_gap") is None for r in records)
+    return out
+
+
+def _pron_records(phone_aligner, phone_model, optional_ids, device, mels, ref_mels, ids) -> List[Dict]:
+    """The pronunciation fields of every utterance: the synthesized mels and the recordings' scored against the requested phonemes."""
+    if phone_aligner is None:
+        from kokoro_ruslan_amd.align import PhoneAligner
+        phone_aligner = PhoneAligner(device=device, K=int(phone_model["K"]), n_classes=int(phone_model["n_classes"]))
+    syn = phone_aligner.score(list(mels), list(ids), optional_ids, phone_model)
+    ref = phone_aligner.score(list(ref_mels), list(ids), optional_ids, phone_model)
+    out = []
+    for s, r in zip(syn, ref):
+        rec = {k: s[k] for k in PRON_FIELDS}
+        rec.update({f"ref_{k}": r[k] for k in ("gop", "logpost", "phone_acc")})
+        both = s["feasible"] and r["feasible"]
+        rec["gop_gap"] = s["gop"] - r["gop"] if both else None
+        rec["phone_acc_gap"] = s["phone_acc"] - r["phone_acc"] if both else None
+        out.append(rec)
     return out
 
 
@@ -114,6 +138,7 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
              vocoder_kwargs: Optional[Dict[str, Any]] = None, denoiser=None, denoise_strength: float = 0.005, extractor=None,
              ref_pitch: Optional[Sequence[torch.Tensor]] = None, ref_energy: Optional[Sequence[torch.Tensor]] = None,
              want_audio: bool = False, ref_waves: Optional[Sequence[torch.Tensor]] = None, spectral=None,
+             phone_model: Optional[Dict] = None, phone_aligner=None, optional_ids=(),
              **controls) -> Union[Tuple[List[Dict], Dict[str, Any]], Tuple[List[Dict], Dict[str, Any], List[torch.Tensor]]]:
     """Synthesize every utterance free-running (generate_stream with `slots` rows, or generate_batch `batch_size` at a time) and
     compare it with ref_mels[i] [frames, n_mels].  controls: the stop controls of generate_batch.  Returns (records, summary):
@@ -132,7 +157,15 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
     kokoro-precompute --trim-silence / --loudness: its --conditioned-wavs).  The aligner is then asked for its paths and the (denoised)
     waveforms are measured against the recordings along them by `spectral` (default: a kokoro_ruslan_amd.spectral.SpectralDistance on
     the engine's device); every record gains sc_dtw_W, lsd_dtw_W, level_db_W for W in 256, 512, 1024, mr_sc_dtw, mr_lsd_dtw (None when
-    a side is silent), spec_steps and spec_skipped."""
+    a side is silent), spec_steps and spec_skipped.
+    phone_model (a model of kokoro_ruslan_amd.align.PhoneAligner: kokoro-align --model-out; phone_aligner default: a PhoneAligner of
+    the model's K and classes on the engine's device; optional_ids: the phoneme ids whose tokens may get no frame) asks what no warp
+    can: whether the mel holds the phonemes that were requested.  The synthesized mels and ref_mels are each force-aligned to `ids`
+    and scored in one PhoneAligner.score call; records gain "gop", "logpost", "phone_acc", "gop_min", "gop_min_token" (the synthesis),
+    "ref_gop", "ref_logpost", "ref_phone_acc" (the recording) and "gop_gap", "phone_acc_gap" (synthesis - recording).  The phone model
+    was fitted on recordings, so the recording's own score is the ceiling and the absolute numbers carry the model's fit: the gap is
+    the number to read.  A side that cannot be aligned has None (so has the gap) and is counted in the summary's pron_infeasible.
+    Without phone_model nothing of this is launched and the records are what they were."""
     N = len(ids)
     if len(ref_mels) != N:
         raise ValueError(f"{len(ref_mels)} reference mels for {N} utterances")
@@ -141,6 +174,8 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
             raise ValueError(f"{what}: {len(v)} entries for {N} utterances")
     _check_audio_args(N, vocoder, vocoder_kwargs, denoiser, denoise_strength, extractor, ref_pitch, ref_energy, want_audio, ref_waves,
                       spectral)
+    if phone_model is None and (phone_aligner is not None or tuple(optional_ids)):
+        raise ValueError("phone_aligner and optional_ids need a phone_model: they bear on the pronunciation scores alone")
     if N == 0:
         return ([], summarize([]), []) if want_audio else ([], summarize([]))
     if prosody is not None:
@@ -173,6 +208,7 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
         where = torch.as_tensor(ref_pitch[0]).device                             # (one read for all utterances, wherever the tracks lie)
         bare = [n == 0 for n in torch.stack([(torch.count_nonzero(p) + torch.count_nonzero(e)).to(where)
                                              for p, e in zip(ref_pitch, ref_energy)]).tolist()]
+    pron = None if phone_model is None else _pron_records(phone_aligner, phone_model, optional_ids, engine.device, mels, ref_mels, ids)
     records = []
     for i, (mel, al) in enumerate(zip(mels, aligned)):
         rec = {"name": names[i] if names is not None else i, "frames": int(mel.shape[0]), "ref_frames": int(ref_mels[i].shape[0]),
@@ -186,6 +222,8 @@ def evaluate(engine, ids: Sequence[torch.Tensor], stress: Optional[Sequence[torc
                 rec.update({k: al[k] for k in TRACK_METRICS + TRACK_COUNTS})
         if spec is not None:
             rec.update(spec[i])
+        if pron is not None:
+            rec.update(pron[i])
         records.append(rec)
     return (records, summarize(records), audio) if want_audio else (records, summarize(records))
 

@@ -4,7 +4,8 @@ What a monophone first stage does, reduced to essentials: one diagonal Gaussian 
 (c_1..c_K and c_0, mean-normalised per utterance, plus their first differences), a flat start from the even split, and a few passes of
 Viterbi training: align every utterance with the current Gaussians, re-estimate the Gaussians from the alignment.  `PhoneAligner.fit`
 does that over a corpus held as lists, `align` aligns with a given model; an utterance's result is, bit for bit, what it gives alone.
-align_torch is the fp64 oracle of every step.
+`score` aligns and says how well the frames fit the phonemes they were aligned to (goodness of pronunciation, log posterior, frame
+accuracy, per token and per utterance).  align_torch is the fp64 oracle of every step.
 """
 from __future__ import annotations
 
@@ -175,14 +176,15 @@ class PhoneAligner:
                 codes)
         kk.call("kk_align_backtrack", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, durations, label)
         return {"feat": pk["feat"], "L": L, "score": score, "end": end, "codes": codes, "durations": durations, "label": label,
-                "foff_host": pk["foff_host"], "poff_host": pk["poff_host"], "coff_host": pk["coff_host"]}
+                "foff_host": pk["foff_host"], "poff_host": pk["poff_host"], "coff_host": pk["coff_host"],
+                "ids": pk["ids"], "foff": pk["foff"], "poff": pk["poff"]}
 
     def run_packed(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (),
                    model: Optional[Dict] = None, feats: Optional[Sequence[torch.Tensor]] = None) -> Dict:
         """One batch on the device, nothing read back: the features [D, T_total], L [V, T_total], score fp32 [B], end int32 [B] (the
         end state, -1 when infeasible), the code words, durations int32 [P_total], label int32 [T_total] and the host lists foff_host /
-        poff_host / coff_host (first frame / token / code word of each utterance).  feats: features [T, D] per utterance instead of
-        mels (then mels is None)."""
+        poff_host / coff_host (first frame / token / code word of each utterance), with the packed ids and the offsets foff / poff
+        (int32) as the kernels took them.  feats: features [T, D] per utterance instead of mels (then mels is None)."""
         if model is None:
             raise ValueError("run_packed needs a model: fit one, or load one")
         self._check(mels, ids, feats)
@@ -204,6 +206,74 @@ class PhoneAligner:
         may get no frame.  Returns per utterance {"durations": LongTensor [P] summing to T (0 for a skipped token) | None, "score":
         the log-likelihood of the best path, "feasible": whether a path exists}.  One read by the host."""
         return self._records(self.run_packed(mels, ids, optional_ids, model, feats))
+
+    # ---- pronunciation scores ------------------------------------------------------------------------------------------------------
+    def score_packed(self, run: Dict) -> Dict:
+        """The pronunciation scores (align_torch.scores) of a run_packed() result, on the device, nothing read back: per token
+        gop_sum, lpost_sum (fp64 [P_total]) and hits (int32 [P_total]); per utterance utt_gop, utt_lpost (fp64 [B]) and utt_hits (int32
+        [B]); per frame the scratch margin, lpost (fp64 [T_total]) and amax (int32 [T_total]).  Zeros for an infeasible utterance."""
+        L, foff, poff = run["L"], run["foff_host"], run["poff_host"]
+        if L.dim() != 2 or L.dtype != torch.float32 or not (1 <= L.shape[0] <= MAX_CLASSES):
+            raise ValueError(f"L must be fp32 [V <= {MAX_CLASSES}, frames], not {L.dtype} {tuple(L.shape)}")
+        B, T_total, P_total = len(foff) - 1, int(L.shape[1]), int(run["ids"].shape[0])
+        if B < 1 or len(poff) != B + 1 or foff[-1] != T_total or poff[-1] != P_total:
+            raise ValueError(f"the offsets end at {foff[-1]} frames and {poff[-1]} tokens in {B} utterances; L has {T_total} frames and "
+                             f"there are {P_total} tokens")
+        for k, n in (("label", T_total), ("durations", P_total), ("foff", B + 1), ("poff", B + 1)):
+            if tuple(run[k].shape) != (n,) or run[k].dtype != torch.int32:
+                raise ValueError(f"{k} must be int32 [{n}], not {run[k].dtype} {tuple(run[k].shape)}")
+        if run["ids"].dtype != torch.int32:
+            raise ValueError(f"ids must be int32 [{P_total}], not {run['ids'].dtype}")
+        limit = max_tokens()
+        for n in range(B):
+            P, T = poff[n + 1] - poff[n], foff[n + 1] - foff[n]
+            if not (1 <= P <= limit):
+                raise ValueError(f"utterance {n}: {P} tokens; at most {limit}")
+            if not (1 <= T <= MAX_FRAMES):
+                raise ValueError(f"utterance {n}: {T} frames; at most {MAX_FRAMES}")
+        dev = L.device
+        out = {"margin": torch.empty(T_total, dtype=torch.float64, device=dev), "lpost": torch.empty(T_total, dtype=torch.float64, device=dev),
+               "amax": torch.empty(T_total, dtype=torch.int32, device=dev),
+               "gop_sum": torch.empty(P_total, dtype=torch.float64, device=dev), "lpost_sum": torch.empty(P_total, dtype=torch.float64, device=dev),
+               "hits": torch.empty(P_total, dtype=torch.int32, device=dev),
+               "utt_gop": torch.empty(B, dtype=torch.float64, device=dev), "utt_lpost": torch.empty(B, dtype=torch.float64, device=dev),
+               "utt_hits": torch.empty(B, dtype=torch.int32, device=dev)}
+        kk.call("kk_align_scores", L, T_total, L.shape[0], run["label"], run["durations"], run["ids"], run["foff"], run["poff"], B,
+                out["margin"], out["lpost"], out["amax"], out["gop_sum"], out["lpost_sum"], out["hits"], out["utt_gop"], out["utt_lpost"],
+                out["utt_hits"])
+        return out
+
+    def score(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (),
+              model: Optional[Dict] = None, feats: Optional[Sequence[torch.Tensor]] = None) -> List[Dict]:
+        """align(), and how well every utterance's frames fit the phonemes they were aligned to.  Per utterance {"score", "feasible",
+        "durations" as align gives them; "gop": the mean over its frames of L(forced phone) - L(best phone) (<= 0, the classical goodness
+        of pronunciation), "logpost": the mean log posterior of the forced phone under a flat prior, "phone_acc": the share of frames
+        whose best phone is the forced one; "gop_min", "gop_min_token": the lowest token mean of gop and its index (tokens without frames
+        are ignored, the first of equal minima wins); "tokens": {"frames", "hits" int64 [P], "gop", "logpost" fp64 [P], NaN where a
+        token has no frames}}.  An infeasible utterance has None in every field but score and feasible.  One read by the host."""
+        run = self.run_packed(mels, ids, optional_ids, model, feats)
+        sc = self.score_packed(run)
+        parts = [run["score"], run["durations"], sc["gop_sum"], sc["lpost_sum"], sc["hits"], sc["utt_gop"], sc["utt_lpost"], sc["utt_hits"]]
+        host = torch.cat([p.to(torch.float64) for p in parts]).cpu()              # (fp32 and int32 are exact in fp64) the one read
+        score, dur, gsum, lsum, hits, ug, ul, uh = host.split([int(p.shape[0]) for p in parts])
+        poff, foff, out = run["poff_host"], run["foff_host"], []
+        for n, s in enumerate(score.tolist()):
+            rec = {"score": s, "feasible": s > -math.inf}
+            if not rec["feasible"]:
+                rec.update(dict.fromkeys(("durations", "gop", "logpost", "phone_acc", "gop_min", "gop_min_token", "tokens")))
+                out.append(rec)
+                continue
+            sl, T = slice(poff[n], poff[n + 1]), foff[n + 1] - foff[n]
+            frames = dur[sl].to(torch.int64)
+            nan = torch.full_like(gsum[sl], math.nan)
+            tok = {"frames": frames, "gop": torch.where(frames > 0, gsum[sl] / frames, nan),
+                   "logpost": torch.where(frames > 0, lsum[sl] / frames, nan), "hits": hits[sl].to(torch.int64)}
+            low = torch.where(frames > 0, tok["gop"], torch.full_like(nan, math.inf))
+            at = int((low == low.min()).nonzero()[0])                                # (the first of equal minima)
+            rec.update(durations=frames.clone(), gop=float(ug[n]) / T, logpost=float(ul[n]) / T, phone_acc=float(uh[n]) / T,
+                       gop_min=float(low[at]), gop_min_token=at, tokens=tok)
+            out.append(rec)
+        return out
 
     def fit(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (), iters: int = 6,
             batch_size: int = 64, feats: Optional[Sequence[torch.Tensor]] = None):

@@ -115,6 +115,44 @@ def path_score(L, ids, durations) -> float:
     return float(L[lab, np.arange(L.shape[1])].sum())
 
 
+def scores(L, ids, durations) -> Dict:
+    """Pronunciation scores of an alignment: L [V, T] finite, ids [P], durations [P] >= 0 summing to T (None: infeasible).  Frame t
+    belongs to the token whose span holds it, v(t) is that token's id.  Per frame, in fp64 of the values given: fmax = max_v L(v, t),
+    amax = the lowest v that attains it, margin = L(v(t), t) - fmax (<= 0), lpost = margin - log sum_v exp(L(v, t) - fmax) (the log
+    posterior under a flat prior), hit = [amax == v(t)].  Per token: frames, gop_sum and lpost_sum (the sums of margin and lpost over
+    its frames in ascending order, from 0.0) and hits; a token without frames has zeros.  Per utterance the sums of the tokens' values
+    in ascending token order.  Returns {"frames" int64 [P], "gop_sum", "lpost_sum" fp64 [P], "hits" int64 [P], "T", "gop_total",
+    "lpost_total", "hits_total", "margin", "lpost" fp64 [T], "amax" int64 [T]}; an infeasible utterance has zeros throughout."""
+    L, ids = _f64(L), np.asarray(ids, dtype=np.int64)
+    V, T = L.shape
+    P = ids.shape[0]
+    out = {"frames": np.zeros(P, dtype=np.int64), "gop_sum": np.zeros(P), "lpost_sum": np.zeros(P), "hits": np.zeros(P, dtype=np.int64),
+           "T": T, "gop_total": 0.0, "lpost_total": 0.0, "hits_total": 0, "margin": np.zeros(T), "lpost": np.zeros(T),
+           "amax": L.argmax(0).astype(np.int64)}                                # (argmax: the first, so the lowest, maximiser)
+    if durations is None:
+        return out
+    d = np.asarray(durations, dtype=np.int64)
+    if d.shape != (P,) or (d < 0).any() or int(d.sum()) != T:
+        raise ValueError(f"scores needs {P} durations >= 0 that sum to {T}")
+    fmax = L.max(0)
+    first = 0
+    for p in range(P):
+        g = l = 0.0
+        for t in range(first, first + int(d[p])):
+            m = float(L[ids[p], t] - fmax[t])
+            lp = m - math.log(float(np.exp(L[:, t] - fmax[t]).sum()))
+            out["margin"][t], out["lpost"][t] = m, lp
+            g, l = g + m, l + lp
+            out["hits"][p] += int(out["amax"][t] == ids[p])
+        first += int(d[p])
+        out["frames"][p], out["gop_sum"][p], out["lpost_sum"][p] = d[p], g, l
+    for p in range(P):
+        out["gop_total"] += float(out["gop_sum"][p])
+        out["lpost_total"] += float(out["lpost_sum"][p])
+        out["hits_total"] += int(out["hits"][p])
+    return out
+
+
 def accumulate(feats: Sequence, labels: Sequence, V: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """(count int64 [V], sum x [V, D], sum x^2 [V, D]) over utterances' features [T, D] and frame labels [T] (a label < 0 counts nowhere)."""
     D = _f64(feats[0]).shape[1]

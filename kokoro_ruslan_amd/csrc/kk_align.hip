@@ -23,6 +23,7 @@
 //               dimensions), thread i sums the frames i, i + 256, ... in order, then a fixed tree.  No atomics: two runs give the
 //               same bits.
 // Nothing an utterance computes in feats, viterbi or backtrack depends on the other utterances, and a frame's L on that frame alone.
+// kk_align_scores (two more launches, described where they stand) turns L and an alignment into pronunciation scores.
 #include "kk_common.h"
 
 namespace {
@@ -237,6 +238,133 @@ __global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const floa
     if (tid == 0 && blockIdx.y == 0) count[v] = cnt[0];
 }
 
+// ---- pronunciation scores of an alignment (align_torch.scores) ------------------------------------------------------------------------
+// Two launches, nothing read by the host in between.
+//   score_frames  thread = frame, so a wave reads 64 consecutive floats of every row of L [V][T_total]; L is read once.  SC_VC rows
+//                 are loaded at a time (SC_VC loads in flight per lane).  The frame's maximum and the lowest class that attains it
+//                 are exact; sum_v exp(L(v) - fmax) is an fp64 running sum that is rescaled by exp(old max - new max) at most once
+//                 per SC_VC rows.  The value of the frame's own class (label[t]) is picked up as its row goes by.  Per frame:
+//                 margin = L(label) - fmax and lpost = margin - log(sum), both fp64, and amax.  A frame without a class (label
+//                 outside 0..V-1: the -1 of an infeasible utterance) gets 0 and 0.
+//   score_tokens  one workgroup per utterance.  A thread owns SC_TPT consecutive tokens; an exclusive scan of the durations (wave
+//                 shuffles, then the waves' totals in LDS) gives every token its first frame.  A token's sums run over its frames in
+//                 ascending order from 0.0, its hits count amax == ids[p]; the utterance's totals run over the tokens' values (kept
+//                 in LDS) in ascending token order, one lane per total.  An utterance outside the limits, or whose durations are not
+//                 all in 0..T with the sum T (the zeros of an infeasible one), gets zeros everywhere: every output is written.
+constexpr int SC_VC = 16;                     // rows of L a frame loads at a time
+constexpr int SC_TPT = AL_MAXP / AL_THREADS;  // tokens a thread of score_tokens owns
+
+__global__ __launch_bounds__(AL_THREADS) void align_score_frames_kernel(const float *__restrict__ L, int64_t T_total, int V,
+                                                                        const int *__restrict__ label, double *__restrict__ margin,
+                                                                        double *__restrict__ lpost, int *__restrict__ amax) {
+    const int64_t t = (int64_t)blockIdx.x * AL_THREADS + threadIdx.x;
+    if (t >= T_total) return;
+    const int lab = label[t];
+    const float ninf = -__builtin_inff();
+    float m = ninf, own = 0.f;
+    int am = 0;
+    double s = 0.0;
+    for (int v0 = 0; v0 < V; v0 += SC_VC) {
+        float x[SC_VC];
+#pragma unroll
+        for (int u = 0; u < SC_VC; ++u) x[u] = v0 + u < V ? L[(int64_t)(v0 + u) * T_total + t] : ninf;
+        const float before = m;
+#pragma unroll
+        for (int u = 0; u < SC_VC; ++u) {
+            if (x[u] > m) m = x[u], am = v0 + u;                      // ascending v, strictly greater: the lowest class wins a tie
+            if (v0 + u == lab) own = x[u];
+        }
+        if (v0 > 0 && m > before) s *= exp((double)before - (double)m);
+#pragma unroll
+        for (int u = 0; u < SC_VC; ++u)
+            if (v0 + u < V) s += exp((double)x[u] - (double)m);
+    }
+    const bool has = lab >= 0 && lab < V;
+    const double mg = has ? (double)own - (double)m : 0.0;
+    margin[t] = mg;
+    lpost[t] = has ? mg - log(s) : 0.0;
+    amax[t] = am;
+}
+
+__global__ __launch_bounds__(AL_THREADS) void align_score_tokens_kernel(const double *__restrict__ margin,
+                                                                        const double *__restrict__ lpost,
+                                                                        const int *__restrict__ amax,
+                                                                        const int *__restrict__ durations,
+                                                                        const int *__restrict__ ids, const int *__restrict__ foff,
+                                                                        const int *__restrict__ poff, double *__restrict__ gop_sum,
+                                                                        double *__restrict__ lpost_sum, int *__restrict__ hits,
+                                                                        double *__restrict__ utt_gop, double *__restrict__ utt_lpost,
+                                                                        int *__restrict__ utt_hits) {
+    __shared__ double tok[2][AL_MAXP];                                // the tokens' gop_sum and lpost_sum, for the totals
+    __shared__ int wave_sum[AL_THREADS / 64], bad, hit_total;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f0 = foff[b], T = foff[b + 1] - f0, p0 = poff[b], P = poff[b + 1] - p0;
+    if (P < 1 || P > AL_MAXP || T < 1 || T > AL_MAXT) {               // (the host checks) zeros, whatever its durations hold
+        for (int q = tid; q < P; q += AL_THREADS) gop_sum[p0 + q] = 0.0, lpost_sum[p0 + q] = 0.0, hits[p0 + q] = 0;
+        if (tid == 0) utt_gop[b] = 0.0, utt_lpost[b] = 0.0, utt_hits[b] = 0;
+        return;
+    }
+    if (tid == 0) bad = 0, hit_total = 0;
+    __syncthreads();
+    int d[SC_TPT], mine = 0;
+    bool wrong = false;
+#pragma unroll
+    for (int u = 0; u < SC_TPT; ++u) {
+        const int q = tid * SC_TPT + u;
+        d[u] = q < P ? durations[p0 + q] : 0;
+        if (d[u] < 0 || d[u] > T) wrong = true, d[u] = 0;
+        mine += d[u];                                                 // (at most AL_MAXP * AL_MAXT: no overflow)
+    }
+    int incl = mine;                                                  // inclusive scan over the wave, then over the waves
+#pragma unroll
+    for (int h = 1; h < 64; h <<= 1) {
+        const int up = __shfl_up(incl, h);
+        if (lane >= h) incl += up;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    if (wrong) bad = 1;
+    __syncthreads();
+    int first = incl - mine, total = 0;
+#pragma unroll
+    for (int w = 0; w < AL_THREADS / 64; ++w) {
+        if (w < wave) first += wave_sum[w];
+        total += wave_sum[w];
+    }
+    const bool valid = !bad && total == T;                            // (so no span leaves the utterance's frames)
+    int nh = 0;
+#pragma unroll
+    for (int u = 0; u < SC_TPT; ++u) {
+        const int q = tid * SC_TPT + u;
+        if (q >= P) break;
+        double g = 0.0, l = 0.0;
+        int h = 0;
+        if (valid) {
+            const int id = ids[p0 + q];
+            const int64_t base = (int64_t)f0 + first;
+#pragma unroll 4
+            for (int k = 0; k < d[u]; ++k) {
+                g += margin[base + k];
+                l += lpost[base + k];
+                h += amax[base + k] == id;
+            }
+            first += d[u];
+        }
+        gop_sum[p0 + q] = g, lpost_sum[p0 + q] = l, hits[p0 + q] = h;
+        tok[0][q] = g, tok[1][q] = l;
+        nh += h;
+    }
+    if (nh) atomicAdd(&hit_total, nh);
+    __syncthreads();
+    if (tid < 2) {                                                    // lane 0 the gop total, lane 1 the lpost total: the same loop
+        const double *x = tok[tid];
+        double acc = 0.0;
+#pragma unroll 8
+        for (int q = 0; q < P; ++q) acc += x[q];
+        (tid == 0 ? utt_gop : utt_lpost)[b] = acc;
+    }
+    if (tid == 2) utt_hits[b] = hit_total;
+}
+
 }  // namespace
 
 extern "C" int kk_align_max_tokens(void) { return AL_MAXP; }
@@ -296,5 +424,23 @@ extern "C" int kk_align_accumulate(const float *feat, const int *label, int64_t 
     hipLaunchKernelGGL(align_accumulate_kernel, dim3(V, kk_cdiv(D, ACC_DG)), dim3(AL_THREADS), 0, (hipStream_t)stream, feat, label, T_total,
                        D, (long long *)count, sum, sumsq);
     KK_LAUNCH_CHECK("kk_align_accumulate");
+    return 0;
+}
+
+extern "C" int kk_align_scores(const float *L, int64_t T_total, int V, const int *label, const int *durations, const int *ids,
+                               const int *foff, const int *poff, int B, double *margin, double *lpost, int *amax, double *gop_sum,
+                               double *lpost_sum, int *hits, double *utt_gop, double *utt_lpost, int *utt_hits, void *stream) {
+    KK_REQUIRE(L && label && durations && ids && foff && poff && margin && lpost && amax && gop_sum && lpost_sum && hits && utt_gop &&
+                   utt_lpost && utt_hits && B > 0 && T_total > 0 && T_total < ((int64_t)1 << 31),
+               "kk_align_scores: bad args");
+    KK_REQUIRE(V >= 1 && V <= 256, "kk_align_scores: V = %d; needs 1 <= V <= 256", V);
+    kk_note_kernel("align_score_frames");
+    hipLaunchKernelGGL(align_score_frames_kernel, dim3(kk_cdiv(T_total, AL_THREADS)), dim3(AL_THREADS), 0, (hipStream_t)stream, L, T_total,
+                       V, label, margin, lpost, amax);
+    KK_LAUNCH_CHECK("kk_align_scores (frames)");
+    kk_note_kernel("align_score_tokens");
+    hipLaunchKernelGGL(align_score_tokens_kernel, dim3(B), dim3(AL_THREADS), 0, (hipStream_t)stream, margin, lpost, amax, durations, ids,
+                       foff, poff, gop_sum, lpost_sum, hits, utt_gop, utt_lpost, utt_hits);
+    KK_LAUNCH_CHECK("kk_align_scores (tokens)");
     return 0;
 }

@@ -280,6 +280,7 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_align_viterbi": [_P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "kk_align_backtrack": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "kk_align_accumulate": [_P, _P, _L, _I, _I, _P, _P, _P, _P],
+    "kk_align_scores": [_P, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "kk_mel_finish": [_P, _P, _I, _L, _I, _F, _F, _D, _D, _I, _I, _P, _P, _P, _P],
     "kk_wave_join": [_P, _P, _P, _I, _P, _I, _L, _P, _P, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
