@@ -22,7 +22,9 @@
 extern "C" {
 #endif
 
-#define KK_ABI_VERSION 2 /* 2 (round 6): kk_seg_sumsq takes a record workspace instead of `zeroed`; p_sumsq of kk_adamw_ema /
+#define KK_ABI_VERSION 3 /* 3: kk_im2col3_fwd, kk_groupnorm_relu_fwd and kk_rowdot_fwd take the rows' lengths (`lens`, may be NULL); the
+                          per-row variants of the first two and the row-mask entry point of batched synthesis are gone;
+                          2 (round 6): kk_seg_sumsq takes a record workspace instead of `zeroed`; p_sumsq of kk_adamw_ema /
                           kk_weight_norm_project is an int64 Q34.30 sum; round 5 had already added parameters to kk_losses_fwd,
                           kk_losses_finalize, kk_opt_prepare, kk_adamw_ema, kk_rowdot_bwd and fields to KkOptCfg under version 1 */
 #define KK_MATH_F32 0
@@ -291,20 +293,29 @@ int kk_pad2d_f32(const float *src, int64_t lds, int cols_src, float *dst, int64_
 int kk_frame_mask(const int64_t *lens, uint8_t *mask, int B, int T, void *stream);
 
 /* ---- variance adaptor pieces (variance_predictor.py:89-115, 363-437) ---- */
-/* col[(b,l), c*3+k] = x[b, l+k-1, c] inside the 512-frame chunk of l, else 0. */
-int kk_im2col3_fwd(const float *x, float *col, int B, int L, int C, int chunk, int col_bf16, void *stream);
+/* The three forward calls take `lens` (int32 [B], or NULL): each row's sequence length, which takes the place of L at B = 1, so that
+ * row b of a padded batch gets what the B = 1 forward gives utterance b alone (KokoroEngine.generate_batch).  Row b is then
+ * min(L, lens[b]) frames long: chunk k of it is frames [512k, min(512(k+1), lens[b])), and everything at or past lens[b] is zero, as
+ * it would be outside the single-utterance tensor.  NULL: every row is L frames long (the training step), and lens is never read. */
+/* col[(b,l), c*3+k] = x[b, l+k-1, c] inside the 512-frame chunk of l, else 0.  lens: a tap or an output at a position >= lens[b] is 0
+ * (chunk boundaries unchanged). */
+int kk_im2col3_fwd(const float *x, float *col, const int *lens, int B, int L, int C, int chunk, int col_bf16, void *stream);
 int kk_im2col3_bwd(const float *dcol, float *dx, int B, int L, int C, int chunk, int dcol_bf16, void *stream);
 /* GroupNorm(1,C) over (C x chunk frames) per sample per chunk + ReLU; chunks with < 2 frames yield zeros.
  * stats [B*nchunks, 2] = (mean, rstd).  scratch: 2*B*nchunks doubles, shared by the forward and the backward: each zeroes it when it
- * starts and hands it back zeroed. */
+ * starts and hands it back zeroed.  lens: the statistics of (row b, chunk k) are over the row's own frames of the chunk; zeros at
+ * positions >= lens[b] and in a chunk with < 2 of the row's frames (variance_predictor.py:94-99), stats (0, 0) for a chunk past
+ * the row's end. */
 int kk_groupnorm_relu_fwd(const float *x, const float *gamma, const float *beta, float *y, float *stats,
-                          double *scratch, int B, int L, int C, int chunk, const uint32_t *seed, uint32_t site,
-                          float p, void *stream);
+                          double *scratch, const int *lens, int B, int L, int C, int chunk, const uint32_t *seed,
+                          uint32_t site, float p, void *stream);
 int kk_groupnorm_relu_bwd(const float *dy, const float *x, const float *y, const float *gamma,
                           const float *stats, float *dx, float *dgamma, float *dbeta, double *scratch, int B,
                           int L, int C, int chunk, float p, int dx_bf16 /* dx is written as bf16 */, void *stream);
-/* out[r] = mask[r] ? 0 : dot(x[r,:], w) + b  (Linear(C->1) + masked_fill; also the stop head, model.py:562). */
-int kk_rowdot_fwd(const float *x, const float *w, const float *b, const uint8_t *mask, float *out,
+/* out[r] = dead(r) ? 0 : dot(x[r,:], w) + b  (Linear(C->1) + masked_fill; also the stop head, model.py:562).  Row r = (b, l) is dead
+ * when mask[r] is set (mask may be NULL) or, with chunk > 0, when the chunk of l has < 2 frames.  lens (needs chunk > 0 and
+ * rows == B * L): also when l >= lens[b], and the chunk's frames are counted within row b's own length. */
+int kk_rowdot_fwd(const float *x, const float *w, const float *b, const uint8_t *mask, const int *lens, float *out,
                   int64_t rows, int C, int L, int chunk, int x_bf16, void *stream);
 /* partials == NULL: dw[C] and db[1] are ACCUMULATED with atomics (every workgroup adds to the same C + 1 addresses: ~15 us of
  * same-address serialisation at 256 workgroups).  partials != NULL (C % 4 == 0): nothing is added; workgroup g writes the plain row
@@ -358,21 +369,11 @@ int kk_decode_epilogue(const float *frame_out, const float *stop, float *mel_all
                        void *stream);
 
 /* ---- batched synthesis (KokoroEngine.generate_batch; kk_synth.hip): row b of a padded batch gets what the B = 1 path gives
- * utterance b alone.  lens [B] (int32) is each row's sequence length; it takes the place of L at B = 1.
- * im2col3_rows: kk_im2col3_fwd, except that a tap at a position >= lens[b] reads 0 (chunk boundaries unchanged).
- * groupnorm_relu_rows: kk_groupnorm_relu_fwd with the statistics of (row b, chunk k) over frames [512k, min(512(k+1), lens[b]));
- *   zeros at positions >= lens[b] and in a chunk with < 2 valid frames (variance_predictor.py:94-99).
- * varpred_row_mask: mask_out[b,l] = mask_in[b,l] (mask_in may be NULL) | l >= lens[b] | the chunk of l has < 2 valid frames of row b
- *   (the kk_rowdot_fwd mask of a predictor's Linear(C->1), with chunk = 0 there).
+ * utterance b alone.  (Its variance predictors: kk_im2col3_fwd, kk_groupnorm_relu_fwd and kk_rowdot_fwd with `lens`, above.)
  * decode_epilogue_rows: kk_decode_epilogue for the rows with done[b] == 0, then the stop rule of model/generator.py:67-88 applied to
  *   row b alone: from t >= min_b[b], stop when sigmoid(stop[b]) > (t < expected_b[b] ? thr : min(thr, post_thr)), else, once 30
  *   frames exist, when the mean of the row's last 30 frames < -9.5; also when t + 1 == max_b[b].  A row that stops gets
  *   frames[b] = t + 1, done[b] = 1 and *live -= 1, and is never written again.  *t_dev = t + 1. */
-int kk_im2col3_rows_fwd(const float *x, float *col, const int *lens, int B, int L, int C, int chunk, int col_bf16, void *stream);
-int kk_groupnorm_relu_rows_fwd(const float *x, const float *gamma, const float *beta, float *y, float *stats, double *scratch,
-                               const int *lens, int B, int L, int C, int chunk, const uint32_t *seed, uint32_t site, float p,
-                               void *stream);
-int kk_varpred_row_mask(const uint8_t *mask_in, const int *lens, uint8_t *mask_out, int B, int L, int chunk, void *stream);
 int kk_decode_epilogue_rows(const float *frame_out, const float *stop, float *mel_all, float *stop_all, int *t_dev, uint8_t *done,
                             int *frames, int *live, const int *min_b, const int *expected_b, const int *max_b, int B, int L1, int M,
                             float stop_threshold, float post_expected_stop_threshold, void *stream);

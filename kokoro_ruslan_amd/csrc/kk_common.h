@@ -103,6 +103,19 @@ int kk_gemm16_dgrad_glu(int64_t T, int64_t F, int64_t H, const void *dy, int64_t
 
 static inline int kk_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// Valid frames of row b inside the chunk that starts at frame cb (cb < L) of a [B, L] batch cut into `chunk`-frame chunks.  The row is
+// L frames long, or min(L, lens[b]) when lens is given (batched synthesis: row b as the B = 1 forward sees it); a chunk past the row's
+// end has 0.  The variance predictors' im2col, GroupNorm and Linear(C->1) all take their chunk bounds from here.
+__device__ __forceinline__ int kk_chunk_frames(const int *lens, int b, int L, int cb, int chunk) {
+    int n = L - cb;
+    if (lens) {
+        const int r = lens[b] - cb;
+        n = r < n ? r : n;
+        n = n < 0 ? 0 : n;
+    }
+    return n < chunk ? n : chunk;
+}
+
 // Cross-lane reductions by DPP (data-parallel primitives: the partner lane's value arrives as an operand modifier of a VALU instruction).
 // __shfl_xor compiles to index arithmetic + ds_bpermute_b32 + s_waitcnt — a round trip through the LDS queue per step, ~150 clocks x 6
 // dependent steps per wave reduction, and the row-per-wave kernels (sub-layer tails, LayerNorms, the encoder launch's tail phases) do

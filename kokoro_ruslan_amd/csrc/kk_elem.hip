@@ -236,17 +236,21 @@ __global__ __launch_bounds__(256) void max_i64_kernel(const int64_t *__restrict_
 }
 
 // ------------------------------------------------------------------ conv k=3 as im2col (per 512-frame chunk)
-template <typename TO>
-__global__ __launch_bounds__(256) void im2col3_fwd_kernel(const float *__restrict__ x, TO *__restrict__ col, int64_t total,
-                                                          int L, int C, int chunk) {
+// ROWS: row b ends at lens[b]: a tap or an output at a position >= lens[b] is 0, chunk boundaries unchanged.
+// (lens is the LAST argument of the templated kernels: the argument block of the plain instantiation then starts as it always did.)
+template <typename TO, bool ROWS>
+__global__ __launch_bounds__(256) void im2col3_fwd_kernel(const float *__restrict__ x, TO *__restrict__ col, int64_t total, int L, int C,
+                                                          int chunk, const int *__restrict__ lens) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t fr = i / C;
         const int c = (int)(i - fr * C);
-        const int l = (int)(fr % L);
-        const int cb = (l / chunk) * chunk, ce = cb + chunk < L ? cb + chunk : L;
+        const int l = (int)(fr % L), b = (int)(fr / L);
+        const int cb = (l / chunk) * chunk;
+        int ce = cb + chunk < L ? cb + chunk : L;
+        if (ROWS && lens[b] < ce) ce = lens[b];
         TO *o = col + fr * 3 * C + c * 3;
-        o[0] = (TO)((l - 1 >= cb) ? x[i - C] : 0.f);
-        o[1] = (TO)x[i];
+        o[0] = (TO)((l - 1 >= cb && (!ROWS || l - 1 < ce)) ? x[i - C] : 0.f);
+        o[1] = (TO)((!ROWS || l < ce) ? x[i] : 0.f);
         o[2] = (TO)((l + 1 < ce) ? x[i + C] : 0.f);
     }
 }
@@ -268,11 +272,13 @@ __global__ __launch_bounds__(256) void im2col3_bwd_kernel(const TI *__restrict__
 }
 
 // ------------------------------------------------------------------ Linear(C->1) + masked_fill  (wave per row)
-__device__ __forceinline__ bool row_dead(const uint8_t *mask, int64_t r, int L, int chunk) {
+// lens (may be null; needs chunk > 0 and rows == B * L): row b ends at lens[b], so frames past it and chunks of < 2 of ITS frames are dead.
+__device__ __forceinline__ bool row_dead(const uint8_t *mask, const int *lens, int64_t r, int L, int chunk) {
     if (mask && mask[r]) return true;
     if (chunk > 0) {
-        const int l = (int)(r % L), cb = (l / chunk) * chunk;
-        if ((L - cb < chunk ? L - cb : chunk) < 2) return true;
+        const int b = (int)(r / L), l = (int)(r - (int64_t)b * L);
+        if (lens && l >= lens[b]) return true;
+        if (kk_chunk_frames(lens, b, L, (l / chunk) * chunk, chunk) < 2) return true;
     }
     return false;
 }
@@ -280,7 +286,8 @@ __device__ __forceinline__ bool row_dead(const uint8_t *mask, int64_t r, int L, 
 template <typename TX>
 __global__ __launch_bounds__(256) void rowdot_fwd_kernel(const TX *__restrict__ x, const float *__restrict__ w,
                                                          const float *__restrict__ b, const uint8_t *__restrict__ mask,
-                                                         float *__restrict__ out, int64_t rows, int C, int L, int chunk) {
+                                                         const int *__restrict__ lens, float *__restrict__ out, int64_t rows, int C, int L,
+                                                         int chunk) {
     const int lane = threadIdx.x & 63;
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
         float s = 0.f;
@@ -289,7 +296,7 @@ __global__ __launch_bounds__(256) void rowdot_fwd_kernel(const TX *__restrict__ 
             s += xv.x * wv.x + xv.y * wv.y + xv.z * wv.z + xv.w * wv.w;
         }
         s = wave_sum(s);
-        if (lane == 0) out[r] = row_dead(mask, r, L, chunk) ? 0.f : s + b[0];
+        if (lane == 0) out[r] = row_dead(mask, lens, r, L, chunk) ? 0.f : s + b[0];
     }
 }
 
@@ -304,7 +311,7 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const float *__restrict
     float aw[4] = {0.f, 0.f, 0.f, 0.f};
     float ab = 0.f;
     for (int64_t r = rbeg; r < rend; ++r) {
-        const float d = row_dead(mask, r, L, chunk) ? 0.f : dout[r];
+        const float d = row_dead(mask, nullptr, r, L, chunk) ? 0.f : dout[r];
         if (threadIdx.x == 0) ab += d;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -797,14 +804,14 @@ extern "C" int kk_max_i64(const int64_t *x, int64_t n, int64_t *out, void *strea
     return 0;
 }
 
-extern "C" int kk_im2col3_fwd(const float *x, float *col, int B, int L, int C, int chunk, int col_bf16, void *stream) {
+extern "C" int kk_im2col3_fwd(const float *x, float *col, const int *lens, int B, int L, int C, int chunk, int col_bf16, void *stream) {
     KK_REQUIRE(B > 0 && L > 0 && C > 0 && chunk > 0, "kk_im2col3_fwd: bad shape");
     const int64_t total = (int64_t)B * L * C;
-    if (col_bf16)
-        hipLaunchKernelGGL(im2col3_fwd_kernel<__bf16>, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, x,
-                           reinterpret_cast<__bf16 *>(col), total, L, C, chunk);
-    else
-        hipLaunchKernelGGL(im2col3_fwd_kernel<float>, dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, x, col, total, L, C, chunk);
+#define KK_IM2COL(TY, ROWS) hipLaunchKernelGGL((im2col3_fwd_kernel<TY, ROWS>), dim3(grid_for(total, 8192)), dim3(256), 0, (hipStream_t)stream, x, \
+                                               reinterpret_cast<TY *>(col), total, L, C, chunk, lens)
+    if (col_bf16) { if (lens) KK_IM2COL(__bf16, true); else KK_IM2COL(__bf16, false); }
+    else { if (lens) KK_IM2COL(float, true); else KK_IM2COL(float, false); }
+#undef KK_IM2COL
     KK_LAUNCH_CHECK("kk_im2col3_fwd");
     return 0;
 }
@@ -820,16 +827,19 @@ extern "C" int kk_im2col3_bwd(const float *dcol, float *dx, int B, int L, int C,
     return 0;
 }
 
-extern "C" int kk_rowdot_fwd(const float *x, const float *w, const float *b, const uint8_t *mask, float *out,
+extern "C" int kk_rowdot_fwd(const float *x, const float *w, const float *b, const uint8_t *mask, const int *lens, float *out,
                              int64_t rows, int C, int L, int chunk, int x_bf16, void *stream) {
     KK_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && L > 0, "kk_rowdot_fwd: bad shape");
+    KK_REQUIRE(!lens || (chunk > 0 && rows % L == 0), "kk_rowdot_fwd: lens needs chunk > 0 and rows == B * L (rows=%ld L=%d chunk=%d)",
+               (long)rows, L, chunk);
     int blocks = kk_cdiv(rows, 4);
     if (blocks > 4096) blocks = 4096;
     if (x_bf16)
         hipLaunchKernelGGL(rowdot_fwd_kernel<__bf16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const __bf16 *>(x), w, b, mask, out, rows, C, L, chunk);
+                           reinterpret_cast<const __bf16 *>(x), w, b, mask, lens, out, rows, C, L, chunk);
     else
-        hipLaunchKernelGGL(rowdot_fwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, w, b, mask, out, rows, C, L, chunk);
+        hipLaunchKernelGGL(rowdot_fwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, w, b, mask, lens, out, rows, C, L,
+                           chunk);
     KK_LAUNCH_CHECK("kk_rowdot_fwd");
     return 0;
 }

@@ -377,17 +377,17 @@ __global__ __launch_bounds__(256) void headnorm_rope_bwd_kernel(HeadNormArgs a) 
 }
 
 // ------------------------------------------------------------------ GroupNorm(1,C) per 512-frame chunk + ReLU
-__device__ __forceinline__ int chunk_frames(int L, int chunk, int ci) {
-    const int beg = ci * chunk;
-    return (L - beg) < chunk ? (L - beg) : chunk;
-}
+// ROWS (the forward kernels): row b ends at lens[b] (kk_chunk_frames), so the statistics of (row b, chunk) are over the row's own frames
+// of the chunk, and the output is 0 at positions >= lens[b] and in chunks with < 2 of the row's frames.  Without it lens is never read; it is the kernels' last argument, so that the plain instantiations are the
+// training step's kernels instruction for instruction.
 
 // scratch[(b*nch+ci)*2 + {0,1}] += (sum, sumsq) of slice `blockIdx.x` of the chunk (contiguous frames*C floats).
-__global__ __launch_bounds__(256) void gn_partial_kernel(const float *__restrict__ x, double *__restrict__ scratch, int L,
-                                                         int C, int chunk, int nch, int slices) {
+template <bool ROWS>
+__global__ __launch_bounds__(256) void gn_partial_kernel(const float *__restrict__ x, double *__restrict__ scratch, int L, int C,
+                                                         int chunk, int nch, int slices, const int *__restrict__ lens) {
     __shared__ double red[4];
     const int bc = blockIdx.y, b = bc / nch, ci = bc % nch;
-    const int64_t n = (int64_t)chunk_frames(L, chunk, ci) * C;
+    const int64_t n = (int64_t)kk_chunk_frames(ROWS ? lens : nullptr, b, L, ci * chunk, chunk) * C;
     const float *base = x + ((int64_t)b * L + (int64_t)ci * chunk) * C;
     const int64_t per = ((n / 4 + slices - 1) / slices) * 4;
     const int64_t beg = (int64_t)blockIdx.x * per, end = beg + per < n ? beg + per : n;
@@ -406,24 +406,29 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float *__restrict
 }
 
 // The only reader of the forward's sums: it hands the scratch back zeroed (the forward and the backward share the buffer).
-__global__ void gn_finalize_kernel(double *__restrict__ scratch, float *__restrict__ stats, int L, int C, int chunk,
-                                   int nch, int total) {
+template <bool ROWS>
+__global__ void gn_finalize_kernel(double *__restrict__ scratch, float *__restrict__ stats, int L, int C, int chunk, int nch,
+                                   int total, const int *__restrict__ lens) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const double n = (double)chunk_frames(L, chunk, i % nch) * C;
+    const int frames = kk_chunk_frames(ROWS ? lens : nullptr, i / nch, L, (i % nch) * chunk, chunk);
+    const double n = (double)frames * C;
     const double mean = scratch[i * 2] / n;
     double var = scratch[i * 2 + 1] / n - mean * mean;
     scratch[i * 2] = 0.0;
     scratch[i * 2 + 1] = 0.0;
     if (var < 0) var = 0;
-    stats[i * 2] = (float)mean;
-    stats[i * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
+    const bool past = ROWS && frames == 0;          // chunk past the row's end: never read (the apply writes zeros there)
+    stats[i * 2] = past ? 0.f : (float)mean;
+    stats[i * 2 + 1] = past ? 0.f : (float)(1.0 / sqrt(var + 1e-5));
 }
 
+template <bool ROWS>
 __global__ __launch_bounds__(256) void gn_apply_relu_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
                                                             const float *__restrict__ beta, const float *__restrict__ stats,
                                                             float *__restrict__ y, int64_t total4, int L, int C, int chunk, int nch,
-                                                            const uint32_t *__restrict__ seedp, uint32_t site, float p) {
+                                                            const uint32_t *__restrict__ seedp, uint32_t site, float p,
+                                                            const int *__restrict__ lens) {
     // dropout after the ReLU (variance_predictor.py:106) is fused: dropped elements are stored as 0, kept ones scaled
     const uint32_t thr = seedp ? kk_drop_threshold(p) : 0u, seed = thr ? *seedp : 0u;
     const float ik = thr ? 1.f / (1.f - p) : 1.f;
@@ -433,7 +438,7 @@ __global__ __launch_bounds__(256) void gn_apply_relu_kernel(const float *__restr
         const int64_t fr = e / C;
         const int l = (int)(fr % L), b = (int)(fr / L), ci = l / chunk;
         float4 o = f4zero();
-        if (chunk_frames(L, chunk, ci) >= 2) {
+        if (kk_chunk_frames(ROWS ? lens : nullptr, b, L, ci * chunk, chunk) >= 2 && (!ROWS || l < lens[b])) {
             const float mu = stats[(b * nch + ci) * 2], rs = stats[(b * nch + ci) * 2 + 1];
             const float4 v = ld4(x + e), g = ld4(gamma + c), bt = ld4(beta + c);
             o.x = fmaxf((v.x - mu) * rs * g.x + bt.x, 0.f);
@@ -459,7 +464,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float *__rest
                                                              int chunk, int nch, int slabs, float inv_keep) {
     __shared__ double red[4];
     const int bc = blockIdx.y, b = bc / nch, ci = bc % nch;
-    const int nf = chunk_frames(L, chunk, ci);
+    const int nf = kk_chunk_frames(nullptr, b, L, ci * chunk, chunk);
     const int lanes = 256 / C, c = threadIdx.x % C, fl = threadIdx.x / C;
     const int per = (nf + slabs - 1) / slabs;
     const int fbeg = blockIdx.x * per, fend = fbeg + per < nf ? fbeg + per : nf;
@@ -495,7 +500,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_v4_kernel(const float *__r
     __shared__ double red[4];
     __shared__ float colred[2][1024];                           // [dgamma | dbeta][frame lane][C]: lanes * C = 1024
     const int bc = blockIdx.y, b = bc / nch, ci = bc % nch;
-    const int nf = chunk_frames(L, chunk, ci);
+    const int nf = kk_chunk_frames(nullptr, b, L, ci * chunk, chunk);
     const int C4 = C >> 2, lanes = 256 / C4, c = (threadIdx.x % C4) * 4, fl = threadIdx.x / C4;
     const int per = (nf + slabs - 1) / slabs;
     const int fbeg = blockIdx.x * per, fend = fbeg + per < nf ? fbeg + per : nf;
@@ -556,7 +561,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float *__restri
         const int c = (int)(e % C);
         const int64_t fr = e / C;
         const int l = (int)(fr % L), b = (int)(fr / L), ci = l / chunk, bc = b * nch + ci;
-        const int nf = chunk_frames(L, chunk, ci);
+        const int nf = kk_chunk_frames(nullptr, b, L, ci * chunk, chunk);
         float4 o = f4zero();
         if (nf >= 2) {
             const double n = (double)nf * C;
@@ -706,21 +711,28 @@ extern "C" int kk_headnorm_rope_bwd(const float *dy, int64_t lddy, const float *
 }
 
 extern "C" int kk_groupnorm_relu_fwd(const float *x, const float *gamma, const float *beta, float *y, float *stats,
-                                     double *scratch, int B, int L, int C, int chunk, const uint32_t *seed, uint32_t site,
-                                     float p, void *stream) {
+                                     double *scratch, const int *lens, int B, int L, int C, int chunk, const uint32_t *seed,
+                                     uint32_t site, float p, void *stream) {
     KK_REQUIRE(B > 0 && L > 0 && C > 0 && C % 4 == 0 && chunk > 0 && p >= 0.f && p < 1.f, "kk_groupnorm_relu_fwd: bad shape");
     hipStream_t s = (hipStream_t)stream;
     const int nch = kk_cdiv(L, chunk), total = B * nch;
     const int e = kk_zero_async(scratch, sizeof(double) * 2 * total, s);
     if (e != 0) return e;
     const int slices = 32;
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(slices, total), dim3(256), 0, s, x, scratch, L, C, chunk, nch, slices);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(kk_cdiv(total, 64)), dim3(64), 0, s, scratch, stats, L, C, chunk, nch, total);
     const int64_t total4 = (int64_t)B * L * C / 4;
     int blocks = kk_cdiv(total4, 256);
     { static const int ec = kk_tune_env("KK_ELEM_GRID_CAP", 1024); const int cap_ = ec > 0 ? ec : 4096; if (blocks > cap_) blocks = cap_; }      // (see grid_for, kk_elem.hip)
-    hipLaunchKernelGGL(gn_apply_relu_kernel, dim3(blocks), dim3(256), 0, s, x, gamma, beta, stats, y, total4, L, C, chunk, nch,
-                       p > 0.f ? seed : nullptr, site, p);
+#define KK_GN_FWD(ROWS)                                                                                                                  \
+    do {                                                                                                                                 \
+        hipLaunchKernelGGL(gn_partial_kernel<ROWS>, dim3(slices, total), dim3(256), 0, s, x, scratch, L, C, chunk, nch, slices, lens);  \
+        hipLaunchKernelGGL(gn_finalize_kernel<ROWS>, dim3(kk_cdiv(total, 64)), dim3(64), 0, s, scratch, stats, L, C, chunk, nch, total,  \
+                           lens);                                                                                                         \
+        hipLaunchKernelGGL(gn_apply_relu_kernel<ROWS>, dim3(blocks), dim3(256), 0, s, x, gamma, beta, stats, y, total4, L, C, chunk,     \
+                           nch, p > 0.f ? seed : nullptr, site, p, lens);                                                                 \
+    } while (0)
+    if (lens) KK_GN_FWD(true);
+    else KK_GN_FWD(false);
+#undef KK_GN_FWD
     KK_LAUNCH_CHECK("kk_groupnorm_relu_fwd");
     return 0;
 }

@@ -1247,9 +1247,8 @@ class KokoroEngine:
     # ------------------------------------------------------------------ variance predictor
     def _varpred_fwd(self, key, prefix, x, col1, B, L, mask, out, site=0, p=0.0, lens=None):
         """x [B*L, H]; col1 = im2col3(x) (shared by pitch & energy predictors); out [B*L].
-        lens (int32 [B], inference only: no dropout): row b is a sequence of lens[b] positions, as the B = 1 predictor sees it (the row
-        kernels of kk_synth.hip).  Then col1 = kk_im2col3_rows_fwd(x, lens) and mask = kk_varpred_row_mask(...), which carries the
-        per-row chunk guard, so the rowdot's own is off."""
+        lens (int32 [B], or None: every row is L long): row b is a sequence of lens[b] positions, as the B = 1 predictor sees it; the
+        three kernels take it as it is.  Then col1 = kk_im2col3_fwd(x, lens) too, and mask is the plain padding mask."""
         P, Fv = self.arena.P, self.dims.var_filter
         rows, nch = B * L, -(-L // CHUNK)
         scratch = self._buf("tmp.gn_scratch", 2 * B * nch, dtype=torch.float64)
@@ -1259,18 +1258,11 @@ class KokoroEngine:
             stats = self._buf(f"{key}.st{li}", B * nch, 2)
             self._linear(inp_col, self._Wconv(f"{prefix}.conv_layers.{li}.weight", Fv, 3 * cin), P[f"{prefix}.conv_layers.{li}.bias"], c)
             gw, gb = P[f"{prefix}.norms.{li}.weight"], P[f"{prefix}.norms.{li}.bias"]
-            if lens is None:
-                kk.call("kk_groupnorm_relu_fwd", c, gw, gb, y, stats, scratch, B, L, Fv, CHUNK, self.rng, site + li, p)
-            else:
-                kk.call("kk_groupnorm_relu_rows_fwd", c, gw, gb, y, stats, scratch, lens, B, L, Fv, CHUNK, self.rng, 0, 0.0)
+            kk.call("kk_groupnorm_relu_fwd", c, gw, gb, y, stats, scratch, lens, B, L, Fv, CHUNK, self.rng, site + li, p)
             if li == 0:
                 inp_col, cin = self._buf(f"{key}.col2", rows, 3 * Fv, dtype=col1.dtype), Fv
-                if lens is None:
-                    kk.call("kk_im2col3_fwd", y, inp_col, B, L, Fv, CHUNK, _b16(inp_col))
-                else:
-                    kk.call("kk_im2col3_rows_fwd", y, inp_col, lens, B, L, Fv, CHUNK, _b16(inp_col))
-        kk.call("kk_rowdot_fwd", y, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, out, rows, Fv, L,
-                CHUNK if lens is None else 0, 0)
+                kk.call("kk_im2col3_fwd", y, inp_col, lens, B, L, Fv, CHUNK, _b16(inp_col))
+        kk.call("kk_rowdot_fwd", y, P[f"{prefix}.linear.weight"], P[f"{prefix}.linear.bias"], mask, lens, out, rows, Fv, L, CHUNK, 0)
 
     def _varpred_bwd(self, key, prefix, dout, x, col1, B, L, mask, dx, p=0.0):
         """Accumulate the predictor's parameter grads; write dx (dL/dx) when dx is not None."""
@@ -1548,13 +1540,13 @@ class KokoroEngine:
                 st.be_order, st.be_items = (self._buf("va.be_order", 2, Nd, dtype=torch.int32),
                                             self._buf("va.be_items", 2, n_items, 4, dtype=torch.int32))
                 kk.call("kk_bucket_sort", st.pidx, st.eidx, st.fmask, Nd, d.var_bins, st.be_order, st.be_items)
-            kk.call("kk_im2col3_fwd", st.enc, st.col_e, B, Pn, H, CHUNK, _b16(st.col_e))
+            kk.call("kk_im2col3_fwd", st.enc, st.col_e, None, B, Pn, H, CHUNK, _b16(st.col_e))
             if Tp != T:
                 idx_p, lens_p = self._buf("lr.idx_p", B, Tp, dtype=torch.int64), self._buf("lr.lens_p", B, dtype=torch.int64)
                 kk.call("kk_length_regulate_index", dur, idx_p, lens_p, self._buf("lr.total_p", B, dtype=torch.int64), B, Pn, Tp)
                 kk.call("kk_length_regulate_gather", st.enc, idx_p, st.xf_p, B, Pn, Tp, H)
                 kk.call("kk_frame_mask", lens_p, st.fmask_p, B, Tp)
-            kk.call("kk_im2col3_fwd", st.xf_p, st.col_f, B, Tp, H, CHUNK, _b16(st.col_f))
+            kk.call("kk_im2col3_fwd", st.xf_p, st.col_f, None, B, Tp, H, CHUNK, _b16(st.col_f))
             self._varpred_fwd("vp.dur", f"{VA}.duration_predictor", st.enc, st.col_e, B, Pn, st.text_mask, st.dur_pred, 10, st.p_var)
             self._varpred_fwd("vp.pitch", f"{VA}.pitch_predictor", st.xf_p, st.col_f, B, Tp, st.fmask_p, st.pitch_pred, 12, st.p_var)
             self._varpred_fwd("vp.energy", f"{VA}.energy_predictor", st.xf_p, st.col_f, B, Tp, st.fmask_p, st.energy_pred, 14, st.p_var)
@@ -1582,7 +1574,7 @@ class KokoroEngine:
         st.dec_last, st.dec_out = y, n1                   # (n1: decoder.norm of the last stream, from the last feed-forward's tail)
         st.mel_pred, st.stop = self._buf("out.mel", B, T, M), self._buf("out.stop", B, T)
         self._linear(st.dec_out, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], st.mel_pred.view(Nd, M))
-        kk.call("kk_rowdot_fwd", st.dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, st.stop, Nd, H, T, 0,
+        kk.call("kk_rowdot_fwd", st.dec_out, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, None, st.stop, Nd, H, T, 0,
                 _b16(st.dec_out))
 
     def _fb_losses(self, st) -> Dict[str, torch.Tensor]:
@@ -1824,7 +1816,7 @@ class KokoroEngine:
             n1 = self._ffn_fwd(key + ".ff", pf + ".ff", n3, yc, yo, d.dec_ff, 1, next_ln=lay.next_ln["ff"], split_k=split_k)
             yl = yo
         self._linear(n1, self._W("mel_projection_out.weight"), P["mel_projection_out.bias"], frame_out, split_k=split_k)
-        kk.call("kk_rowdot_fwd", n1, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, stop_now, rows, H, 1, 0, _b16(n1))
+        kk.call("kk_rowdot_fwd", n1, P["stop_token_predictor.weight"], P["stop_token_predictor.bias"], None, None, stop_now, rows, H, 1, 0, _b16(n1))
         return frame_out, stop_now
 
     def _decode_step(self, ns, B, T, max_expected, fm2):
@@ -1891,12 +1883,7 @@ class KokoroEngine:
         kk.call("kk_length_regulate_gather", enc, idx, xf, B, Pn, T, H)
         fmask = (torch.arange(T, device=self.device)[None, :] >= lens[:, None]).to(torch.uint8).contiguous()
         col_f = self._buf(ns + "vp.col_frames", Nd, 3 * H, dtype=ddt)
-        if flens is None:
-            kk.call("kk_im2col3_fwd", xf, col_f, B, T, H, CHUNK, _b16(col_f))
-        else:
-            pad, fmask = fmask, self._buf(ns + "vp.frame_mask", B, T, dtype=torch.uint8)
-            kk.call("kk_varpred_row_mask", pad, flens, fmask, B, T, CHUNK)
-            kk.call("kk_im2col3_rows_fwd", xf, col_f, flens, B, T, H, CHUNK, _b16(col_f))
+        kk.call("kk_im2col3_fwd", xf, col_f, flens, B, T, H, CHUNK, _b16(col_f))
         pitch, energy = self._buf(ns + "out.pitch", B, T), self._buf(ns + "out.energy", B, T)
         self._varpred_fwd(ns + "vp.pitch", f"{VA}.pitch_predictor", xf, col_f, B, T, fmask, pitch, lens=flens)
         self._varpred_fwd(ns + "vp.energy", f"{VA}.energy_predictor", xf, col_f, B, T, fmask, energy, lens=flens)
@@ -2020,7 +2007,7 @@ class KokoroEngine:
             # ---- duration predictor ----
             log_dur = self._buf("out.log_dur", B, Pn)
             col_e = self._buf("vp.col_enc", B * Pn, 3 * H, dtype=self.enc_dt)
-            kk.call("kk_im2col3_fwd", enc, col_e, B, Pn, H, CHUNK, _b16(col_e))
+            kk.call("kk_im2col3_fwd", enc, col_e, None, B, Pn, H, CHUNK, _b16(col_e))
             self._varpred_fwd("vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, text_mask, log_dur)
             if controls is None:
                 dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
@@ -2101,10 +2088,8 @@ class KokoroEngine:
         plens = torch.tensor(lens_p, dtype=torch.int32).to(self.device)
         log_dur = self._buf(ns + "out.log_dur", B, Pn)
         col_e = self._buf(ns + "vp.col_enc", B * Pn, 3 * H, dtype=self.enc_dt)
-        kk.call("kk_im2col3_rows_fwd", enc, col_e, plens, B, Pn, H, CHUNK, _b16(col_e))
-        dmask = self._buf(ns + "vp.dur_mask", B, Pn, dtype=torch.uint8)
-        kk.call("kk_varpred_row_mask", text_mask, plens, dmask, B, Pn, CHUNK)
-        self._varpred_fwd(ns + "vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, dmask, log_dur, lens=plens)
+        kk.call("kk_im2col3_fwd", enc, col_e, plens, B, Pn, H, CHUNK, _b16(col_e))
+        self._varpred_fwd(ns + "vp.dur", f"{VA}.duration_predictor", enc, col_e, B, Pn, text_mask, log_dur, lens=plens)
         if controls is None:
             dur = torch.clamp(torch.round(torch.expm1(log_dur)), min=0).to(torch.int64)
             sums = dur.sum(dim=1).cpu().tolist()               # (host sync: the row lengths size everything below)
@@ -2136,8 +2121,8 @@ class KokoroEngine:
 
         Row lengths are those of the single-utterance call: L_b = P_b phonemes, T_b = max(sum(dur_b), 3) frames (frames in
         [sum(dur_b), T_b) are zero inputs that count in the predictors' convolutions and GroupNorms, as at B = 1).  The stages are
-        generate's, on workspace keys of their own ("syn."): the duration, pitch and energy predictors are given the row lengths
-        and so run the row kernels (_varpred_fwd(lens=...), _expand_fwd(flens=...)); the encoder (key mask), length regulator,
+        generate's, on workspace keys of their own ("syn."): the duration, pitch and energy predictors are given the row lengths,
+        which their kernels take as `lens` (_varpred_fwd(lens=...), _expand_fwd(flens=...)); the encoder (key mask), length regulator,
         bucket embeddings and cross-attention (frame mask) are row-independent already.  Each row has its own bounds
         (_generation_bounds) and its own stop rule, applied on the device by kk_decode_epilogue_rows inside the replayed step; the
         host reads only the count of live rows, every `check_every` frames.

@@ -199,11 +199,11 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_max_i64": [_P, _L, _P, _P],
     "kk_pad2d_f32": [_P, _L, _I, _P, _L, _I, _L, _P],
     "kk_frame_mask": [_P, _P, _I, _I, _P],
-    "kk_im2col3_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "kk_im2col3_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "kk_im2col3_bwd": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "kk_groupnorm_relu_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _U, _F, _P],
+    "kk_groupnorm_relu_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _U, _F, _P],
     "kk_groupnorm_relu_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
-    "kk_rowdot_fwd": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "kk_rowdot_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
     "kk_rowdot_bwd": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P],
     "kk_rowdot_bwd_blocks": [_L],
     "kk_bucket_embed_add_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -229,9 +229,6 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_decode_prologue": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "kk_decode_cache_append": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "kk_decode_epilogue": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "kk_im2col3_rows_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "kk_groupnorm_relu_rows_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _U, _F, _P],
-    "kk_varpred_row_mask": [_P, _P, _P, _I, _I, _I, _P],
     "kk_decode_epilogue_rows": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
     "kk_attn_decode_rows": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _F, _I, _P],
     "kk_decode_prologue_rows": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -329,7 +326,7 @@ def profile_stop():
     return [(n, a, s.elapsed_time(e)) for n, a, s, e in rec]
 
 
-ABI_VERSION = 2        # include/kokoro_hip.h: KK_ABI_VERSION
+ABI_VERSION = 3        # include/kokoro_hip.h: KK_ABI_VERSION
 
 
 def use_library(flavour: str) -> None:

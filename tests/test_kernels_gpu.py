@@ -459,17 +459,17 @@ def test_variance_predictor_chain(kk, L):
     acts, cin, inp = [], H, xd
     for li in range(2):
         col = torch.empty(rows, 3 * cin, device="cuda")
-        kk.call("kk_im2col3_fwd", inp, col, B, L, cin, 512, 0)
+        kk.call("kk_im2col3_fwd", inp, col, None, B, L, cin, 512, 0)
         c = torch.empty(rows, Fv, device="cuda")
         kk.call("kk_gemm", 0, 0, rows, Fv, 3 * cin, 1.0, col, 3 * cin, Pd[f"vp.conv_layers.{li}.weight"], 3 * cin, 0.0, c, Fv,
                 Pd[f"vp.conv_layers.{li}.bias"], None, 0, 0, 1, 0, 0)
         y, stats = torch.empty(rows, Fv, device="cuda"), torch.empty(B * nch, 2, device="cuda")
-        kk.call("kk_groupnorm_relu_fwd", c, Pd[f"vp.norms.{li}.weight"], Pd[f"vp.norms.{li}.bias"], y, stats, scratch, B, L, Fv, 512, None, 0, 0.0)
+        kk.call("kk_groupnorm_relu_fwd", c, Pd[f"vp.norms.{li}.weight"], Pd[f"vp.norms.{li}.bias"], y, stats, scratch, None, B, L, Fv, 512, None, 0, 0.0)
         acts.append((col, c, y, stats, cin))
         inp, cin = y, Fv
     md = dev(mask.to(torch.uint8))
     out = torch.empty(rows, device="cuda")
-    kk.call("kk_rowdot_fwd", inp, Pd["vp.linear.weight"], Pd["vp.linear.bias"], md, out, rows, Fv, L, 512, 0)
+    kk.call("kk_rowdot_fwd", inp, Pd["vp.linear.weight"], Pd["vp.linear.bias"], md, None, out, rows, Fv, L, 512, 0)
     close(out.view(B, L), ref, 2e-4, 2e-4, "varpred fwd")
     dy = torch.empty(rows, Fv, device="cuda")
     kk.call("kk_rowdot_bwd", dev(dout), inp, Pd["vp.linear.weight"], md, dy, Gd["vp.linear.weight"], Gd["vp.linear.bias"],
@@ -601,7 +601,7 @@ def test_side_branch_backward_kernels_model_shapes(kk, B, L, C, chunk, xbf):
         nch = (L + ck - 1) // ck
         y, st = torch.empty(rows, C, device="cuda"), torch.empty(B * nch, 2, device="cuda")
         scr = torch.zeros(2 * B * nch, dtype=torch.float64, device="cuda")
-        kk.call("kk_groupnorm_relu_fwd", xg, gam, bet, y, st, scr, B, L, C, ck, None, 0, 0.0)
+        kk.call("kk_groupnorm_relu_fwd", xg, gam, bet, y, st, scr, None, B, L, C, ck, None, 0, 0.0)
         dy = dev(torch.randn(rows, C, generator=g))
         dxg, dg, dbt = torch.empty(rows, C, device="cuda"), torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
         kk.call("kk_groupnorm_relu_bwd", dy, xg, y, gam, st, dxg, dg, dbt, scr, B, L, C, ck, 0.0, 0)
@@ -878,8 +878,8 @@ def test_fused_dropout_masks_match_between_forward_and_backward(kk):
     x, gam, bet = torch.randn(Bn * L, C, generator=g), torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1
     y0, y1, st = torch.empty(Bn * L, C, device="cuda"), torch.empty(Bn * L, C, device="cuda"), torch.empty(Bn, 2, device="cuda")
     scr = torch.zeros(2 * Bn, dtype=torch.float64, device="cuda")
-    kk.call("kk_groupnorm_relu_fwd", dev(x), dev(gam), dev(bet), y0, st, scr, Bn, L, C, 512, None, 0, 0.0)
-    kk.call("kk_groupnorm_relu_fwd", dev(x), dev(gam), dev(bet), y1, st, scr, Bn, L, C, 512, _seed(), 2, pv)
+    kk.call("kk_groupnorm_relu_fwd", dev(x), dev(gam), dev(bet), y0, st, scr, None, Bn, L, C, 512, None, 0, 0.0)
+    kk.call("kk_groupnorm_relu_fwd", dev(x), dev(gam), dev(bet), y1, st, scr, None, Bn, L, C, 512, _seed(), 2, pv)
     pos = y0 > 1e-6
     mask = torch.where(pos, y1 / y0.clamp(min=1e-6), torch.ones_like(y0)).cpu()
     assert abs(float((mask[pos.cpu()] > 0).float().mean()) - (1 - pv)) < 0.03
@@ -1107,8 +1107,8 @@ def test_elementwise_bf16_storage(kk):
     B, L, C = 2, 600, 64
     x = dev(torch.randn(B * L, C, generator=g))
     c32, c16 = torch.empty(B * L, 3 * C, device="cuda"), torch.empty(B * L, 3 * C, device="cuda", dtype=torch.bfloat16)
-    kk.call("kk_im2col3_fwd", x, c32, B, L, C, 512, 0)
-    kk.call("kk_im2col3_fwd", x, c16, B, L, C, 512, 1)
+    kk.call("kk_im2col3_fwd", x, c32, None, B, L, C, 512, 0)
+    kk.call("kk_im2col3_fwd", x, c16, None, B, L, C, 512, 1)
     assert torch.equal(c16, c32.bfloat16())
     dcol = dev(_r16(torch.randn(B * L, 3 * C, generator=g)))
     a32, a16 = torch.empty(B * L, C, device="cuda"), torch.empty(B * L, C, device="cuda")
@@ -1118,8 +1118,8 @@ def test_elementwise_bf16_storage(kk):
     # rowdot with a bf16 x (stop head on the bf16 decoder output)
     xr, w, b = dev(_r16(torch.randn(B * L, C, generator=g))), dev(torch.randn(C, generator=g)), dev(torch.randn(1, generator=g))
     o32, o16 = torch.empty(B * L, device="cuda"), torch.empty(B * L, device="cuda")
-    kk.call("kk_rowdot_fwd", xr, w, b, None, o32, B * L, C, L, 0, 0)
-    kk.call("kk_rowdot_fwd", xr.bfloat16(), w, b, None, o16, B * L, C, L, 0, 1)
+    kk.call("kk_rowdot_fwd", xr, w, b, None, None, o32, B * L, C, L, 0, 0)
+    kk.call("kk_rowdot_fwd", xr.bfloat16(), w, b, None, None, o16, B * L, C, L, 0, 1)
     close(o16, o32, 1e-5, 1e-5, "rowdot fwd bf16 x")
     dout = dev(torch.randn(B * L, generator=g))
     dw32, dw16, db32, db16 = (torch.zeros(n, device="cuda") for n in (C, C, 1, 1))

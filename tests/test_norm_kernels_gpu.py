@@ -484,7 +484,7 @@ def test_groupnorm_relu_fp64(kk, B, L, C, chunk, dx_bf16):
     xd, gd, bd, dyd = dev(x), dev(gamma), dev(beta), dev(dy)
     tag = f"groupnorm {B}x{L}x{C} chunk={chunk} dx_bf16={dx_bf16}"
     y, st, scr = Guarded(rows, C), Guarded(B * nch, 2), Guarded(1, 2 * B * nch, dtype=torch.float64)
-    kk.call("kk_groupnorm_relu_fwd", xd, gd, bd, y.t, st.t, scr.t, B, L, C, chunk, None, 0, 0.0)
+    kk.call("kk_groupnorm_relu_fwd", xd, gd, bd, y.t, st.t, scr.t, None, B, L, C, chunk, None, 0, 0.0)
     torch.cuda.synchronize()
     assert y.intact() and st.intact() and scr.intact(), f"{tag}: a guard row / column was written"
     bounded(f"{tag} y", y.t, r32["y"], r64["y"])
@@ -521,7 +521,7 @@ def test_groupnorm_relu_scratch_is_zero_after_use(kk, B, L, C, chunk):
     xd, gd = dev(x), dev(gamma)
     y, st = torch.empty(rows, C, device="cuda"), torch.empty(B * nch, 2, device="cuda")
     scr = torch.zeros(2 * B * nch, dtype=torch.float64, device="cuda")
-    kk.call("kk_groupnorm_relu_fwd", xd, gd, dev(beta), y, st, scr, B, L, C, chunk, None, 0, 0.0)
+    kk.call("kk_groupnorm_relu_fwd", xd, gd, dev(beta), y, st, scr, None, B, L, C, chunk, None, 0, 0.0)
     after_fwd = float(scr.abs().max())
     dx, dg, db = torch.empty(rows, C, device="cuda"), torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
     kk.call("kk_groupnorm_relu_bwd", dev(dy), xd, y, gd, st, dx, dg, db, scr, B, L, C, chunk, 0.0, 0)
@@ -540,8 +540,8 @@ def test_groupnorm_relu_dropout_backward_equals_explicit_mask(kk, B, L, C, chunk
     y0, y1, st = torch.empty(rows, C, device="cuda"), torch.empty(rows, C, device="cuda"), torch.empty(B * nch, 2, device="cuda")
     scr = torch.zeros(2 * B * nch, dtype=torch.float64, device="cuda")
     seed = torch.tensor([1234], dtype=torch.int32, device="cuda")
-    kk.call("kk_groupnorm_relu_fwd", xd, gd, bd, y0, st, scr, B, L, C, chunk, None, 0, 0.0)
-    kk.call("kk_groupnorm_relu_fwd", xd, gd, bd, y1, st, scr, B, L, C, chunk, seed, 2, p)
+    kk.call("kk_groupnorm_relu_fwd", xd, gd, bd, y0, st, scr, None, B, L, C, chunk, None, 0, 0.0)
+    kk.call("kk_groupnorm_relu_fwd", xd, gd, bd, y1, st, scr, None, B, L, C, chunk, seed, 2, p)
     pos = y0 > 1e-6
     ratio = (y1[pos] / y0[pos]).cpu()
     assert bool(((ratio.abs() < 1e-5) | ((ratio - 1 / (1 - p)).abs() < 1e-4)).all()), "mask values must be 0 or 1/keep"

@@ -1,5 +1,5 @@
-"""GPU suite, kernel level: the batched-synthesis kernels of kk_synth.hip (KokoroEngine.generate_batch) against plain torch
-restatements of what each row would get at B = 1."""
+"""GPU suite, kernel level: the batched-synthesis kernels (KokoroEngine.generate_batch: the variance predictors' kernels with the rows'
+lengths, the decode epilogue of kk_synth.hip) against plain torch restatements of what each row would get at B = 1."""
 import math
 
 import pytest
@@ -47,7 +47,7 @@ def test_im2col3_rows_fwd(kk, bf16):
     B = len(lens)
     x = torch.randn(B * L, C, generator=torch.Generator().manual_seed(1))
     col = torch.full((B * L, 3 * C), 7.0, device="cuda", dtype=torch.bfloat16 if bf16 else torch.float32)
-    kk.call("kk_im2col3_rows_fwd", x.cuda(), col, _lens_t(lens), B, L, C, CHUNK, 1 if bf16 else 0)
+    kk.call("kk_im2col3_fwd", x.cuda(), col, _lens_t(lens), B, L, C, CHUNK, 1 if bf16 else 0)
     ref = _ref_im2col3_rows(x, lens, L, C)
     if bf16:
         ref = ref.to(torch.bfloat16)
@@ -55,12 +55,12 @@ def test_im2col3_rows_fwd(kk, bf16):
 
 
 def test_im2col3_rows_equals_the_plain_kernel_at_full_length(kk):
-    """Rows of full length: exactly kk_im2col3_fwd."""
+    """Rows of full length: exactly kk_im2col3_fwd without lens."""
     B, L, C = 3, 700, 16
     x = torch.randn(B * L, C, generator=torch.Generator().manual_seed(2)).cuda()
     a, b = torch.empty(B * L, 3 * C, device="cuda"), torch.empty(B * L, 3 * C, device="cuda")
-    kk.call("kk_im2col3_fwd", x, a, B, L, C, CHUNK, 0)
-    kk.call("kk_im2col3_rows_fwd", x, b, _lens_t([L] * B), B, L, C, CHUNK, 0)
+    kk.call("kk_im2col3_fwd", x, a, None, B, L, C, CHUNK, 0)
+    kk.call("kk_im2col3_fwd", x, b, _lens_t([L] * B), B, L, C, CHUNK, 0)
     assert torch.equal(a, b)
 
 
@@ -74,9 +74,10 @@ def test_groupnorm_relu_rows_fwd(kk):
     nch = -(-L // CHUNK)
     y = torch.full((B * L, C), 9.0, device="cuda")
     stats = torch.empty(B * nch, 2, device="cuda")
-    scratch = torch.empty(2 * B * nch, dtype=torch.float64, device="cuda")
-    kk.call("kk_groupnorm_relu_rows_fwd", x.cuda(), gamma.cuda(), beta.cuda(), y, stats, scratch, _lens_t(lens), B, L, C, CHUNK,
+    scratch = torch.full((2 * B * nch,), float("nan"), dtype=torch.float64, device="cuda")      # the call zeroes it itself
+    kk.call("kk_groupnorm_relu_fwd", x.cuda(), gamma.cuda(), beta.cuda(), y, stats, scratch, _lens_t(lens), B, L, C, CHUNK,
             None, 0, 0.0)
+    assert float(scratch.abs().max()) == 0.0, "the scratch is handed back zeroed"
     ref = torch.zeros(B, L, C)
     xv = x.view(B, L, C)
     for b, n in enumerate(lens):
@@ -92,28 +93,58 @@ def test_groupnorm_relu_rows_fwd(kk):
     assert float(got[2, 511:].abs().max()) == 0.0, "positions past the row's length are zeros"
 
 
-def test_varpred_row_mask(kk):
-    lens, L = [1, 2, 511, 513, 600, 1025], 1100
-    B = len(lens)
-    mask_in = (torch.rand(B, L, generator=torch.Generator().manual_seed(4)) < 0.1).to(torch.uint8)
-    out = torch.full((B, L), 5, dtype=torch.uint8, device="cuda")
-    kk.call("kk_varpred_row_mask", mask_in.cuda(), _lens_t(lens), out, B, L, CHUNK)
-    ref = mask_in.bool().clone()
+def test_groupnorm_relu_rows_equals_the_plain_kernel_at_full_length(kk):
+    """lens = [L] * B against lens = None, bit for bit in y and stats.  The input is multiples of 0.25 in [-2, 2]: every fp32 partial
+    sum (<= 2048 terms of at most 2, resp. 4 = 64 quarter-squares, far below 2^24 units of 1/16) and every fp64 sum is exact, so the
+    order in which the fp64 atomics arrive cannot change a bit and equality is a fair demand."""
+    B, L, C, chunk = 3, 513, 32, 512
+    g = torch.Generator().manual_seed(6)
+    x = (torch.randint(-8, 9, (B * L, C), generator=g).float() * 0.25).cuda()
+    gamma, beta = (torch.randn(C, generator=g) * 0.5 + 1.0).cuda(), (torch.randn(C, generator=g) * 0.2).cuda()
+    nch = -(-L // chunk)
+    res = []
+    for lens in (None, _lens_t([L] * B)):
+        y, stats = torch.full((B * L, C), 9.0, device="cuda"), torch.full((B * nch, 2), 9.0, device="cuda")
+        scratch = torch.full((2 * B * nch,), float("nan"), dtype=torch.float64, device="cuda")
+        kk.call("kk_groupnorm_relu_fwd", x, gamma, beta, y, stats, scratch, lens, B, L, C, chunk, None, 0, 0.0)
+        assert float(scratch.abs().max()) == 0.0
+        res.append((y, stats))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+    assert float(res[0][0].abs().max()) > 0.0
+
+
+def _ref_row_mask(mask_in, lens, L):
+    """The rows of a predictor's Linear(C->1) that are filled with 0: padding, frames past the row's length, chunks of < 2 valid frames."""
+    ref = mask_in.bool().clone() if mask_in is not None else torch.zeros(len(lens), L, dtype=torch.bool)
     for b, n in enumerate(lens):
         ref[b, n:] = True
         for s in range(0, n, CHUNK):
             if min(s + CHUNK, n) - s < 2:
                 ref[b, s:s + CHUNK] = True
-    assert torch.equal(out.cpu().bool(), ref)
-    out2 = torch.empty(B, L, dtype=torch.uint8, device="cuda")
-    kk.call("kk_varpred_row_mask", None, _lens_t(lens), out2, B, L, CHUNK)
-    ref2 = torch.zeros(B, L, dtype=torch.bool)
-    for b, n in enumerate(lens):
-        ref2[b, n:] = True
-        for s in range(0, n, CHUNK):
-            if min(s + CHUNK, n) - s < 2:
-                ref2[b, s:s + CHUNK] = True
-    assert torch.equal(out2.cpu().bool(), ref2)
+    return ref
+
+
+def test_varpred_row_mask(kk):
+    """kk_rowdot_fwd with lens: with w = 0 and b = 1 the output IS the complement of the row mask, element for element."""
+    lens, L, C = [1, 2, 511, 513, 600, 1025], 1100, 8
+    B = len(lens)
+    g = torch.Generator().manual_seed(4)
+    mask_in = (torch.rand(B, L, generator=g) < 0.1).to(torch.uint8)
+    x = torch.randn(B * L, C, generator=g).cuda()
+    w0, b1 = torch.zeros(C, device="cuda"), torch.ones(1, device="cuda")
+    for m in (mask_in, None):
+        out = torch.full((B, L), 5.0, device="cuda")
+        kk.call("kk_rowdot_fwd", x, w0, b1, m.cuda() if m is not None else None, _lens_t(lens), out, B * L, C, L, CHUNK, 0)
+        ref = _ref_row_mask(m, lens, L)
+        assert torch.equal(out.cpu(), (~ref).float()), "exactly 0.0 on the masked rows, exactly 1.0 elsewhere"
+    # a random w: x @ w + b on the live rows, in float64 (atol = rtol = 1e-5: the rowdot's own tolerance in test_kernels_gpu.py)
+    w, bias = torch.randn(C, generator=g), torch.randn(1, generator=g)
+    out = torch.full((B, L), 5.0, device="cuda")
+    kk.call("kk_rowdot_fwd", x, w.cuda(), bias.cuda(), mask_in.cuda(), _lens_t(lens), out, B * L, C, L, CHUNK, 0)
+    dead = _ref_row_mask(mask_in, lens, L)
+    ref = (x.cpu().double() @ w.double() + bias.double()).view(B, L).masked_fill(dead, 0.0)
+    torch.testing.assert_close(out.cpu().double(), ref, atol=1e-5, rtol=1e-5)
+    assert float(out.cpu()[dead].abs().max()) == 0.0
 
 
 def _ref_stop_rule(frames, logits, bounds, thr, post, steps):
