@@ -649,6 +649,20 @@ int kk_align_viterbi(const float *L, int64_t T_total, const int *ids, const unsi
  * label [T_total] (the phoneme id of every frame); an infeasible utterance gets durations 0 and labels -1 */
 int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids, const int *end,
                        int B, int *durations, int *label, void *stream);
+/* multi-state phone models: `states` = S in 1..kk_align_max_states() states per phoneme in a left-to-right chain, class v S + j, L:
+ * [V S][T_total].  Sigma(p, j, t) = L[ids[p] S + j][t] + max(stay Sigma(p, j, t-1); advance Sigma(p, j-1, t-1) if j > 0, else
+ * Sigma(p-1, S-1, t-1); skip Sigma(p-2, S-1, t-1) only for j = 0 and opt[p-1]), a later candidate only when strictly greater.  Start
+ * (0, 0) and, if opt[0], (1, 0); end (P-1, S-1), or (P-2, S-1) when opt[P-1] and strictly greater.  score and end (the end TOKEN) as
+ * kk_align_viterbi.  codes: state j of token p at frame t of utterance b in word coff[b] + (t S + j) ceil(P / 16) + p / 16, bits as
+ * above; coff counts T S ceil(P / 16) words per utterance.  With S = 1 every output is kk_align_viterbi's, bit for bit */
+int kk_align_max_states(void);
+int kk_align_viterbi_states(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff,
+                            const int *poff, const int64_t *coff, int B, int threads, int states, float *score, int *end,
+                            uint32_t *codes, void *stream);
+/* one wave per utterance walks (p, j) from (end[b], S-1) back to frame 0: state_durations [P_total][S], durations [P_total] (their
+ * row sums) and label [T_total], the CLASS ids[p] S + j of every frame; an infeasible utterance gets zeros and labels -1 */
+int kk_align_backtrack_states(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids,
+                              const int *end, int B, int states, int *state_durations, int *durations, int *label, void *stream);
 /* per class v < V over the frames with label[t] == v: count [V], sum [V][D] and sumsq [V][D] of feat [D][T_total] in fp64, by
  * fixed-order partial sums and a fixed tree (no atomics: two runs give the same bits) */
 int kk_align_accumulate(const float *feat, const int *label, int64_t T_total, int D, int V, int64_t *count, double *sum,

@@ -1,7 +1,7 @@
 """`kokoro-align`: phoneme durations for a feature cache by flat-start forced alignment on the device (no external aligner).
 
     kokoro-align --cache-dir DIR [--iters N] [--optional-id ID ...] [--batch-size N] [--var-floor F] [--mcep K] [--n-classes V]
-                 [--model-in FILE | --model-out FILE] [--output FILE.jsonl] [--write-cache] [--scores [--worst N]]
+                 [--model-in FILE | --model-out FILE] [--output FILE.jsonl] [--write-cache] [--scores [--worst N]] [--states S]
 
 Reads the schema-v7 entries of a feature cache (mel_spec, phoneme_indices), fits one diagonal Gaussian per phoneme id by Viterbi
 training from the even split (kokoro_ruslan_amd.align.PhoneAligner.fit) -- or, with --model-in, loads a fitted model and only aligns --
@@ -16,6 +16,12 @@ log posterior of the forced phoneme; phone_acc, the share of frames whose best p
 the worst token and where it is.  The five fields join every --output line (null for an utterance that was not aligned) and the
 --worst N (default 10) utterances by gop are printed, lowest first: where a transcript does not match its audio, the scores fall.  They
 rank; no threshold says "wrong".
+--states S (1, 2 or 3; default 1) gives every phoneme a left-to-right chain of S states with a Gaussian each: a phone is a closure and
+a burst, an onset and an offset, and a token that has frames then has at least S of them (at a 11.6 ms hop S = 3 means >= 35 ms per
+phone, which is why 1 stays the default; a present optional silence needs >= S frames too, so a shorter pause falls to its
+neighbours).  With --model-in the file's value holds (a conflicting --states is named, exit status 1).  With S > 1 the --output lines
+gain "state_durations" ([P][S], rows summing to phoneme_durations; null where the utterance was not aligned); --write-cache writes the
+phone durations.
 """
 from __future__ import annotations
 
@@ -47,6 +53,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--scores", action="store_true", default=argparse.SUPPRESS,
                    help="score every utterance against its transcript: gop, logpost, phone_acc, gop_min, gop_min_token")
     p.add_argument("--worst", type=int, default=argparse.SUPPRESS, metavar="N", help="with --scores: print the N utterances of lowest gop (default 10)")
+    p.add_argument("--states", type=int, default=argparse.SUPPRESS, metavar="S",
+                   help="states per phoneme, 1..3 (default 1; with --model-in the file's value)")
     return p
 
 
@@ -67,6 +75,10 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--worst needs --scores")
     if getattr(args, "worst", 10) < 0:
         p.error("--worst must be >= 0")
+    if not (1 <= getattr(args, "states", 1) <= 3):
+        p.error("--states must be 1, 2 or 3")
+    if args.n_classes * getattr(args, "states", 1) > 256:
+        p.error(f"--n-classes {args.n_classes} x --states {args.states} = {args.n_classes * args.states} Gaussians; at most 256")
 
 
 def read_cache(cache_dir: str) -> List[Dict]:
@@ -100,8 +112,17 @@ def main(argv=None) -> int:
     import torch
     from kokoro_ruslan_amd import align as A
 
+    S = getattr(args, "states", 1)
+    if args.model_in:
+        S = A.PhoneAligner.file_states(args.model_in)
+        if getattr(args, "states", S) != S:
+            print(f"kokoro-align: --states {args.states}, but {args.model_in} is a model of states = {S}: leave --states out, or fit another "
+                  "model", file=sys.stderr)
+            return 1
+        if args.n_classes * S > 256:
+            p.error(f"{args.model_in}: states = {S}; --n-classes {args.n_classes} x {S} Gaussians are more than 256")
     entries = read_cache(args.cache_dir)
-    al = A.PhoneAligner(K=args.mcep, n_classes=args.n_classes, var_floor=args.var_floor)
+    al = A.PhoneAligner(K=args.mcep, n_classes=args.n_classes, var_floor=args.var_floor, **({"states": S} if S > 1 else {}))
     limit = A.max_tokens()
     failed = 0
     todo = []
@@ -127,10 +148,11 @@ def main(argv=None) -> int:
         model = al.load(args.model_in)
         recs = batches(al.score if want_scores else al.align)
         durs, how = [r["durations"] for r in recs], f"model {args.model_in}"
+        sdurs = [r["state_durations"] for r in recs] if S > 1 else None
         score = sum(r["score"] for r in recs if r["feasible"])
     else:
         model, durs, scores = al.fit(mels, ids, args.optional_id, iters=args.iters, batch_size=args.batch_size)
-        how, score = f"{len(scores)} passes", scores[-1]
+        how, score, sdurs = f"{len(scores)} passes", scores[-1], al.state_durations
         if args.model_out:
             al.save(model, args.model_out)
         recs = batches(al.score) if want_scores else None
@@ -138,22 +160,32 @@ def main(argv=None) -> int:
         for n, r in zip(todo, recs):
             entries[n]["scores"] = {k: r[k] for k in SCORE_FIELDS}
     aligned = 0
-    for n, d in zip(todo, durs):
+    optional = torch.tensor(sorted(set(args.optional_id)), dtype=torch.int64)
+    for k, (n, d) in enumerate(zip(todo, durs)):
         e = entries[n]
         if d is None:
             failed += 1
+            need = S * int((~torch.isin(e["ids"], optional)).sum())
+            if S > 1 and need > e["mel"].shape[0]:
+                print(f"kokoro-align: {e['name']}: {e['ids'].shape[0]} tokens of {S} states need at least {need} frames and cannot be laid "
+                      f"on {e['mel'].shape[0]}; its durations stay (a lower --states would need fewer)", file=sys.stderr)
+                continue
             print(f"kokoro-align: {e['name']}: {e['ids'].shape[0]} tokens cannot be laid on {e['mel'].shape[0]} frames; its durations stay",
                   file=sys.stderr)
             continue
         aligned += 1
         e["durations"] = d
+        if S > 1:
+            e["state_durations"] = sdurs[k]
         if args.write_cache:
             replace_durations(e["path"], d)
     if args.output:
         with open(args.output, "w") as f:
             for e in entries:
                 f.write(json.dumps({"name": e["name"], "phoneme_durations": [int(v) for v in e["durations"]],
-                                    **(e.get("scores", dict.fromkeys(SCORE_FIELDS)) if want_scores else {})}) + "\n")
+                                    **(e.get("scores", dict.fromkeys(SCORE_FIELDS)) if want_scores else {}),
+                                    **({"state_durations": e["state_durations"].tolist() if "state_durations" in e else None}
+                                       if S > 1 else {})}) + "\n")
     frames = sum(int(entries[n]["mel"].shape[0]) for n, d in zip(todo, durs) if d is not None)
     print(f"kokoro-align: {aligned} aligned, {failed} infeasible ({len(entries)} utterances), {how}, "
           f"log-likelihood per frame {score / max(frames, 1):.4f}" + (" -> " + args.cache_dir if args.write_cache else ""))

@@ -6,6 +6,9 @@ Viterbi training: align every utterance with the current Gaussians, re-estimate 
 does that over a corpus held as lists, `align` aligns with a given model; an utterance's result is, bit for bit, what it gives alone.
 `score` aligns and says how well the frames fit the phonemes they were aligned to (goodness of pronunciation, log posterior, frame
 accuracy, per token and per utterance).  align_torch is the fp64 oracle of every step.
+
+`PhoneAligner(states=S)`, S = 2 or 3, gives every phoneme a left-to-right chain of S states, each with its own Gaussian (class v S + j):
+a token that has frames has at least S, one per state.  Everything follows the aligner's `states`; 1 is the default and changes nothing.
 """
 from __future__ import annotations
 
@@ -15,13 +18,14 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import torch
 
 from kokoro_ruslan_amd import lib as kk
-from kokoro_ruslan_amd.align_torch import VAR_MIN, even_split
+from kokoro_ruslan_amd.align_torch import VAR_MIN, even_split, split_states
 from kokoro_ruslan_amd.dtw_torch import dct_table
 
 MAX_FRAMES = 4096                        # the longest utterance the kernels take (the positional table's order)
 MAX_MEL = 128                            # kk_mcep stages 64 frames of at most this many channels
 MAX_CLASSES = 256                        # kk_align_loglik
 MAX_DIM = 64
+MAX_STATES = 3                           # kk_align_viterbi_states
 
 
 def max_tokens() -> int:
@@ -29,27 +33,38 @@ def max_tokens() -> int:
     return int(kk.load().kk_align_max_tokens())
 
 
-def code_words(P: int, T: int) -> int:
-    """32-bit code words of a P-token, T-frame utterance: 16 tokens of a frame per word."""
-    return T * ((P + 15) // 16)
+def code_words(P: int, T: int, S: int = 1) -> int:
+    """32-bit code words of a P-token, T-frame utterance with S states per token: 16 tokens of a (frame, state) per word, [T][S][W]."""
+    return T * S * ((P + 15) // 16)
 
 
 class PhoneAligner:
     """Batched Viterbi alignment and Viterbi training on the MI355X."""
 
-    def __init__(self, device: str = "cuda", K: int = 13, n_classes: int = 59, var_floor: float = 0.01):
+    def __init__(self, device: str = "cuda", K: int = 13, n_classes: int = 59, var_floor: float = 0.01, states: int = 1):
         if int(K) != K or not (0 <= K <= MAX_DIM // 2 - 1):
             raise ValueError(f"K must be an integer in 0..{MAX_DIM // 2 - 1}, not {K!r}")
         if int(n_classes) != n_classes or not (1 <= n_classes <= MAX_CLASSES):
             raise ValueError(f"n_classes must be an integer in 1..{MAX_CLASSES}, not {n_classes!r}")
         if not (0.0 <= var_floor < 1.0):
             raise ValueError(f"var_floor must be in [0, 1), not {var_floor!r}")
+        if int(states) != states or not (1 <= states <= MAX_STATES):
+            raise ValueError(f"states must be an integer in 1..{MAX_STATES}, not {states!r}")
+        if n_classes * states > MAX_CLASSES:
+            raise ValueError(f"{n_classes} phoneme ids of {states} states are {n_classes * states} classes; at most {MAX_CLASSES}")
         self.device, self.K, self.n_classes, self.var_floor = torch.device(device), int(K), int(n_classes), float(var_floor)
+        self.states = int(states)
+        self.state_durations: Optional[List[Optional[torch.Tensor]]] = None      # of the last fit(), when states > 1
         self._tables: Dict[int, torch.Tensor] = {}
 
     @property
     def dim(self) -> int:
         return 2 * (self.K + 1)
+
+    @property
+    def classes(self) -> int:
+        """Gaussians of the model: `states` per phoneme id, class v states + j."""
+        return self.n_classes * self.states
 
     # ---- guards: everything is checked before anything is launched --------------------------------------------------------------
     def _check(self, mels, ids, feats) -> None:
@@ -82,9 +97,11 @@ class PhoneAligner:
                 raise ValueError(f"utterance {i}: phoneme ids must lie in 0..{self.n_classes - 1}")
 
     def _check_model(self, model: Dict, D: int) -> None:
+        if int(model.get("states", 1)) != self.states:
+            raise ValueError(f"the model has states = {int(model.get('states', 1))}; this aligner has states = {self.states}")
         for k in ("mean", "var"):
-            if tuple(model[k].shape) != (self.n_classes, D):
-                raise ValueError(f"the model's {k} is {tuple(model[k].shape)}; this aligner and these features need ({self.n_classes}, {D})")
+            if tuple(model[k].shape) != (self.classes, D):
+                raise ValueError(f"the model's {k} is {tuple(model[k].shape)}; this aligner and these features need ({self.classes}, {D})")
 
     # ---- pieces ------------------------------------------------------------------------------------------------------------------
     def table(self, M: int) -> torch.Tensor:
@@ -120,14 +137,14 @@ class PhoneAligner:
         D, T = feat.shape
         self._check_model(model, D)
         a, mu, c = self.params(model)
-        L = torch.empty(self.n_classes, T, dtype=torch.float32, device=self.device)
-        kk.call("kk_align_loglik", feat, T, D, self.n_classes, a, mu, c, L)
+        L = torch.empty(self.classes, T, dtype=torch.float32, device=self.device)
+        kk.call("kk_align_loglik", feat, T, D, self.classes, a, mu, c, L)
         return L
 
     def accumulate(self, feat: torch.Tensor, label: torch.Tensor):
         """(count int64 [V], sum x fp64 [V, D], sum x^2 fp64 [V, D]) of packed features [D, T_total] under frame labels int32 [T_total]."""
         D, T = feat.shape
-        V = self.n_classes
+        V = self.classes
         count = torch.empty(V, dtype=torch.int64, device=self.device)
         sums = torch.empty(2, V, D, dtype=torch.float64, device=self.device)
         kk.call("kk_align_accumulate", feat, label, T, D, V, count, sums[0], sums[1])
@@ -145,14 +162,20 @@ class PhoneAligner:
         few = (n < 2)[:, None]
         mean, var = torch.where(few, gmean, mean), torch.where(few, gvar, var)
         var = torch.maximum(torch.maximum(var, self.var_floor * gvar), torch.full_like(var, VAR_MIN))
-        return {"mean": mean, "var": var, "K": self.K, "n_classes": self.n_classes}
+        return self._tag({"mean": mean, "var": var, "K": self.K, "n_classes": self.n_classes})
+
+    def _tag(self, model: Dict) -> Dict:
+        """A multi-state model says so; a 1-state model stays the dictionary it always was."""
+        if self.states > 1:
+            model["states"] = self.states
+        return model
 
     # ---- one batch on the device -------------------------------------------------------------------------------------------------
     def _pack(self, mels, ids, optional_ids: Iterable[int], feats) -> Dict:
         dev = self.device
         x = mels if feats is None else feats
         nt, np_ = [int(m.shape[0]) for m in x], [int(t.shape[0]) for t in ids]
-        coff_h = kk.packed_offsets([code_words(p, t) for p, t in zip(np_, nt)])
+        coff_h = kk.packed_offsets([code_words(p, t, self.states) for p, t in zip(np_, nt)])
         tok_h = torch.cat([t.to("cpu", torch.int64) for t in ids])
         opt_h = torch.isin(tok_h, torch.tensor(sorted(set(int(o) for o in optional_ids)), dtype=torch.int64))
         pk = {"B": len(ids), "frames": nt, "tokens": np_,
@@ -172,19 +195,31 @@ class PhoneAligner:
         codes = torch.empty(pk["coff_host"][-1], dtype=torch.int32, device=dev)
         durations = torch.empty(pk["poff_host"][-1], dtype=torch.int32, device=dev)
         label = torch.empty(pk["foff_host"][-1], dtype=torch.int32, device=dev)
-        kk.call("kk_align_viterbi", L, L.shape[1], pk["ids"], pk["opt"], pk["foff"], pk["poff"], pk["coff"], B, pk["threads"], score, end,
-                codes)
-        kk.call("kk_align_backtrack", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, durations, label)
-        return {"feat": pk["feat"], "L": L, "score": score, "end": end, "codes": codes, "durations": durations, "label": label,
-                "foff_host": pk["foff_host"], "poff_host": pk["poff_host"], "coff_host": pk["coff_host"],
-                "ids": pk["ids"], "foff": pk["foff"], "poff": pk["poff"]}
+        run = {"feat": pk["feat"], "L": L, "score": score, "end": end, "codes": codes, "durations": durations, "label": label,
+               "foff_host": pk["foff_host"], "poff_host": pk["poff_host"], "coff_host": pk["coff_host"],
+               "ids": pk["ids"], "foff": pk["foff"], "poff": pk["poff"]}
+        if self.states == 1:
+            kk.call("kk_align_viterbi", L, L.shape[1], pk["ids"], pk["opt"], pk["foff"], pk["poff"], pk["coff"], B, pk["threads"], score,
+                    end, codes)
+            kk.call("kk_align_backtrack", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, durations, label)
+            return run
+        S = self.states
+        sdur = torch.empty(pk["poff_host"][-1], S, dtype=torch.int32, device=dev)
+        kk.call("kk_align_viterbi_states", L, L.shape[1], pk["ids"], pk["opt"], pk["foff"], pk["poff"], pk["coff"], B, pk["threads"], S,
+                score, end, codes)
+        kk.call("kk_align_backtrack_states", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, S, sdur, durations, label)
+        # label is the class v S + j of every frame (what accumulate takes); the scores take the phoneme: label // S, -1 staying -1
+        run.update(states=S, state_durations=sdur, phone_label=torch.div(label, S, rounding_mode="floor"))
+        return run
 
     def run_packed(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (),
                    model: Optional[Dict] = None, feats: Optional[Sequence[torch.Tensor]] = None) -> Dict:
         """One batch on the device, nothing read back: the features [D, T_total], L [V, T_total], score fp32 [B], end int32 [B] (the
         end state, -1 when infeasible), the code words, durations int32 [P_total], label int32 [T_total] and the host lists foff_host /
         poff_host / coff_host (first frame / token / code word of each utterance), with the packed ids and the offsets foff / poff
-        (int32) as the kernels took them.  feats: features [T, D] per utterance instead of mels (then mels is None)."""
+        (int32) as the kernels took them.  feats: features [T, D] per utterance instead of mels (then mels is None).  With states = S
+        > 1: L is [V S, T_total], end the end TOKEN, label the class v S + j of every frame, and the result also has "states",
+        state_durations int32 [P_total, S] (durations are their row sums) and phone_label = label // S."""
         if model is None:
             raise ValueError("run_packed needs a model: fit one, or load one")
         self._check(mels, ids, feats)
@@ -193,26 +228,43 @@ class PhoneAligner:
 
     @staticmethod
     def _records(run: Dict) -> List[Dict]:
-        score, dur, poff = run["score"].cpu().tolist(), run["durations"].cpu().to(torch.int64), run["poff_host"]
+        score, poff, sdur = run["score"].cpu().tolist(), run["poff_host"], None
+        if "state_durations" in run:                                             # the phone durations are the row sums: not read
+            sdur = run["state_durations"].cpu().to(torch.int64)
+            dur = sdur.sum(1)
+        else:
+            dur = run["durations"].cpu().to(torch.int64)
         out = []
         for n, s in enumerate(score):
             ok = s > -math.inf
             out.append({"durations": dur[poff[n]:poff[n + 1]].clone() if ok else None, "score": s, "feasible": ok})
+            if sdur is not None:
+                out[-1]["state_durations"] = sdur[poff[n]:poff[n + 1]].clone() if ok else None
         return out
 
     def align(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (),
               model: Optional[Dict] = None, feats: Optional[Sequence[torch.Tensor]] = None) -> List[Dict]:
         """mels: log-mels [T, M], ids: integer tokens [P], utterance i = (mels[i], ids[i]); optional_ids: the phoneme ids whose tokens
         may get no frame.  Returns per utterance {"durations": LongTensor [P] summing to T (0 for a skipped token) | None, "score":
-        the log-likelihood of the best path, "feasible": whether a path exists}.  One read by the host."""
+        the log-likelihood of the best path, "feasible": whether a path exists}, and with states = S > 1 "state_durations": LongTensor
+        [P, S] whose rows sum to the durations (every state of a token that has frames has at least one) | None.  One read of the
+        scores and one of the durations by the host."""
         return self._records(self.run_packed(mels, ids, optional_ids, model, feats))
 
     # ---- pronunciation scores ------------------------------------------------------------------------------------------------------
     def score_packed(self, run: Dict) -> Dict:
         """The pronunciation scores (align_torch.scores) of a run_packed() result, on the device, nothing read back: per token
         gop_sum, lpost_sum (fp64 [P_total]) and hits (int32 [P_total]); per utterance utt_gop, utt_lpost (fp64 [B]) and utt_hits (int32
-        [B]); per frame the scratch margin, lpost (fp64 [T_total]) and amax (int32 [T_total]).  Zeros for an infeasible utterance."""
+        [B]); per frame the scratch margin, lpost (fp64 [T_total]) and amax (int32 [T_total]).  Zeros for an infeasible utterance.
+        A run of S > 1 states is scored on the phonemes: L is the maximum over each phoneme's states (exact; "phone_L" [V, T_total] in
+        the result), the labels are phone_label: another state of the same phoneme winning a frame is no pronunciation error."""
         L, foff, poff = run["L"], run["foff_host"], run["poff_host"]
+        S, label = int(run.get("states", 1)), run["label"]
+        if S > 1:
+            if L.dim() != 2 or L.shape[0] % S:
+                raise ValueError(f"L {tuple(L.shape)} does not hold {S} states per phoneme")
+            L, label = L.view(L.shape[0] // S, S, L.shape[1]).amax(1).contiguous(), run["phone_label"].contiguous()
+            run = dict(run, L=L, label=label)
         if L.dim() != 2 or L.dtype != torch.float32 or not (1 <= L.shape[0] <= MAX_CLASSES):
             raise ValueError(f"L must be fp32 [V <= {MAX_CLASSES}, frames], not {L.dtype} {tuple(L.shape)}")
         B, T_total, P_total = len(foff) - 1, int(L.shape[1]), int(run["ids"].shape[0])
@@ -238,6 +290,8 @@ class PhoneAligner:
                "hits": torch.empty(P_total, dtype=torch.int32, device=dev),
                "utt_gop": torch.empty(B, dtype=torch.float64, device=dev), "utt_lpost": torch.empty(B, dtype=torch.float64, device=dev),
                "utt_hits": torch.empty(B, dtype=torch.int32, device=dev)}
+        if S > 1:
+            out["phone_L"] = L
         kk.call("kk_align_scores", L, T_total, L.shape[0], run["label"], run["durations"], run["ids"], run["foff"], run["poff"], B,
                 out["margin"], out["lpost"], out["amax"], out["gop_sum"], out["lpost_sum"], out["hits"], out["utt_gop"], out["utt_lpost"],
                 out["utt_hits"])
@@ -250,17 +304,23 @@ class PhoneAligner:
         of pronunciation), "logpost": the mean log posterior of the forced phone under a flat prior, "phone_acc": the share of frames
         whose best phone is the forced one; "gop_min", "gop_min_token": the lowest token mean of gop and its index (tokens without frames
         are ignored, the first of equal minima wins); "tokens": {"frames", "hits" int64 [P], "gop", "logpost" fp64 [P], NaN where a
-        token has no frames}}.  An infeasible utterance has None in every field but score and feasible.  One read by the host."""
+        token has no frames}}; with states = S > 1 also "state_durations" [P, S].  An infeasible utterance has None in every field but
+        score and feasible.  One read by the host."""
         run = self.run_packed(mels, ids, optional_ids, model, feats)
         sc = self.score_packed(run)
         parts = [run["score"], run["durations"], sc["gop_sum"], sc["lpost_sum"], sc["hits"], sc["utt_gop"], sc["utt_lpost"], sc["utt_hits"]]
+        if "state_durations" in run:
+            parts.append(run["state_durations"].reshape(-1))
         host = torch.cat([p.to(torch.float64) for p in parts]).cpu()              # (fp32 and int32 are exact in fp64) the one read
-        score, dur, gsum, lsum, hits, ug, ul, uh = host.split([int(p.shape[0]) for p in parts])
+        score, dur, gsum, lsum, hits, ug, ul, uh, *rest = host.split([int(p.shape[0]) for p in parts])
+        sdur = rest[0].to(torch.int64).view(-1, run["states"]) if rest else None
         poff, foff, out = run["poff_host"], run["foff_host"], []
         for n, s in enumerate(score.tolist()):
             rec = {"score": s, "feasible": s > -math.inf}
             if not rec["feasible"]:
                 rec.update(dict.fromkeys(("durations", "gop", "logpost", "phone_acc", "gop_min", "gop_min_token", "tokens")))
+                if sdur is not None:
+                    rec["state_durations"] = None
                 out.append(rec)
                 continue
             sl, T = slice(poff[n], poff[n + 1]), foff[n + 1] - foff[n]
@@ -272,6 +332,8 @@ class PhoneAligner:
             at = int((low == low.min()).nonzero()[0])                                # (the first of equal minima)
             rec.update(durations=frames.clone(), gop=float(ug[n]) / T, logpost=float(ul[n]) / T, phone_acc=float(uh[n]) / T,
                        gop_min=float(low[at]), gop_min_token=at, tokens=tok)
+            if sdur is not None:
+                rec["state_durations"] = sdur[sl].clone()
             out.append(rec)
         return out
 
@@ -279,7 +341,9 @@ class PhoneAligner:
             batch_size: int = 64, feats: Optional[Sequence[torch.Tensor]] = None):
         """Viterbi training from the even split: `iters` passes of estimate -> align over the corpus in batches of batch_size, the
         class statistics accumulated batch by batch in that order; stops once no duration changes.  Returns (model, durations: list of
-        LongTensor [P] | None, scores: the corpus score of each pass)."""
+        LongTensor [P] | None, scores: the corpus score of each pass).  With states = S > 1 the flat start spreads every token's frames
+        of the even split evenly over its S states (align_torch.split_states), the passes stop once no STATE duration changes, and the
+        state durations of the last pass are in `self.state_durations` (list of LongTensor [P, S] | None)."""
         if int(iters) != iters or iters < 1:
             raise ValueError(f"iters must be an integer >= 1, not {iters!r}")
         if int(batch_size) != batch_size or batch_size < 1:
@@ -294,9 +358,16 @@ class PhoneAligner:
         labels, n = [], 0
         for pk in packs:
             d = torch.cat(flat[n:n + pk["B"]])
-            labels.append(torch.repeat_interleave(pk["ids_host"], d).to(torch.int32).to(self.device))
+            if self.states == 1:
+                labels.append(torch.repeat_interleave(pk["ids_host"], d).to(torch.int32).to(self.device))
+            else:
+                S = self.states
+                cls = (pk["ids_host"][:, None] * S + torch.arange(S)[None, :]).reshape(-1)
+                labels.append(torch.repeat_interleave(cls, torch.from_numpy(split_states(d.numpy(), S)).reshape(-1)).to(torch.int32).to(self.device))
             n += pk["B"]
-        durs: List[Optional[torch.Tensor]] = list(flat)
+        key = "durations" if self.states == 1 else "state_durations"          # what has to stop changing
+        durs: List[Optional[torch.Tensor]] = list(flat) if self.states == 1 else [torch.from_numpy(split_states(d.numpy(), self.states)) for d in flat]
+        phone: List[Optional[torch.Tensor]] = list(flat)
         model, scores = None, []
         for _ in range(int(iters)):
             stats = None
@@ -304,28 +375,43 @@ class PhoneAligner:
                 part = self.accumulate(pk["feat"], lab)
                 stats = part if stats is None else tuple(a + b for a, b in zip(stats, part))
             model = self.estimate(*stats)
-            new, labels, total = [], [], 0.0
+            new, phone, labels, total = [], [], [], 0.0
             for pk in packs:
                 run = self._align_packed(pk, model)
                 labels.append(run["label"])
                 for r in self._records(run):
-                    new.append(r["durations"])
+                    new.append(r[key])
+                    phone.append(r["durations"])
                     total += r["score"] if r["feasible"] else 0.0
             scores.append(total)
             same = all((d is None and e is None) or (d is not None and e is not None and torch.equal(d, e)) for d, e in zip(durs, new))
             durs = new
             if same:
                 break
-        return model, durs, scores
+        self.state_durations = durs if self.states > 1 else None
+        return model, phone, scores
 
     # ---- the model on disk -------------------------------------------------------------------------------------------------------
     def save(self, model: Dict, path: str) -> None:
-        torch.save({"mean": model["mean"].detach().to("cpu", torch.float64), "var": model["var"].detach().to("cpu", torch.float64),
-                    "K": self.K, "n_classes": self.n_classes}, path)
+        """A multi-state model's file also has "states"; a 1-state model's file stays what it was (a file without the field is S = 1)."""
+        if int(model.get("states", 1)) != self.states:
+            raise ValueError(f"the model has states = {int(model.get('states', 1))}; this aligner has states = {self.states}")
+        torch.save(self._tag({"mean": model["mean"].detach().to("cpu", torch.float64), "var": model["var"].detach().to("cpu", torch.float64),
+                              "K": self.K, "n_classes": self.n_classes}), path)
+
+    @staticmethod
+    def file_states(path: str) -> int:
+        """The states per phoneme of a saved model: 1 for a file without the field."""
+        return int(torch.load(path, map_location="cpu", weights_only=True).get("states", 1))
 
     def load(self, path: str) -> Dict:
         m = torch.load(path, map_location="cpu", weights_only=True)
         if int(m["K"]) != self.K or int(m["n_classes"]) != self.n_classes:
             raise ValueError(f"{path}: a model of K = {int(m['K'])}, {int(m['n_classes'])} classes; this aligner has K = {self.K}, "
                              f"{self.n_classes} classes")
-        return {"mean": m["mean"].to(self.device), "var": m["var"].to(self.device), "K": self.K, "n_classes": self.n_classes}
+        S = int(m.get("states", 1))
+        if S != self.states:
+            raise ValueError(f"{path}: a model of states = {S}; this aligner has states = {self.states}")
+        if tuple(m["mean"].shape[:1]) != (self.classes,) or tuple(m["var"].shape[:1]) != (self.classes,):
+            raise ValueError(f"{path}: a model of {int(m['mean'].shape[0])} Gaussians; {self.n_classes} classes of {S} states need {self.classes}")
+        return self._tag({"mean": m["mean"].to(self.device), "var": m["var"].to(self.device), "K": self.K, "n_classes": self.n_classes})

@@ -251,3 +251,144 @@ def frame_accuracy(ids: Sequence, durations: Sequence, truth: Sequence) -> float
         if d is not None:
             good += int((np.repeat(i, d) == want).sum())
     return good / max(total, 1)
+
+
+# ---- multi-state phone models: a left-to-right chain of S states per phoneme (DESIGN §5 "Forced alignment", "States") -----------------
+# The classes are c = v S + j, j = 0..S-1; a model is {"mean", "var"} [V S, D] plus "states": S, and L is [V S, T].  loglik_params,
+# loglik_from_params, accumulate and model_from_stats above take V S as their class count.
+
+def viterbi_states(L, ids, S: int, optional=None):
+    """L [V S, T], ids [P].  State (p, j) of token p scores
+        Sigma(p, j, t) = L(ids[p] S + j, t) + max of, in this order, a later candidate only when strictly greater:
+            code 0 stay     Sigma(p, j, t-1)
+            code 1 advance  Sigma(p, j-1, t-1) if j > 0, else Sigma(p-1, S-1, t-1)
+            code 2 skip     Sigma(p-2, S-1, t-1), only for j = 0 and optional[p-1].
+    Start: (0, 0) and, if optional[0], (1, 0).  End: (P-1, S-1), or (P-2, S-1) when optional[P-1] and that cell is strictly greater.
+    A skipped token loses all its states; a present one has >= 1 frame in each.  Returns (state durations int64 [P, S], phone durations
+    int64 [P] = their row sums, score), or (None, None, -inf) when no path exists.  With S = 1 this is `viterbi`, operation by operation."""
+    L, ids = _f64(L), np.asarray(ids, dtype=np.int64)
+    if int(S) != S or S < 1:
+        raise ValueError(f"states must be an integer >= 1, not {S!r}")
+    S = int(S)
+    P, T = ids.shape[0], L.shape[1]
+    if P < 1 or T < 1:
+        raise ValueError("viterbi_states needs at least one token and one frame")
+    if L.shape[0] % S or (ids < 0).any() or (ids >= L.shape[0] // S).any():
+        raise ValueError(f"L has {L.shape[0]} classes: not {S} states each of the ids given")
+    opt = np.zeros(P, dtype=bool) if optional is None else np.asarray(optional, dtype=bool)
+    if opt.shape != (P,):
+        raise ValueError(f"{opt.shape[0]} optional flags for {P} tokens")
+    ninf = -np.inf
+    Lp = L[ids[:, None] * S + np.arange(S)[None, :]]                            # [P, S, T]
+    may_skip = np.concatenate([[False], opt[:-1]])
+    sig = np.full((P, S), ninf)
+    sig[0, 0] = Lp[0, 0, 0]
+    if P > 1 and opt[0]:
+        sig[1, 0] = Lp[1, 0, 0]
+    code = np.zeros((T, P, S), dtype=np.int8)
+    for t in range(1, T):
+        best, c = sig.copy(), np.zeros((P, S), dtype=np.int8)
+        adv = np.empty((P, S))
+        adv[:, 1:], adv[0, 0], adv[1:, 0] = sig[:, :-1], ninf, sig[:-1, S - 1]
+        take = adv > best
+        best, c = np.where(take, adv, best), np.where(take, np.int8(1), c)
+        skip = np.full((P, S), ninf)
+        skip[:, 0] = np.where(may_skip, np.concatenate([[ninf, ninf], sig[:-2, S - 1]])[:P], ninf)
+        take = skip > best
+        best, c = np.where(take, skip, best), np.where(take, np.int8(2), c)
+        sig, code[t] = Lp[:, :, t] + best, c
+    p, j = P - 1, S - 1
+    if P > 1 and opt[P - 1] and sig[P - 2, j] > sig[P - 1, j]:
+        p = P - 2
+    score = float(sig[p, j])
+    if not np.isfinite(score):
+        return None, None, ninf
+    sd = np.zeros((P, S), dtype=np.int64)
+    for t in range(T - 1, -1, -1):
+        sd[p, j] += 1
+        if t:
+            c = int(code[t, p, j])
+            if c == 1 and j > 0:
+                j -= 1
+            elif c:
+                p, j = p - c, S - 1
+    return sd, sd.sum(1), score
+
+
+def state_labels(ids, state_durations, S: int) -> np.ndarray:
+    """The class ids[p] S + j of every frame under state durations [P, S]."""
+    cls = np.asarray(ids, dtype=np.int64)[:, None] * int(S) + np.arange(int(S))[None, :]
+    return np.repeat(cls.ravel(), np.asarray(state_durations, dtype=np.int64).reshape(-1))
+
+
+def path_score_states(L, ids, state_durations, S: int) -> float:
+    """The fp64 score of a given state alignment: sum over the frames of L(class of the frame's state, frame)."""
+    L, lab = _f64(L), state_labels(ids, state_durations, S)
+    return float(L[lab, np.arange(L.shape[1])].sum())
+
+
+def split_states(durations, S: int) -> np.ndarray:
+    """[P, S]: each token's d frames spread over its S states as even_split(S, d) spreads them (a state may get none)."""
+    d = np.asarray(durations, dtype=np.int64).reshape(-1)
+    return np.stack([even_split(int(S), int(x)) for x in d]) if d.shape[0] else np.zeros((0, int(S)), dtype=np.int64)
+
+
+def phone_max(L, S: int) -> np.ndarray:
+    """[V S, T] -> [V, T]: a frame's phone likelihood is that of the phone's best state (exact: a maximum does not round)."""
+    L = _f64(L)
+    return L.reshape(L.shape[0] // int(S), int(S), L.shape[1]).max(1)
+
+
+def fit_states(feats: Sequence, ids: Sequence, optional: Optional[Sequence] = None, V: int = 59, S: int = 2, iters: int = 6,
+               var_floor: float = 0.01, models: Optional[List] = None):
+    """`fit` with S states per phoneme.  Pass 0's labels come from even_split(P, T) per utterance, then split_states; then estimate ->
+    viterbi_states, stopping once no state duration changes.  Returns (model with "states", state durations: list of int64 [P, S] |
+    None, scores).  The phone durations are the row sums."""
+    ids = [np.asarray(i, dtype=np.int64) for i in ids]
+    optional = [None] * len(ids) if optional is None else list(optional)
+    durs: List[Optional[np.ndarray]] = [split_states(even_split(len(i), _f64(x).shape[0]), S) for x, i in zip(feats, ids)]
+    model, scores = None, []
+    for _ in range(iters):
+        labels = [state_labels(i, d, S) if d is not None else np.full(_f64(x).shape[0], -1) for x, i, d in zip(feats, ids, durs)]
+        model = dict(model_from_stats(*accumulate(feats, labels, V * S), var_floor=var_floor), states=int(S))
+        if models is not None:
+            models.append(model)
+        a, mu, c = loglik_params(model)
+        new, total = [], 0.0
+        for x, i, o in zip(feats, ids, optional):
+            d, _, s = viterbi_states(loglik_from_params(x, a, mu, c), i, S, o)
+            new.append(d)
+            total += s if d is not None else 0.0
+        scores.append(total)
+        same = all((d is None and e is None) or (d is not None and e is not None and np.array_equal(d, e)) for d, e in zip(durs, new))
+        durs = new
+        if same:
+            break
+    return model, durs, scores
+
+
+def synthetic_corpus_parts(seed: int, parts: int = 2, optional: bool = False, n_utts: int = 40, V: int = 12, D: int = 8,
+                           mean_std: float = 2.0, noise: float = 0.5, max_frames: int = 12):
+    """synthetic_corpus with phones that are not stationary: every class has `parts` sub-means drawn independently, N(0, mean_std^2)
+    per dimension, and a token of d frames is split_states(d, parts) stretches of them in order (every present token has parts..
+    max_frames frames, so each stretch has at least one).  Returns (feats, ids, optional, durations, means [V, parts, D], state
+    durations: list of int64 [P, parts])."""
+    g = np.random.default_rng(seed)
+    means = g.normal(0.0, mean_std, (V, parts, D))
+    feats, ids, opts, durs, sdurs = [], [], [], [], []
+    for _ in range(n_utts):
+        P = int(g.integers(5, 21))
+        i = g.integers(1 if optional else 0, V, P)
+        o = np.zeros(P, dtype=bool)
+        d = g.integers(parts, max_frames + 1, P)
+        if optional:
+            for p in range(1, P - 1):
+                if not o[p - 1] and g.random() < 0.25:
+                    o[p], i[p] = True, 0
+                    if g.random() < 0.5:
+                        d[p] = 0
+        sd = split_states(d, parts)
+        lab = state_labels(i, sd, parts)
+        feats.append((means.reshape(V * parts, D)[lab] + g.normal(0.0, noise, (lab.shape[0], D))).astype(np.float32))
+        ids.append(i.astype(np.int64)), opts.append(o), durs.append(d.astype(np.int64)), sdurs.append(sd)
+    return feats, ids, opts, durs, means, sdurs

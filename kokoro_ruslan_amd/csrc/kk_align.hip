@@ -24,6 +24,8 @@
 //               same bits.
 // Nothing an utterance computes in feats, viterbi or backtrack depends on the other utterances, and a frame's L on that frame alone.
 // kk_align_scores (two more launches, described where they stand) turns L and an alignment into pronunciation scores.
+// kk_align_viterbi_states / kk_align_backtrack_states (described where they stand) are the same two steps for phone models of 2 or 3
+// states per phoneme; feats, loglik, accumulate and scores serve them unchanged, with V S classes.
 #include "kk_common.h"
 
 namespace {
@@ -198,6 +200,129 @@ __global__ __launch_bounds__(64) void align_backtrack_kernel(const uint32_t *__r
     }
     __syncthreads();
     for (int p = lane; p < P; p += 64) durations[p0 + p] = dur[p];
+}
+
+// ---- multi-state phone models: a left-to-right chain of NS states per phoneme (align_torch.viterbi_states) -----------------------------
+// The classes are v NS + j.  Thread p still owns token p and keeps its NS scores in registers; only the LAST state's score goes to
+// LDS, in the same two columns with the same two -inf cells in front, because Sigma(p-1, NS-1) and Sigma(p-2, NS-1) are all a
+// neighbour reads: one barrier per frame, as above.  The states are updated in descending j, so Sigma(p, j-1, t-1) is read before it
+// is overwritten.  Code words as above, one row of ceil(P / 16) words per (frame, state): [T][NS][W].  With NS = 1 every operation, and
+// so every bit written, is align_viterbi_kernel's.
+constexpr int AL_MAXS = 3;                    // states per phoneme
+
+template <int NS>
+__global__ __launch_bounds__(AL_MAXP) void align_viterbi_states_kernel(const VitArgs a) {
+    __shared__ float S[2][AL_MAXP + 2];                               // the last state of token p at [p + 2]; [0] and [1] stay -inf
+    const int b = blockIdx.x, p = threadIdx.x;
+    const int f0 = a.foff[b], T = a.foff[b + 1] - f0, p0 = a.poff[b], P = a.poff[b + 1] - p0;
+    if (P < 1 || P > (int)blockDim.x || T < 1 || T > AL_MAXT) return;  // (the host checks)
+    const bool live = p < P, wave_live = (p & ~63) < P;
+    const int W = (P + 15) >> 4;                                      // code words per (frame, state)
+    uint32_t *codes = a.codes + a.coff[b];
+    const float ninf = -__builtin_inff();
+    const float *Lr = a.L + (int64_t)(live ? a.ids[p0 + p] : 0) * NS * a.T_total + f0;      // state j: Lr + j T_total
+    const bool may_skip = live && p >= 2 && a.opt[p0 + p - 1];
+    const bool starts = p == 0 || (p == 1 && a.opt[p0]);
+    float sc[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) sc[j] = ninf;
+    if (p < 2) S[0][p] = S[1][p] = ninf;
+    __syncthreads();
+    for (int t0 = 0; t0 < T; t0 += AL_PRE) {
+        float l[NS][AL_PRE];
+        if (wave_live) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j)
+#pragma unroll
+                for (int u = 0; u < AL_PRE; ++u) l[j][u] = Lr[(int64_t)j * a.T_total + min(t0 + u, T - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < AL_PRE; ++u) {
+            const int t = t0 + u;
+            if (t >= T) break;
+            if (wave_live) {
+                const float *prev = S[(t & 1) ^ 1];
+                uint32_t code[NS];
+#pragma unroll
+                for (int j = 0; j < NS; ++j) code[j] = 0;
+                if (t == 0) sc[0] = starts ? l[0][u] : ninf;          // (the other states stay -inf)
+                else {
+#pragma unroll
+                    for (int j = NS - 1; j > 0; --j) {                // descending: sc[j - 1] still holds frame t - 1
+                        float best = sc[j];
+                        if (sc[j - 1] > best) best = sc[j - 1], code[j] = 1;
+                        sc[j] = l[j][u] + best;
+                    }
+                    float best = sc[0];
+                    const float adv = prev[p + 1], skip = may_skip ? prev[p] : ninf;
+                    if (adv > best) best = adv, code[0] = 1;
+                    if (skip > best) best = skip, code[0] = 2;
+                    sc[0] = l[0][u] + best;
+                }
+                if (live) S[t & 1][p + 2] = sc[NS - 1];
+#pragma unroll
+                for (int j = 0; j < NS; ++j) {
+                    if (!live) code[j] = 0;
+                    const unsigned long long lo = __ballot(code[j] & 1u), hi = j == 0 ? __ballot(code[j] & 2u) : 0ull;
+                    if (live && (p & 15) == 0) {
+                        const int sh = p & 48;
+                        codes[((int64_t)t * NS + j) * W + (p >> 4)] =
+                            (uint32_t)((lo >> sh) & 0xffffull) | ((uint32_t)((hi >> sh) & 0xffffull) << 16);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (p == 0) {
+        const float *last = S[(T - 1) & 1];
+        int e = P - 1;
+        float s = last[P + 1];
+        if (P > 1 && a.opt[p0 + P - 1] && last[P] > s) e = P - 2, s = last[P];
+        const bool ok = s > ninf;                                     // (false for a NaN too)
+        a.score[b] = ok ? s : ninf;
+        a.end[b] = ok ? e : -1;
+    }
+}
+
+// One wave per utterance: lane 0 walks (p, j) from (end, NS - 1) back to frame 0; code 1 at j > 0 steps to the state before, code 1
+// at j = 0 to the last state of the token before, code 2 to the last state of the token two before.  label is the CLASS ids[p] NS + j.
+__global__ __launch_bounds__(64) void align_backtrack_states_kernel(const uint32_t *__restrict__ codes, const int64_t *__restrict__ coff,
+                                                                    const int *__restrict__ foff, const int *__restrict__ poff,
+                                                                    const int *__restrict__ ids, const int *__restrict__ end, int NS,
+                                                                    int *__restrict__ state_durations, int *__restrict__ durations,
+                                                                    int *__restrict__ label) {
+    __shared__ int dur[AL_MAXP * AL_MAXS];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int f0 = foff[b], T = foff[b + 1] - f0, p0 = poff[b], P = poff[b + 1] - p0;
+    if (P < 1 || P > AL_MAXP || T < 1 || T > AL_MAXT || NS < 1 || NS > AL_MAXS) return;
+    for (int q = lane; q < P * NS; q += 64) dur[q] = 0;
+    __syncthreads();
+    const int e = end[b];
+    if (e < 0 || e >= P) {
+        for (int t = lane; t < T; t += 64) label[f0 + t] = -1;
+    } else if (lane == 0) {
+        const uint32_t *cod = codes + coff[b];
+        const int W = (P + 15) >> 4;
+        int p = e, j = NS - 1;
+        for (int t = T - 1; t >= 0; --t) {
+            ++dur[p * NS + j];
+            label[f0 + t] = ids[p0 + p] * NS + j;
+            if (t) {
+                const uint32_t w = cod[((int64_t)t * NS + j) * W + (p >> 4)] >> (p & 15);
+                const int c = (int)min((w & 1u) | ((w >> 15) & 2u), 2u);
+                if (c == 1 && j > 0) --j;
+                else if (c) p = max(p - c, 0), j = NS - 1;
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = lane; q < P * NS; q += 64) state_durations[(int64_t)p0 * NS + q] = dur[q];
+    for (int q = lane; q < P; q += 64) {
+        int d = 0;
+        for (int j = 0; j < NS; ++j) d += dur[q * NS + j];
+        durations[p0 + q] = d;
+    }
 }
 
 __global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const float *__restrict__ feat, const int *__restrict__ label,
@@ -413,6 +538,37 @@ extern "C" int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, co
     hipLaunchKernelGGL(align_backtrack_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, codes, coff, foff, poff, ids, end, durations,
                        label);
     KK_LAUNCH_CHECK("kk_align_backtrack");
+    return 0;
+}
+
+extern "C" int kk_align_max_states(void) { return AL_MAXS; }
+
+extern "C" int kk_align_viterbi_states(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff,
+                                       const int *poff, const int64_t *coff, int B, int threads, int states, float *score, int *end,
+                                       uint32_t *codes, void *stream) {
+    KK_REQUIRE(L && ids && opt && foff && poff && coff && score && end && codes && B > 0 && T_total > 0, "kk_align_viterbi_states: bad args");
+    KK_REQUIRE(threads >= 64 && threads <= AL_MAXP && threads % 64 == 0,
+               "kk_align_viterbi_states: %d threads; needs a multiple of 64 in 64..%d", threads, AL_MAXP);
+    KK_REQUIRE(states >= 1 && states <= AL_MAXS, "kk_align_viterbi_states: %d states; needs 1..%d", states, AL_MAXS);
+    VitArgs r{L, T_total, ids, opt, foff, poff, coff, score, end, codes};
+    kk_note_kernel("align_viterbi_states");
+    if (states == 1) hipLaunchKernelGGL(align_viterbi_states_kernel<1>, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
+    else if (states == 2) hipLaunchKernelGGL(align_viterbi_states_kernel<2>, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
+    else hipLaunchKernelGGL(align_viterbi_states_kernel<3>, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
+    KK_LAUNCH_CHECK("kk_align_viterbi_states");
+    return 0;
+}
+
+extern "C" int kk_align_backtrack_states(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids,
+                                         const int *end, int B, int states, int *state_durations, int *durations, int *label,
+                                         void *stream) {
+    KK_REQUIRE(codes && coff && foff && poff && ids && end && state_durations && durations && label && B > 0,
+               "kk_align_backtrack_states: bad args");
+    KK_REQUIRE(states >= 1 && states <= AL_MAXS, "kk_align_backtrack_states: %d states; needs 1..%d", states, AL_MAXS);
+    kk_note_kernel("align_backtrack_states");
+    hipLaunchKernelGGL(align_backtrack_states_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, codes, coff, foff, poff, ids, end, states,
+                       state_durations, durations, label);
+    KK_LAUNCH_CHECK("kk_align_backtrack_states");
     return 0;
 }
 

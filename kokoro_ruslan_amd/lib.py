@@ -276,6 +276,9 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_align_loglik": [_P, _L, _I, _I, _P, _P, _P, _P, _P],
     "kk_align_viterbi": [_P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "kk_align_backtrack": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "kk_align_max_states": [],
+    "kk_align_viterbi_states": [_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "kk_align_backtrack_states": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "kk_align_accumulate": [_P, _P, _L, _I, _I, _P, _P, _P, _P],
     "kk_align_scores": [_P, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "kk_mel_finish": [_P, _P, _I, _L, _I, _F, _F, _D, _D, _I, _I, _P, _P, _P, _P],

@@ -8,7 +8,13 @@ one frame at a time, the recurrence alone: L given, no codes, no path), and the 
 in 16 threads.  Five repeats with the device paths interleaved inside every repeat; medians, with the spread.  The host oracle runs
 once per size on 16 utterances.  One JSON line at the end.
 
-    python tools/align_bench.py [repeats=5]"""
+    python tools/align_bench.py [repeats=5]
+    python tools/align_bench.py [repeats=5] --states S
+
+With --states S (1, 2 or 3) the same two sizes are aligned with S states per phoneme instead: PhoneAligner(states=S).align as above, and
+the Viterbi launch alone (device events) -- kk_align_viterbi_states with S states on L [V S, T] beside the 1-state kk_align_viterbi on
+the same box and the same frames (on the maximum over each phoneme's states), interleaved inside every repeat; medians, with the spread."""
+import argparse
 import json
 import os
 import statistics
@@ -22,7 +28,11 @@ import torch
 from kokoro_ruslan_amd import align_torch as R
 from kokoro_ruslan_amd.align import PhoneAligner
 
-REPEATS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+_ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+_ap.add_argument("repeats", nargs="?", type=int, default=5)
+_ap.add_argument("--states", type=int, choices=(1, 2, 3), default=None, metavar="S", help="states per phoneme: 1, 2 or 3")
+_args = _ap.parse_args()
+REPEATS, STATES = _args.repeats, _args.states
 SIZES, B, FIT_B, M, V = ((100, 600), (300, 1800)), 64, 256, 80, 59
 al = PhoneAligner(n_classes=V)
 
@@ -59,6 +69,56 @@ def torch_viterbi(L, ids):
     return S[:, P]
 
 
+def device_ms(fn):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e)
+
+
+def states_bench(S):
+    """--states S: the whole alignment with S states, and the S-state Viterbi launch beside the 1-state one."""
+    from kokoro_ruslan_amd import lib as kk
+    from kokoro_ruslan_amd.align import code_words
+    als = PhoneAligner(n_classes=V, states=S)
+    out, todo = {"repeats": REPEATS, "states": S, "align": {}}, []
+    for P, T in SIZES:
+        mels, ids = corpus(B, P, T, 1000 + P)
+        model, _, _ = als.fit(mels, ids, iters=2)                   # warm-up, and a model worth aligning with
+        run = als.run_packed(mels, ids, (), model)
+        Ls, L1 = run["L"], run["L"].view(V, S, -1).amax(1).contiguous()
+        opt = torch.zeros(B * P, dtype=torch.uint8, device="cuda")
+        score, end = torch.empty(B, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+        coff = {n: kk.packed_offsets([code_words(P, T, n)] * B).cuda() for n in {1, S}}
+        codes = torch.empty(B * code_words(P, T, S), dtype=torch.int32, device="cuda")
+        threads = (P + 63) // 64 * 64
+        def many(Ls=Ls, run=run, opt=opt, coff=coff[S], threads=threads, score=score, end=end, codes=codes):
+            kk.call("kk_align_viterbi_states", Ls, Ls.shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, threads, S, score, end, codes)
+
+        def one(L1=L1, run=run, opt=opt, coff=coff[1], threads=threads, score=score, end=end, codes=codes):
+            kk.call("kk_align_viterbi", L1, L1.shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, threads, score, end, codes)
+        many(), one()
+        todo.append(((P, T), mels, ids, model, many, one, {"align_s": [], "viterbi_states_ms": [], "viterbi_1state_ms": []}))
+    for _ in range(REPEATS):
+        for _, mels, ids, model, many, one, r in todo:
+            r["align_s"].append(timed(lambda: als.align(mels, ids, (), model))[1])   # (called at once: this pass's mels)
+            r["viterbi_states_ms"].append(device_ms(many))
+            r["viterbi_1state_ms"].append(device_ms(one))
+    for (P, T), _, _, _, _, _, r in todo:
+        ta, tm, t1 = (statistics.median(r[k]) for k in ("align_s", "viterbi_states_ms", "viterbi_1state_ms"))
+        r.update(align_median_s=ta, utterances_per_s=B / ta, viterbi_states_median_ms=tm, viterbi_1state_median_ms=t1, ratio=tm / t1)
+        out["align"][f"{P}x{T}"] = r
+        print(f"{P} x {T}, B = {B}, {S} state(s): align {ta * 1e3:8.2f} ms [{min(r['align_s']) * 1e3:.2f}, {max(r['align_s']) * 1e3:.2f}] = "
+              f"{B / ta:8.0f} utterances/s | Viterbi launch {tm:.3f} ms [{min(r['viterbi_states_ms']):.3f}, {max(r['viterbi_states_ms']):.3f}] "
+              f"| 1-state kernel {t1:.3f} ms [{min(r['viterbi_1state_ms']):.3f}, {max(r['viterbi_1state_ms']):.3f}] | x{tm / t1:.2f}")
+    print(json.dumps(out))
+
+
+if STATES is not None:
+    states_bench(STATES)
+    sys.exit(0)
 result = {"repeats": REPEATS, "align": {}, "fit": {}}
 cases = {}
 for P, T in SIZES:
