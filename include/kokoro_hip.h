@@ -22,7 +22,9 @@
 extern "C" {
 #endif
 
-#define KK_ABI_VERSION 3 /* 3: kk_im2col3_fwd, kk_groupnorm_relu_fwd and kk_rowdot_fwd take the rows' lengths (`lens`, may be NULL); the
+#define KK_ABI_VERSION 4 /* 4: kk_align_viterbi and kk_align_backtrack take `states` (backtrack also `state_durations`, may be NULL at 1
+                          state); kk_align_viterbi_states and kk_align_backtrack_states are gone;
+                          3: kk_im2col3_fwd, kk_groupnorm_relu_fwd and kk_rowdot_fwd take the rows' lengths (`lens`, may be NULL); the
                           per-row variants of the first two and the row-mask entry point of batched synthesis are gone;
                           2 (round 6): kk_seg_sumsq takes a record workspace instead of `zeroed`; p_sumsq of kk_adamw_ema /
                           kk_weight_norm_project is an int64 Q34.30 sum; round 5 had already added parameters to kk_losses_fwd,
@@ -637,32 +639,23 @@ int kk_align_feats(const float *cep, const float *mel, int64_t T_total, int M, i
  * sum_d ln(2 pi var): [V][D], [V][D], [V] from the HOST (fp64, rounded once).  D <= 64, V <= 256; L: [V][T_total] */
 int kk_align_loglik(const float *feat, int64_t T_total, int D, int V, const float *a, const float *mu, const float *c, float *L,
                     void *stream);
-/* one workgroup of `threads` (a multiple of 64 >= every P) per utterance: S(p, t) = L[ids[p]][t] + max(S(p, t-1), S(p-1, t-1),
- * S(p-2, t-1) if opt[p-1]), a later candidate only when strictly greater; S(0, 0) = L[ids[0]][0] and, if opt[0], S(1, 0) =
- * L[ids[1]][0]; the end state is P-1, or P-2 when opt[P-1] and that cell is strictly greater.  score[b] = S(end, T-1) and end[b],
- * or -inf and -1 when no path exists.  codes: the candidate of every cell as 2 bits (0 stay, 1 advance, 2 skip), token p at frame t
- * of utterance b in word coff[b] + t ceil(P / 16) + p / 16: its low bit at bit p % 16, its high bit at bit 16 + p % 16; coff: int64
- * [B + 1] */
-int kk_align_viterbi(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff, const int *poff,
-                     const int64_t *coff, int B, int threads, float *score, int *end, uint32_t *codes, void *stream);
-/* one wave per utterance walks codes from end[b] back to frame 0: durations [P_total] (frames per token, 0 for a skipped one) and
- * label [T_total] (the phoneme id of every frame); an infeasible utterance gets durations 0 and labels -1 */
-int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids, const int *end,
-                       int B, int *durations, int *label, void *stream);
-/* multi-state phone models: `states` = S in 1..kk_align_max_states() states per phoneme in a left-to-right chain, class v S + j, L:
- * [V S][T_total].  Sigma(p, j, t) = L[ids[p] S + j][t] + max(stay Sigma(p, j, t-1); advance Sigma(p, j-1, t-1) if j > 0, else
- * Sigma(p-1, S-1, t-1); skip Sigma(p-2, S-1, t-1) only for j = 0 and opt[p-1]), a later candidate only when strictly greater.  Start
- * (0, 0) and, if opt[0], (1, 0); end (P-1, S-1), or (P-2, S-1) when opt[P-1] and strictly greater.  score and end (the end TOKEN) as
- * kk_align_viterbi.  codes: state j of token p at frame t of utterance b in word coff[b] + (t S + j) ceil(P / 16) + p / 16, bits as
- * above; coff counts T S ceil(P / 16) words per utterance.  With S = 1 every output is kk_align_viterbi's, bit for bit */
+/* states per phoneme kk_align_viterbi and kk_align_backtrack take */
 int kk_align_max_states(void);
-int kk_align_viterbi_states(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff,
-                            const int *poff, const int64_t *coff, int B, int threads, int states, float *score, int *end,
-                            uint32_t *codes, void *stream);
-/* one wave per utterance walks (p, j) from (end[b], S-1) back to frame 0: state_durations [P_total][S], durations [P_total] (their
- * row sums) and label [T_total], the CLASS ids[p] S + j of every frame; an infeasible utterance gets zeros and labels -1 */
-int kk_align_backtrack_states(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids,
-                              const int *end, int B, int states, int *state_durations, int *durations, int *label, void *stream);
+/* a phoneme is a left-to-right chain of `states` = S in 1..kk_align_max_states() states, class v S + j for state j of phoneme v; L:
+ * [V S][T_total].  One workgroup of `threads` (a multiple of 64 >= every P) per utterance: Sigma(p, j, t) = L[ids[p] S + j][t] +
+ * max(stay Sigma(p, j, t-1); advance Sigma(p, j-1, t-1) if j > 0, else Sigma(p-1, S-1, t-1); skip Sigma(p-2, S-1, t-1) only for j = 0
+ * and opt[p-1]), a later candidate only when strictly greater.  Start (0, 0) and, if opt[0], (1, 0); end (P-1, S-1), or (P-2, S-1)
+ * when opt[P-1] and that cell is strictly greater.  score[b] = Sigma(end, S-1, T-1) and end[b], the end TOKEN, or -inf and -1 when no
+ * path exists.  codes: the candidate of every cell as 2 bits (0 stay, 1 advance, 2 skip), state j of token p at frame t of utterance
+ * b in word coff[b] + (t S + j) ceil(P / 16) + p / 16: its low bit at bit p % 16, its high bit at bit 16 + p % 16; coff: int64 [B + 1],
+ * T S ceil(P / 16) words per utterance.  S = 1 is the plain case: one Gaussian per phoneme, class = phoneme id, [T][ceil(P / 16)] */
+int kk_align_viterbi(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff, const int *poff,
+                     const int64_t *coff, int B, int threads, int states, float *score, int *end, uint32_t *codes, void *stream);
+/* one wave per utterance walks (p, j) along codes from (end[b], S-1) back to frame 0: state_durations [P_total][S] (NULL allowed iff
+ * S = 1, where it equals durations), durations [P_total] (their row sums: frames per token, 0 for a skipped one) and label [T_total],
+ * the CLASS ids[p] S + j of every frame; an infeasible utterance gets zeros and labels -1 */
+int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids, const int *end,
+                       int B, int states, int *state_durations, int *durations, int *label, void *stream);
 /* per class v < V over the frames with label[t] == v: count [V], sum [V][D] and sumsq [V][D] of feat [D][T_total] in fp64, by
  * fixed-order partial sums and a fixed tree (no atomics: two runs give the same bits) */
 int kk_align_accumulate(const float *feat, const int *label, int64_t T_total, int D, int V, int64_t *count, double *sum,

@@ -18,14 +18,14 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import torch
 
 from kokoro_ruslan_amd import lib as kk
-from kokoro_ruslan_amd.align_torch import VAR_MIN, even_split, split_states
+from kokoro_ruslan_amd.align_torch import VAR_MIN, even_split
 from kokoro_ruslan_amd.dtw_torch import dct_table
 
 MAX_FRAMES = 4096                        # the longest utterance the kernels take (the positional table's order)
 MAX_MEL = 128                            # kk_mcep stages 64 frames of at most this many channels
 MAX_CLASSES = 256                        # kk_align_loglik
 MAX_DIM = 64
-MAX_STATES = 3                           # kk_align_viterbi_states
+MAX_STATES = 3                           # kk_align_viterbi
 
 
 def max_tokens() -> int:
@@ -36,6 +36,15 @@ def max_tokens() -> int:
 def code_words(P: int, T: int, S: int = 1) -> int:
     """32-bit code words of a P-token, T-frame utterance with S states per token: 16 tokens of a (frame, state) per word, [T][S][W]."""
     return T * S * ((P + 15) // 16)
+
+
+def flat_start(ids: torch.Tensor, d: torch.Tensor, S: int):
+    """The labels Viterbi training starts from: tokens ids [P] with d [P] frames each, every token's frames spread over its S states as
+    align_torch.split_states spreads them.  (state durations [P, S], the class ids[p] S + j of every frame); with S = 1 these are d[:, None]
+    and repeat_interleave(ids, d)."""
+    j = torch.arange(S)[None, :]
+    sd = torch.div(d[:, None], S, rounding_mode="floor") + (j < (d % S)[:, None])
+    return sd, torch.repeat_interleave((ids[:, None] * S + j).reshape(-1), sd.reshape(-1))
 
 
 class PhoneAligner:
@@ -198,18 +207,14 @@ class PhoneAligner:
         run = {"feat": pk["feat"], "L": L, "score": score, "end": end, "codes": codes, "durations": durations, "label": label,
                "foff_host": pk["foff_host"], "poff_host": pk["poff_host"], "coff_host": pk["coff_host"],
                "ids": pk["ids"], "foff": pk["foff"], "poff": pk["poff"]}
-        if self.states == 1:
-            kk.call("kk_align_viterbi", L, L.shape[1], pk["ids"], pk["opt"], pk["foff"], pk["poff"], pk["coff"], B, pk["threads"], score,
-                    end, codes)
-            kk.call("kk_align_backtrack", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, durations, label)
-            return run
         S = self.states
-        sdur = torch.empty(pk["poff_host"][-1], S, dtype=torch.int32, device=dev)
-        kk.call("kk_align_viterbi_states", L, L.shape[1], pk["ids"], pk["opt"], pk["foff"], pk["poff"], pk["coff"], B, pk["threads"], S,
-                score, end, codes)
-        kk.call("kk_align_backtrack_states", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, S, sdur, durations, label)
-        # label is the class v S + j of every frame (what accumulate takes); the scores take the phoneme: label // S, -1 staying -1
-        run.update(states=S, state_durations=sdur, phone_label=torch.div(label, S, rounding_mode="floor"))
+        sdur = torch.empty(pk["poff_host"][-1], S, dtype=torch.int32, device=dev) if S > 1 else None      # (1 state: the durations)
+        kk.call("kk_align_viterbi", L, L.shape[1], pk["ids"], pk["opt"], pk["foff"], pk["poff"], pk["coff"], B, pk["threads"], S, score,
+                end, codes)
+        kk.call("kk_align_backtrack", codes, pk["coff"], pk["foff"], pk["poff"], pk["ids"], end, B, S, sdur, durations, label)
+        if sdur is not None:
+            # label is the class v S + j of every frame (what accumulate takes); the scores take the phoneme: label // S, -1 staying -1
+            run.update(states=S, state_durations=sdur, phone_label=torch.div(label, S, rounding_mode="floor"))
         return run
 
     def run_packed(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (),
@@ -342,7 +347,7 @@ class PhoneAligner:
         """Viterbi training from the even split: `iters` passes of estimate -> align over the corpus in batches of batch_size, the
         class statistics accumulated batch by batch in that order; stops once no duration changes.  Returns (model, durations: list of
         LongTensor [P] | None, scores: the corpus score of each pass).  With states = S > 1 the flat start spreads every token's frames
-        of the even split evenly over its S states (align_torch.split_states), the passes stop once no STATE duration changes, and the
+        of the even split evenly over its S states (flat_start), the passes stop once no STATE duration changes, and the
         state durations of the last pass are in `self.state_durations` (list of LongTensor [P, S] | None)."""
         if int(iters) != iters or iters < 1:
             raise ValueError(f"iters must be an integer >= 1, not {iters!r}")
@@ -355,18 +360,13 @@ class PhoneAligner:
             e = s + batch_size
             packs.append(self._pack(None if feats is not None else x[s:e], ids[s:e], optional_ids, None if feats is None else x[s:e]))
         flat = [torch.from_numpy(even_split(int(t.shape[0]), int(m.shape[0]))) for m, t in zip(x, ids)]
-        labels, n = [], 0
+        S, labels, n = self.states, [], 0
+        durs: List[Optional[torch.Tensor]] = []                                   # state durations [P, S]
         for pk in packs:
-            d = torch.cat(flat[n:n + pk["B"]])
-            if self.states == 1:
-                labels.append(torch.repeat_interleave(pk["ids_host"], d).to(torch.int32).to(self.device))
-            else:
-                S = self.states
-                cls = (pk["ids_host"][:, None] * S + torch.arange(S)[None, :]).reshape(-1)
-                labels.append(torch.repeat_interleave(cls, torch.from_numpy(split_states(d.numpy(), S)).reshape(-1)).to(torch.int32).to(self.device))
+            sd, lab = flat_start(pk["ids_host"], torch.cat(flat[n:n + pk["B"]]), S)
+            durs.extend(sd.split(pk["tokens"]))
+            labels.append(lab.to(torch.int32).to(self.device))
             n += pk["B"]
-        key = "durations" if self.states == 1 else "state_durations"          # what has to stop changing
-        durs: List[Optional[torch.Tensor]] = list(flat) if self.states == 1 else [torch.from_numpy(split_states(d.numpy(), self.states)) for d in flat]
         phone: List[Optional[torch.Tensor]] = list(flat)
         model, scores = None, []
         for _ in range(int(iters)):
@@ -380,15 +380,16 @@ class PhoneAligner:
                 run = self._align_packed(pk, model)
                 labels.append(run["label"])
                 for r in self._records(run):
-                    new.append(r[key])
+                    new.append(r.get("state_durations", r["durations"]))          # what has to stop changing (1 state: the durations)
                     phone.append(r["durations"])
                     total += r["score"] if r["feasible"] else 0.0
             scores.append(total)
-            same = all((d is None and e is None) or (d is not None and e is not None and torch.equal(d, e)) for d, e in zip(durs, new))
+            same = all((d is None and e is None) or (d is not None and e is not None and torch.equal(d.reshape(-1), e.reshape(-1)))
+                       for d, e in zip(durs, new))
             durs = new
             if same:
                 break
-        self.state_durations = durs if self.states > 1 else None
+        self.state_durations = durs if S > 1 else None
         return model, phone, scores
 
     # ---- the model on disk -------------------------------------------------------------------------------------------------------

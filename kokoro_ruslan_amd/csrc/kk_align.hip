@@ -10,28 +10,34 @@
 //   loglik      L[v][t] = sum over ascending d of a[v][d] (x[d][t] - mu[v][d])^2 (one fmaf chain), plus c[v]: a = -1/2 / var, mu and
 //               c = -1/2 sum_d ln(2 pi var) come from the HOST (fp64, rounded once).  A workgroup takes 256 frames and 16 classes,
 //               whose parameters it stages in LDS (read wave-uniformly); a thread holds its frame's features in registers.
-//   viterbi     one workgroup per utterance, thread p = token p: S(p, t) = L[ids[p]][t] + max(S(p, t-1), S(p-1, t-1), S(p-2, t-1) if
-//               token p-1 is optional), a later candidate only when strictly greater.  Only column t-1 is needed: two columns of S
-//               in LDS, two cells of -inf in front of each so that p-1 and p-2 need no branch, one barrier per frame.  A thread
-//               loads its row of L eight frames ahead.  The candidate chosen (0 stay, 1 advance, 2 skip) goes out as 2 bits, 16
-//               tokens per 32-bit word, straight from two wave ballots: bits 0..15 of a word are the low bits of the 16 codes, bits
-//               16..31 their high bits.
-//   backtrack   one wave per utterance: lane 0 walks the code words from the end state back to frame 0, counting durations in LDS
-//               and writing every frame's class id; the wave writes the durations out.  An infeasible utterance (no finite path)
-//               gets durations 0 and labels -1.
+//   viterbi     a phoneme is a left-to-right chain of NS states (1..3; align_torch.viterbi_states), class v NS + j for state j of
+//               phoneme v.  One workgroup per utterance, thread p = token p, which keeps its NS scores in registers:
+//               S(p, j, t) = L[ids[p] NS + j][t] + max(S(p, j, t-1), S(p, j-1, t-1)) for j > 0, and for j = 0 the maximum of
+//               S(p, 0, t-1), S(p-1, NS-1, t-1) and, if token p-1 is optional, S(p-2, NS-1, t-1); a later candidate only when
+//               strictly greater.  The states are updated in descending j, so S(p, j-1, t-1) is read before it is overwritten.  A
+//               neighbour reads only the LAST state's score, and only of column t-1: two columns of it in LDS, two cells of -inf in
+//               front of each so that p-1 and p-2 need no branch, one barrier per frame.  A thread loads its rows of L eight frames
+//               ahead.  The candidate chosen (0 stay, 1 advance, 2 skip) goes out as 2 bits, 16 tokens per 32-bit word, straight
+//               from the wave ballots: bits 0..15 of a word are the low bits of the 16 codes, bits 16..31 their high bits (zero
+//               for j > 0); one row of W = ceil(P / 16) words per (frame, state): [T][NS][W].
+//   backtrack   one wave per utterance: lane 0 walks (p, j) from (end, NS - 1) back to frame 0 along the code words; code 1 at j > 0
+//               steps to the state before, code 1 at j = 0 to the last state of the token before, code 2 to the last state of the
+//               token two before.  It counts the state durations in LDS and writes every frame's class ids[p] NS + j; the wave
+//               writes the state durations and their row sums, the durations, out.  An infeasible utterance (no finite path) gets
+//               durations 0 and labels -1.
 //   accumulate  per class the count and, in fp64, sum x and sum x^2 over the frames labelled with it: one workgroup per (class, four
 //               dimensions), thread i sums the frames i, i + 256, ... in order, then a fixed tree.  No atomics: two runs give the
 //               same bits.
 // Nothing an utterance computes in feats, viterbi or backtrack depends on the other utterances, and a frame's L on that frame alone.
 // kk_align_scores (two more launches, described where they stand) turns L and an alignment into pronunciation scores.
-// kk_align_viterbi_states / kk_align_backtrack_states (described where they stand) are the same two steps for phone models of 2 or 3
-// states per phoneme; feats, loglik, accumulate and scores serve them unchanged, with V S classes.
+// feats, loglik, accumulate and scores know nothing of states: they take V NS classes.
 #include "kk_common.h"
 
 namespace {
 
 constexpr int AL_MAXP = 1024;                 // tokens of an utterance = threads of its workgroup
 constexpr int AL_MAXT = 4096;                 // frames of an utterance (the positional table's order, as kk_dtw)
+constexpr int AL_MAXS = 3;                    // states per phoneme
 constexpr int AL_PRE = 8;                     // frames of L a state loads ahead
 constexpr int AL_THREADS = 256;
 constexpr int LL_VC = 16;                     // classes per workgroup of loglik_kernel
@@ -103,115 +109,19 @@ __global__ __launch_bounds__(AL_THREADS) void align_loglik_kernel(const float *_
 }
 
 struct VitArgs {
-    const float *L;                           // [V][T_total]
+    const float *L;                           // [V NS][T_total]
     int64_t T_total;
     const int *ids;                           // [P_total]
     const unsigned char *opt;                 // [P_total]: 1 where the token may be skipped
     const int *foff, *poff;
     const int64_t *coff;                      // first code word of each utterance
     float *score;
-    int *end;                                 // the end state, -1 when infeasible
+    int *end;                                 // the end token, -1 when infeasible
     uint32_t *codes;
 };
 
-__global__ __launch_bounds__(AL_MAXP) void align_viterbi_kernel(const VitArgs a) {
-    __shared__ float S[2][AL_MAXP + 2];                               // state p at [p + 2]; [0] and [1] stay -inf
-    const int b = blockIdx.x, p = threadIdx.x;
-    const int f0 = a.foff[b], T = a.foff[b + 1] - f0, p0 = a.poff[b], P = a.poff[b + 1] - p0;
-    if (P < 1 || P > (int)blockDim.x || T < 1 || T > AL_MAXT) return;  // (the host checks)
-    const bool live = p < P, wave_live = (p & ~63) < P;               // a wave past the last token only keeps the barriers
-    const int W = (P + 15) >> 4;                                      // code words per frame
-    uint32_t *codes = a.codes + a.coff[b];
-    const float ninf = -__builtin_inff();
-    const float *Lr = a.L + (int64_t)(live ? a.ids[p0 + p] : 0) * a.T_total + f0;
-    const bool may_skip = live && p >= 2 && a.opt[p0 + p - 1];
-    const bool starts = p == 0 || (p == 1 && a.opt[p0]);
-    if (p < 2) S[0][p] = S[1][p] = ninf;
-    __syncthreads();
-    for (int t0 = 0; t0 < T; t0 += AL_PRE) {
-        float l[AL_PRE];
-        if (wave_live) {
-#pragma unroll
-            for (int u = 0; u < AL_PRE; ++u) l[u] = Lr[min(t0 + u, T - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < AL_PRE; ++u) {
-            const int t = t0 + u;
-            if (t >= T) break;
-            if (wave_live) {
-                const float *prev = S[(t & 1) ^ 1];
-                float s;
-                uint32_t code = 0;
-                if (t == 0) s = starts ? l[u] : ninf;
-                else {
-                    float best = prev[p + 2];
-                    const float adv = prev[p + 1], skip = may_skip ? prev[p] : ninf;
-                    if (adv > best) best = adv, code = 1;
-                    if (skip > best) best = skip, code = 2;
-                    s = l[u] + best;
-                }
-                if (live) S[t & 1][p + 2] = s;
-                else code = 0;
-                const unsigned long long lo = __ballot(code & 1u), hi = __ballot(code & 2u);
-                if (live && (p & 15) == 0) {
-                    const int sh = p & 48;
-                    codes[(int64_t)t * W + (p >> 4)] = (uint32_t)((lo >> sh) & 0xffffull) | ((uint32_t)((hi >> sh) & 0xffffull) << 16);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (p == 0) {
-        const float *last = S[(T - 1) & 1];
-        int e = P - 1;
-        float s = last[P + 1];
-        if (P > 1 && a.opt[p0 + P - 1] && last[P] > s) e = P - 2, s = last[P];
-        const bool ok = s > ninf;                                     // (false for a NaN too)
-        a.score[b] = ok ? s : ninf;
-        a.end[b] = ok ? e : -1;
-    }
-}
-
-__global__ __launch_bounds__(64) void align_backtrack_kernel(const uint32_t *__restrict__ codes, const int64_t *__restrict__ coff,
-                                                             const int *__restrict__ foff, const int *__restrict__ poff,
-                                                             const int *__restrict__ ids, const int *__restrict__ end,
-                                                             int *__restrict__ durations, int *__restrict__ label) {
-    __shared__ int dur[AL_MAXP];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int f0 = foff[b], T = foff[b + 1] - f0, p0 = poff[b], P = poff[b + 1] - p0;
-    if (P < 1 || P > AL_MAXP || T < 1 || T > AL_MAXT) return;
-    for (int p = lane; p < P; p += 64) dur[p] = 0;
-    __syncthreads();
-    const int e = end[b];
-    if (e < 0 || e >= P) {
-        for (int t = lane; t < T; t += 64) label[f0 + t] = -1;
-    } else if (lane == 0) {
-        const uint32_t *cod = codes + coff[b];
-        const int W = (P + 15) >> 4;
-        int p = e;
-        for (int t = T - 1; t >= 0; --t) {
-            ++dur[p];
-            label[f0 + t] = ids[p0 + p];
-            if (t) {
-                const uint32_t w = cod[(int64_t)t * W + (p >> 4)] >> (p & 15);
-                p = max(p - (int)min((w & 1u) | ((w >> 15) & 2u), 2u), 0);
-            }
-        }
-    }
-    __syncthreads();
-    for (int p = lane; p < P; p += 64) durations[p0 + p] = dur[p];
-}
-
-// ---- multi-state phone models: a left-to-right chain of NS states per phoneme (align_torch.viterbi_states) -----------------------------
-// The classes are v NS + j.  Thread p still owns token p and keeps its NS scores in registers; only the LAST state's score goes to
-// LDS, in the same two columns with the same two -inf cells in front, because Sigma(p-1, NS-1) and Sigma(p-2, NS-1) are all a
-// neighbour reads: one barrier per frame, as above.  The states are updated in descending j, so Sigma(p, j-1, t-1) is read before it
-// is overwritten.  Code words as above, one row of ceil(P / 16) words per (frame, state): [T][NS][W].  With NS = 1 every operation, and
-// so every bit written, is align_viterbi_kernel's.
-constexpr int AL_MAXS = 3;                    // states per phoneme
-
 template <int NS>
-__global__ __launch_bounds__(AL_MAXP) void align_viterbi_states_kernel(const VitArgs a) {
+__global__ __launch_bounds__(AL_MAXP) void align_viterbi_kernel(const VitArgs a) {
     __shared__ float S[2][AL_MAXP + 2];                               // the last state of token p at [p + 2]; [0] and [1] stay -inf
     const int b = blockIdx.x, p = threadIdx.x;
     const int f0 = a.foff[b], T = a.foff[b + 1] - f0, p0 = a.poff[b], P = a.poff[b + 1] - p0;
@@ -285,17 +195,16 @@ __global__ __launch_bounds__(AL_MAXP) void align_viterbi_states_kernel(const Vit
     }
 }
 
-// One wave per utterance: lane 0 walks (p, j) from (end, NS - 1) back to frame 0; code 1 at j > 0 steps to the state before, code 1
-// at j = 0 to the last state of the token before, code 2 to the last state of the token two before.  label is the CLASS ids[p] NS + j.
-__global__ __launch_bounds__(64) void align_backtrack_states_kernel(const uint32_t *__restrict__ codes, const int64_t *__restrict__ coff,
-                                                                    const int *__restrict__ foff, const int *__restrict__ poff,
-                                                                    const int *__restrict__ ids, const int *__restrict__ end, int NS,
-                                                                    int *__restrict__ state_durations, int *__restrict__ durations,
-                                                                    int *__restrict__ label) {
-    __shared__ int dur[AL_MAXP * AL_MAXS];
+template <int NS>
+__global__ __launch_bounds__(64) void align_backtrack_kernel(const uint32_t *__restrict__ codes, const int64_t *__restrict__ coff,
+                                                             const int *__restrict__ foff, const int *__restrict__ poff,
+                                                             const int *__restrict__ ids, const int *__restrict__ end,
+                                                             int *__restrict__ state_durations,      // NULL: not wanted (NS = 1)
+                                                             int *__restrict__ durations, int *__restrict__ label) {
+    __shared__ int dur[AL_MAXP * NS];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int f0 = foff[b], T = foff[b + 1] - f0, p0 = poff[b], P = poff[b + 1] - p0;
-    if (P < 1 || P > AL_MAXP || T < 1 || T > AL_MAXT || NS < 1 || NS > AL_MAXS) return;
+    if (P < 1 || P > AL_MAXP || T < 1 || T > AL_MAXT) return;
     for (int q = lane; q < P * NS; q += 64) dur[q] = 0;
     __syncthreads();
     const int e = end[b];
@@ -311,19 +220,33 @@ __global__ __launch_bounds__(64) void align_backtrack_states_kernel(const uint32
             if (t) {
                 const uint32_t w = cod[((int64_t)t * NS + j) * W + (p >> 4)] >> (p & 15);
                 const int c = (int)min((w & 1u) | ((w >> 15) & 2u), 2u);
-                if (c == 1 && j > 0) --j;
-                else if (c) p = max(p - c, 0), j = NS - 1;
+                if (NS > 1 && c == 1 && j > 0) --j;
+                else {                                                // (NS = 1: p - c alone, nothing to choose in the walk's chain)
+                    p = max(p - c, 0);
+                    if (NS > 1 && c) j = NS - 1;
+                }
             }
         }
     }
     __syncthreads();
-    for (int q = lane; q < P * NS; q += 64) state_durations[(int64_t)p0 * NS + q] = dur[q];
+    if (state_durations)
+        for (int q = lane; q < P * NS; q += 64) state_durations[(int64_t)p0 * NS + q] = dur[q];
     for (int q = lane; q < P; q += 64) {
         int d = 0;
+#pragma unroll
         for (int j = 0; j < NS; ++j) d += dur[q * NS + j];
         durations[p0 + q] = d;
     }
 }
+
+// The one place that turns the run-time `states` into NS: launches align_viterbi_kernel<NS> or align_backtrack_kernel<NS>.
+#define AL_LAUNCH_NS(kernel, states, ...)                                   \
+    do {                                                                    \
+        if ((states) == 1) hipLaunchKernelGGL(kernel<1>, __VA_ARGS__);      \
+        else if ((states) == 2) hipLaunchKernelGGL(kernel<2>, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kernel<3>, __VA_ARGS__);                    \
+    } while (0)
+static_assert(AL_MAXS == 3, "AL_LAUNCH_NS instantiates 1..3");
 
 __global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const float *__restrict__ feat, const int *__restrict__ label,
                                                                       int64_t T_total, int D, long long *__restrict__ count,
@@ -518,57 +441,31 @@ extern "C" int kk_align_loglik(const float *feat, int64_t T_total, int D, int V,
     return 0;
 }
 
+extern "C" int kk_align_max_states(void) { return AL_MAXS; }
+
 extern "C" int kk_align_viterbi(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff,
-                                const int *poff, const int64_t *coff, int B, int threads, float *score, int *end, uint32_t *codes,
-                                void *stream) {
+                                const int *poff, const int64_t *coff, int B, int threads, int states, float *score, int *end,
+                                uint32_t *codes, void *stream) {
     KK_REQUIRE(L && ids && opt && foff && poff && coff && score && end && codes && B > 0 && T_total > 0, "kk_align_viterbi: bad args");
     KK_REQUIRE(threads >= 64 && threads <= AL_MAXP && threads % 64 == 0, "kk_align_viterbi: %d threads; needs a multiple of 64 in 64..%d",
                threads, AL_MAXP);
+    KK_REQUIRE(states >= 1 && states <= AL_MAXS, "kk_align_viterbi: %d states; needs 1..%d", states, AL_MAXS);
     VitArgs r{L, T_total, ids, opt, foff, poff, coff, score, end, codes};
     kk_note_kernel("align_viterbi");
-    hipLaunchKernelGGL(align_viterbi_kernel, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
+    AL_LAUNCH_NS(align_viterbi_kernel, states, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
     KK_LAUNCH_CHECK("kk_align_viterbi");
     return 0;
 }
 
 extern "C" int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids,
-                                  const int *end, int B, int *durations, int *label, void *stream) {
+                                  const int *end, int B, int states, int *state_durations, int *durations, int *label, void *stream) {
     KK_REQUIRE(codes && coff && foff && poff && ids && end && durations && label && B > 0, "kk_align_backtrack: bad args");
+    KK_REQUIRE(states >= 1 && states <= AL_MAXS, "kk_align_backtrack: %d states; needs 1..%d", states, AL_MAXS);
+    KK_REQUIRE(state_durations || states == 1, "kk_align_backtrack: %d states need state_durations", states);
     kk_note_kernel("align_backtrack");
-    hipLaunchKernelGGL(align_backtrack_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, codes, coff, foff, poff, ids, end, durations,
-                       label);
+    AL_LAUNCH_NS(align_backtrack_kernel, states, dim3(B), dim3(64), 0, (hipStream_t)stream, codes, coff, foff, poff, ids, end,
+                 state_durations, durations, label);
     KK_LAUNCH_CHECK("kk_align_backtrack");
-    return 0;
-}
-
-extern "C" int kk_align_max_states(void) { return AL_MAXS; }
-
-extern "C" int kk_align_viterbi_states(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff,
-                                       const int *poff, const int64_t *coff, int B, int threads, int states, float *score, int *end,
-                                       uint32_t *codes, void *stream) {
-    KK_REQUIRE(L && ids && opt && foff && poff && coff && score && end && codes && B > 0 && T_total > 0, "kk_align_viterbi_states: bad args");
-    KK_REQUIRE(threads >= 64 && threads <= AL_MAXP && threads % 64 == 0,
-               "kk_align_viterbi_states: %d threads; needs a multiple of 64 in 64..%d", threads, AL_MAXP);
-    KK_REQUIRE(states >= 1 && states <= AL_MAXS, "kk_align_viterbi_states: %d states; needs 1..%d", states, AL_MAXS);
-    VitArgs r{L, T_total, ids, opt, foff, poff, coff, score, end, codes};
-    kk_note_kernel("align_viterbi_states");
-    if (states == 1) hipLaunchKernelGGL(align_viterbi_states_kernel<1>, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
-    else if (states == 2) hipLaunchKernelGGL(align_viterbi_states_kernel<2>, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
-    else hipLaunchKernelGGL(align_viterbi_states_kernel<3>, dim3(B), dim3(threads), 0, (hipStream_t)stream, r);
-    KK_LAUNCH_CHECK("kk_align_viterbi_states");
-    return 0;
-}
-
-extern "C" int kk_align_backtrack_states(const uint32_t *codes, const int64_t *coff, const int *foff, const int *poff, const int *ids,
-                                         const int *end, int B, int states, int *state_durations, int *durations, int *label,
-                                         void *stream) {
-    KK_REQUIRE(codes && coff && foff && poff && ids && end && state_durations && durations && label && B > 0,
-               "kk_align_backtrack_states: bad args");
-    KK_REQUIRE(states >= 1 && states <= AL_MAXS, "kk_align_backtrack_states: %d states; needs 1..%d", states, AL_MAXS);
-    kk_note_kernel("align_backtrack_states");
-    hipLaunchKernelGGL(align_backtrack_states_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, codes, coff, foff, poff, ids, end, states,
-                       state_durations, durations, label);
-    KK_LAUNCH_CHECK("kk_align_backtrack_states");
     return 0;
 }
 

@@ -131,6 +131,21 @@ def test_split_states_and_phone_max():
     assert np.array_equal(R.phone_max(L, 1), L)
 
 
+def test_the_hosts_flat_start_is_split_states_and_at_one_state_the_phoneme_per_frame():
+    import torch
+    from kokoro_ruslan_amd.align import flat_start
+    g = torch.Generator().manual_seed(5)
+    for S in (1, 2, 3):
+        for P in (1, 2, 7, 100):
+            ids, d = torch.randint(0, 59, (P,), generator=g), torch.randint(0, 9, (P,), generator=g)
+            sd, lab = flat_start(ids, d, S)
+            want = R.split_states(d.numpy(), S)
+            assert sd.dtype == torch.int64 and np.array_equal(sd.numpy(), want)
+            assert np.array_equal(lab.numpy(), R.state_labels(ids.numpy(), want, S))
+            if S == 1:
+                assert torch.equal(sd, d[:, None]) and torch.equal(lab, torch.repeat_interleave(ids, d))
+
+
 # The parameters of the comparison below: sub-means N(0, 1) per dimension and noise 1.5 make the two halves of a phone as far from each
 # other as from another phone, at a noise level where one Gaussian per phone blurs the boundaries.
 PARTS_KW = dict(parts=2, V=12, D=8, mean_std=1.0, noise=1.5)

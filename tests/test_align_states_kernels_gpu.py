@@ -1,18 +1,21 @@
-"""GPU suite: kk_align_viterbi_states / kk_align_backtrack_states (csrc/kk_align.hip), the recurrence and the backtrack of phone models
+"""GPU suite: kk_align_viterbi / kk_align_backtrack (csrc/kk_align.hip), the recurrence and the backtrack of phone models
 with S = 1, 2 or 3 states per phoneme, called on a given L [V S, T_total] and held against the fp64 oracle
 (kokoro_ruslan_amd.align_torch.viterbi_states).
 
 Shapes: P in {1, 2, 15, 16, 17, 63, 64, 65} (the code word's and the wave's edges), T in {S P, S P + 1, 7, 8, 9, 17, 2 S P + 3} where a
 path exists (the eight-frame prefetch's edges), every S, and optional tokens nowhere, inside, first and last.
 
-  S = 1     every output is, bit for bit, what kk_align_viterbi / kk_align_backtrack give on the same L.
+  parent    every output at every S is, bit for bit, what the entry points of the commit before the two kernel families became one
+            gave on the same L (tests/golden/align_parent_outputs.npz, recorded on an MI355X).
   exact     L holds integers in -6..6, so every fp32 sum is exact and the kernel must agree with the oracle in every state duration,
             the score and every label, ties included (there are many).
   random    fp32 near-ties may choose differently, so as in test_align_kernels_gpu.py the score pins the recurrence: with S64 the
             oracle's optimum on the same L and A = sum_t max_c |L(c, t)|, |score - S64| <= T 2^-23 A, and the fp64 score of the
             kernel's own state durations is >= S64 - T 2^-23 A (the derivation stands there; S changes neither the number of terms
             along a path nor their bound).  And the result is a valid path."""
+import hashlib
 import math
+import os
 
 import numpy as np
 import pytest
@@ -28,6 +31,7 @@ OPT = 0
 PS = (1, 2, 15, 16, 17, 63, 64, 65)
 STATES = (1, 2, 3)
 VARIANTS = ("none", "inner", "first", "last")
+PARENT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "align_parent_outputs.npz")
 
 
 def _ids(g, P, variant):
@@ -52,9 +56,10 @@ def _items(S):
     return out
 
 
-def launch(S, L, ids, frames, threads=None, old=False):
-    """One launch of the Viterbi and the backtrack entry points (the 1-state ones with `old`) on L [V S, T_total] for utterances of
-    ids[n] tokens and frames[n] frames.  Every output on the host, with the offsets."""
+def launch(S, L, ids, frames, threads=None, state_durations=True, out=None):
+    """One launch of the Viterbi and the backtrack entry points on L [V S, T_total] for utterances of ids[n] tokens and frames[n]
+    frames; without `state_durations` the backtrack gets NULL for them.  Every output on the host, with the offsets.  out: a dict
+    that receives the outputs on the device before anything is called (for a call that raises)."""
     from kokoro_ruslan_amd import lib as kk
     from kokoro_ruslan_amd.align import code_words
     dev = "cuda"
@@ -67,21 +72,17 @@ def launch(S, L, ids, frames, threads=None, old=False):
     d = dict(L=L.to(dev).contiguous(), ids=tok.to(torch.int32).to(dev), opt=(tok == OPT).to(torch.uint8).to(dev),
              foff=foff.to(torch.int32).to(dev), poff=poff.to(torch.int32).to(dev), coff=coff.to(dev))
     threads = threads or (max(tokens) + 63) // 64 * 64
-    out = dict(score=torch.full((B,), 7.0, device=dev), end=torch.full((B,), 7, dtype=torch.int32, device=dev),
+    out = {} if out is None else out
+    out.update(score=torch.full((B,), 7.0, device=dev), end=torch.full((B,), 7, dtype=torch.int32, device=dev),
                codes=torch.zeros(int(coff[-1]), dtype=torch.int32, device=dev),
                durations=torch.full((int(poff[-1]),), 7, dtype=torch.int32, device=dev),
                label=torch.full((int(foff[-1]),), 7, dtype=torch.int32, device=dev))
-    if old:
-        assert S == 1
-        kk.call("kk_align_viterbi", d["L"], L.shape[1], d["ids"], d["opt"], d["foff"], d["poff"], d["coff"], B, threads, out["score"],
-                out["end"], out["codes"])
-        kk.call("kk_align_backtrack", out["codes"], d["coff"], d["foff"], d["poff"], d["ids"], out["end"], B, out["durations"], out["label"])
-    else:
+    if state_durations:
         out["state_durations"] = torch.full((int(poff[-1]), S), 7, dtype=torch.int32, device=dev)
-        kk.call("kk_align_viterbi_states", d["L"], L.shape[1], d["ids"], d["opt"], d["foff"], d["poff"], d["coff"], B, threads, S,
-                out["score"], out["end"], out["codes"])
-        kk.call("kk_align_backtrack_states", out["codes"], d["coff"], d["foff"], d["poff"], d["ids"], out["end"], B, S,
-                out["state_durations"], out["durations"], out["label"])
+    kk.call("kk_align_viterbi", d["L"], L.shape[1], d["ids"], d["opt"], d["foff"], d["poff"], d["coff"], B, threads, S, out["score"],
+            out["end"], out["codes"])
+    kk.call("kk_align_backtrack", out["codes"], d["coff"], d["foff"], d["poff"], d["ids"], out["end"], B, S, out.get("state_durations"),
+            out["durations"], out["label"])
     torch.cuda.synchronize()
     host = {k: v.cpu() for k, v in out.items()}
     host.update(foff=foff.tolist(), poff=poff.tolist(), coff=coff.tolist())
@@ -131,19 +132,54 @@ def _oracle(w, n, S):
     return r, L, i, sd64, pd64, S64
 
 
-def test_one_state_is_the_existing_kernels_bit_for_bit(world):
+def _sha256(x):
+    return hashlib.sha256(x.contiguous().numpy().tobytes()).hexdigest()
+
+
+def test_every_output_is_the_parent_commits_bit_for_bit(world):
+    """tests/golden/align_parent_outputs.npz was recorded on an MI355X at the commit it names ("commit"), the last one with a 1-state
+    kernel pair beside the S-state pair, by launching that commit's own entry points on this module's world(S, kind) inputs (a job
+    script that is not kept: it built the inputs as `world` does and called this module's launch() of that commit).  It holds, for
+    world(1, "random") (107 utterances, 4237 frames), L and the full outputs of the 1-state kk_align_viterbi / kk_align_backtrack, which
+    that commit's test proved equal to its S-state kernels' at S = 1; and for world(1, "exact") and both kinds at S = 2 and 3 the
+    SHA-256 of L and of every output of kk_align_viterbi_states / kk_align_backtrack_states."""
+    gold = np.load(PARENT)
+    print(f"recorded at {gold['commit']}")
     w = world(1, "random")
-    old = launch(1, w["L"], w["ids"], w["frames"], old=True)
-    new = w["run"]
-    assert new["coff"] == old["coff"]
+    assert same_bits(w["L"], torch.from_numpy(gold["L"])), "the regenerated L of world(1, 'random') is not the L the fixture was recorded on"
+    new = launch(1, torch.from_numpy(gold["L"]), w["ids"], w["frames"])
     for k in ("score", "end", "codes", "durations", "label"):
-        assert same_bits(new[k], old[k]), k
-    assert same_bits(new["state_durations"][:, 0], old["durations"])
+        assert same_bits(new[k], torch.from_numpy(gold[k])), k
+        assert same_bits(w["run"][k], new[k]), k
+    assert same_bits(new["state_durations"][:, 0], torch.from_numpy(gold["durations"]))
+    for S, kind in ((1, "exact"), (2, "random"), (2, "exact"), (3, "random"), (3, "exact")):
+        w = world(S, kind)
+        assert _sha256(w["L"]) == str(gold[f"sha256_{S}_{kind}_L"]), \
+            f"the regenerated L of world({S}, {kind!r}) is not the L the fixture was recorded on"
+        for k in ("score", "end", "codes", "state_durations", "durations", "label"):
+            assert _sha256(w["run"][k]) == str(gold[f"sha256_{S}_{kind}_{k}"]), (S, kind, k)
+    w, new = world(1, "random"), world(1, "random")["run"]
     skipped = sum(int(((pieces(new, n)["durations"] == 0) & (w["ids"][n] == OPT)).sum()) for n in range(len(w["items"])))
     first = sum(int(pieces(new, n)["durations"][0] == 0) for n, it in enumerate(w["items"]) if it[2] == "first")
     last = sum(int(pieces(new, n)["durations"][-1] == 0) for n, it in enumerate(w["items"]) if it[2] == "last")
     print(f"{len(w['items'])} items, {skipped} optional tokens skipped, {first} at position 0, {last} at position P - 1")
     assert skipped > 0 and first > 0 and last > 0
+
+
+def test_state_durations_may_be_null_with_one_state_only(world):
+    w = world(1, "exact")
+    bare = launch(1, w["L"], w["ids"], w["frames"], state_durations=False)
+    assert "state_durations" not in bare
+    for k in ("score", "end", "codes", "durations", "label"):
+        assert same_bits(bare[k], w["run"][k]), k
+    w = world(2, "exact")
+    refused = {}
+    with pytest.raises(RuntimeError, match="kk_align_backtrack: 2 states need state_durations"):
+        launch(2, w["L"], w["ids"], w["frames"], state_durations=False, out=refused)
+    torch.cuda.synchronize()
+    assert (refused["durations"] == 7).all() and (refused["label"] == 7).all()      # refused before any launch
+    for k in ("score", "end", "codes"):                                   # (the Viterbi launch had run)
+        assert same_bits(refused[k].cpu(), w["run"][k]), k
 
 
 @pytest.mark.parametrize("S", STATES)

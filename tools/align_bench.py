@@ -12,8 +12,9 @@ once per size on 16 utterances.  One JSON line at the end.
     python tools/align_bench.py [repeats=5] --states S
 
 With --states S (1, 2 or 3) the same two sizes are aligned with S states per phoneme instead: PhoneAligner(states=S).align as above, and
-the Viterbi launch alone (device events) -- kk_align_viterbi_states with S states on L [V S, T] beside the 1-state kk_align_viterbi on
-the same box and the same frames (on the maximum over each phoneme's states), interleaved inside every repeat; medians, with the spread."""
+the Viterbi and the backtrack launch alone (device events) -- kk_align_viterbi with S states on L [V S, T] beside the same entry point
+with 1 state on the same box and the same frames (on the maximum over each phoneme's states), interleaved inside every repeat; medians,
+with the spread."""
 import argparse
 import json
 import os
@@ -79,7 +80,7 @@ def device_ms(fn):
 
 
 def states_bench(S):
-    """--states S: the whole alignment with S states, and the S-state Viterbi launch beside the 1-state one."""
+    """--states S: the whole alignment with S states, and the S-state Viterbi and backtrack launches beside the 1-state Viterbi."""
     from kokoro_ruslan_amd import lib as kk
     from kokoro_ruslan_amd.align import code_words
     als = PhoneAligner(n_classes=V, states=S)
@@ -94,24 +95,33 @@ def states_bench(S):
         coff = {n: kk.packed_offsets([code_words(P, T, n)] * B).cuda() for n in {1, S}}
         codes = torch.empty(B * code_words(P, T, S), dtype=torch.int32, device="cuda")
         threads = (P + 63) // 64 * 64
+        sdur = torch.empty(B * P, S, dtype=torch.int32, device="cuda") if S > 1 else None
+        dur, label = torch.empty(B * P, dtype=torch.int32, device="cuda"), torch.empty(B * T, dtype=torch.int32, device="cuda")
         def many(Ls=Ls, run=run, opt=opt, coff=coff[S], threads=threads, score=score, end=end, codes=codes):
-            kk.call("kk_align_viterbi_states", Ls, Ls.shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, threads, S, score, end, codes)
+            kk.call("kk_align_viterbi", Ls, Ls.shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, threads, S, score, end, codes)
+
+        def back(run=run, coff=coff[S], end=end, codes=codes, sdur=sdur, dur=dur, label=label):      # (after many: its codes and end)
+            kk.call("kk_align_backtrack", codes, coff, run["foff"], run["poff"], run["ids"], end, B, S, sdur, dur, label)
 
         def one(L1=L1, run=run, opt=opt, coff=coff[1], threads=threads, score=score, end=end, codes=codes):
-            kk.call("kk_align_viterbi", L1, L1.shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, threads, score, end, codes)
-        many(), one()
-        todo.append(((P, T), mels, ids, model, many, one, {"align_s": [], "viterbi_states_ms": [], "viterbi_1state_ms": []}))
+            kk.call("kk_align_viterbi", L1, L1.shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, threads, 1, score, end, codes)
+        many(), back(), one()
+        todo.append(((P, T), mels, ids, model, many, back, one,
+                     {"align_s": [], "viterbi_states_ms": [], "backtrack_ms": [], "viterbi_1state_ms": []}))
     for _ in range(REPEATS):
-        for _, mels, ids, model, many, one, r in todo:
+        for _, mels, ids, model, many, back, one, r in todo:
             r["align_s"].append(timed(lambda: als.align(mels, ids, (), model))[1])   # (called at once: this pass's mels)
             r["viterbi_states_ms"].append(device_ms(many))
+            r["backtrack_ms"].append(device_ms(back))
             r["viterbi_1state_ms"].append(device_ms(one))
-    for (P, T), _, _, _, _, _, r in todo:
-        ta, tm, t1 = (statistics.median(r[k]) for k in ("align_s", "viterbi_states_ms", "viterbi_1state_ms"))
-        r.update(align_median_s=ta, utterances_per_s=B / ta, viterbi_states_median_ms=tm, viterbi_1state_median_ms=t1, ratio=tm / t1)
+    for (P, T), _, _, _, _, _, _, r in todo:
+        ta, tm, tb, t1 = (statistics.median(r[k]) for k in ("align_s", "viterbi_states_ms", "backtrack_ms", "viterbi_1state_ms"))
+        r.update(align_median_s=ta, utterances_per_s=B / ta, viterbi_states_median_ms=tm, backtrack_median_ms=tb, viterbi_1state_median_ms=t1,
+                 ratio=tm / t1)
         out["align"][f"{P}x{T}"] = r
         print(f"{P} x {T}, B = {B}, {S} state(s): align {ta * 1e3:8.2f} ms [{min(r['align_s']) * 1e3:.2f}, {max(r['align_s']) * 1e3:.2f}] = "
               f"{B / ta:8.0f} utterances/s | Viterbi launch {tm:.3f} ms [{min(r['viterbi_states_ms']):.3f}, {max(r['viterbi_states_ms']):.3f}] "
+              f"| backtrack launch {tb:.3f} ms [{min(r['backtrack_ms']):.3f}, {max(r['backtrack_ms']):.3f}] "
               f"| 1-state kernel {t1:.3f} ms [{min(r['viterbi_1state_ms']):.3f}, {max(r['viterbi_1state_ms']):.3f}] | x{tm / t1:.2f}")
     print(json.dumps(out))
 

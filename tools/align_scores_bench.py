@@ -66,8 +66,8 @@ def torch_scores(run):
 
 
 def viterbi_launch(run, pk_threads, opt, coff):
-    kk.call("kk_align_viterbi", run["L"], run["L"].shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, pk_threads, run["score"],
-            run["end"], run["codes"])
+    kk.call("kk_align_viterbi", run["L"], run["L"].shape[1], run["ids"], opt, run["foff"], run["poff"], coff, B, pk_threads, 1,
+            run["score"], run["end"], run["codes"])
 
 
 result = {"repeats": REPEATS, "sizes": {}}
