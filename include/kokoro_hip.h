@@ -660,6 +660,29 @@ int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *fo
  * fixed-order partial sums and a fixed tree (no atomics: two runs give the same bits) */
 int kk_align_accumulate(const float *feat, const int *label, int64_t T_total, int D, int V, int64_t *count, double *sum,
                         double *sumsq, void *stream);
+/* Gaussian mixtures: M in {1, 2, 4} components per class, G = C M <= 1024 Gaussians, Gaussian c M + m component m of class c; a, mu:
+ * [G][D], k: [G] = ln w - 1/2 sum_d ln(2 pi var), from the HOST (fp64, rounded once); D <= 64.  The entry points above stay as they are.
+ * frames per workgroup of kk_align_loglik_mix, kk_align_mix_labels and kk_align_accumulate_mix's counting passes */
+int kk_align_mix_frames(void);
+/* L[c][t] = mx + logf(sum over ascending m of expf(l_m - mx)), mx = max_m l_m, l_m = sum over ascending d of a[g][d] (feat[d][t] -
+ * mu[g][d])^2 (kk_align_loglik's fp32 fmaf chain) + k[g], g = c M + m.  The component values stay in registers: only L [C][T_total] is
+ * written.  A k of -inf drops its component (L is finite while one component of the class is); M = 1 gives kk_align_loglik's bits */
+int kk_align_loglik_mix(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu, const float *k,
+                        float *L, void *stream);
+/* mixlabel[t] = label[t] M + m*, m* the component of class label[t] with the largest l_m (the same device function, so the same bits,
+ * as in kk_align_loglik_mix; the lowest m on a tie); -1 where label[t] is outside 0..C-1.  Every element of mixlabel [T_total] is
+ * written */
+int kk_align_mix_labels(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu, const float *k,
+                        const int *label, int *mixlabel, void *stream);
+/* bytes of kk_align_accumulate_mix's workspace (0 for sizes it does not take) */
+int64_t kk_align_accumulate_mix_ws_bytes(int64_t T_total, int G);
+/* kk_align_accumulate for G <= 1024 Gaussians without a pass over the labels per Gaussian: a stable counting sort of the frame indices
+ * by mixlabel (counts per 256 frames, scans, a scatter in ascending t), then per Gaussian the fp64 sums over its own list by
+ * fixed-order partial sums and a fixed tree.  count [G], sum and sumsq [G][D]; labels outside 0..G-1 count nowhere; no floating-point
+ * atomics: two runs give the same bits.  ws: at least kk_align_accumulate_mix_ws_bytes(T_total, G) bytes, 4-byte aligned, private to
+ * the stream for the duration of the call */
+int kk_align_accumulate_mix(const float *feat, const int *mixlabel, int64_t T_total, int D, int G, int64_t *count, double *sum,
+                            double *sumsq, void *ws, int64_t ws_bytes, void *stream);
 /* pronunciation scores of an alignment (align_torch.scores), two launches.  Per frame t with class label[t] (scratch, all [T_total]):
  * amax = the lowest v with L[v][t] = fmax = max_v L[v][t]; margin = L[label][t] - fmax and lpost = margin - log sum_v exp(L[v][t] -
  * fmax) in fp64 (0 and 0 where label is outside 0..V-1).  Per token p with durations[p] frames ([P_total]): gop_sum and lpost_sum, the

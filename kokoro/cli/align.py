@@ -2,6 +2,7 @@
 
     kokoro-align --cache-dir DIR [--iters N] [--optional-id ID ...] [--batch-size N] [--var-floor F] [--mcep K] [--n-classes V]
                  [--model-in FILE | --model-out FILE] [--output FILE.jsonl] [--write-cache] [--scores [--worst N]] [--states S]
+                 [--mixtures M [--mix-iters N]]
 
 Reads the schema-v7 entries of a feature cache (mel_spec, phoneme_indices), fits one diagonal Gaussian per phoneme id by Viterbi
 training from the even split (kokoro_ruslan_amd.align.PhoneAligner.fit) -- or, with --model-in, loads a fitted model and only aligns --
@@ -22,6 +23,10 @@ phone, which is why 1 stays the default; a present optional silence needs >= S f
 neighbours).  With --model-in the file's value holds (a conflicting --states is named, exit status 1).  With S > 1 the --output lines
 gain "state_durations" ([P][S], rows summing to phoneme_durations; null where the utterance was not aligned); --write-cache writes the
 phone durations.
+--mixtures M (1, 2 or 4; default 1) gives every state a mixture of M diagonal Gaussians (n-classes x states x M <= 1024): the
+single-Gaussian training runs first as always, then every component is split in two and up to --mix-iters N passes (default 4) assign
+every frame to the best component of its state and re-estimate, once for 2 and again for 4; one closing alignment gives the durations.
+With --model-in the file's value holds (a conflicting --mixtures is named, exit status 1).  The output lines do not change.
 """
 from __future__ import annotations
 
@@ -55,6 +60,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--worst", type=int, default=argparse.SUPPRESS, metavar="N", help="with --scores: print the N utterances of lowest gop (default 10)")
     p.add_argument("--states", type=int, default=argparse.SUPPRESS, metavar="S",
                    help="states per phoneme, 1..3 (default 1; with --model-in the file's value)")
+    p.add_argument("--mixtures", type=int, default=argparse.SUPPRESS, metavar="M",
+                   help="Gaussians per state: 1, 2 or 4 (default 1; with --model-in the file's value)")
+    p.add_argument("--mix-iters", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="with --mixtures 2 or 4: passes after each doubling of the components (default 4)")
     return p
 
 
@@ -77,6 +86,15 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--worst must be >= 0")
     if not (1 <= getattr(args, "states", 1) <= 3):
         p.error("--states must be 1, 2 or 3")
+    if getattr(args, "mixtures", 1) not in (1, 2, 4):
+        p.error("--mixtures must be 1, 2 or 4")
+    if getattr(args, "mix_iters", 4) < 1:
+        p.error("--mix-iters must be >= 1")
+    if hasattr(args, "mix_iters") and (getattr(args, "mixtures", 1) == 1 or args.model_in):
+        p.error("--mix-iters needs --mixtures 2 or 4 and a fit: not with --model-in")
+    if args.n_classes * getattr(args, "states", 1) * getattr(args, "mixtures", 1) > 1024:
+        p.error(f"--n-classes {args.n_classes} x --states {getattr(args, 'states', 1)} x --mixtures {getattr(args, 'mixtures', 1)} = "
+                f"{args.n_classes * getattr(args, 'states', 1) * getattr(args, 'mixtures', 1)} Gaussians; at most 1024")
     if args.n_classes * getattr(args, "states", 1) > 256:
         p.error(f"--n-classes {args.n_classes} x --states {args.states} = {args.n_classes * args.states} Gaussians; at most 256")
 
@@ -112,8 +130,13 @@ def main(argv=None) -> int:
     import torch
     from kokoro_ruslan_amd import align as A
 
-    S = getattr(args, "states", 1)
+    S, M = getattr(args, "states", 1), getattr(args, "mixtures", 1)
     if args.model_in:
+        M = A.PhoneAligner.file_mixtures(args.model_in)
+        if getattr(args, "mixtures", M) != M:
+            print(f"kokoro-align: --mixtures {args.mixtures}, but {args.model_in} is a model of mixtures = {M}: leave --mixtures out, or fit "
+                  "another model", file=sys.stderr)
+            return 1
         S = A.PhoneAligner.file_states(args.model_in)
         if getattr(args, "states", S) != S:
             print(f"kokoro-align: --states {args.states}, but {args.model_in} is a model of states = {S}: leave --states out, or fit another "
@@ -122,7 +145,8 @@ def main(argv=None) -> int:
         if args.n_classes * S > 256:
             p.error(f"{args.model_in}: states = {S}; --n-classes {args.n_classes} x {S} Gaussians are more than 256")
     entries = read_cache(args.cache_dir)
-    al = A.PhoneAligner(K=args.mcep, n_classes=args.n_classes, var_floor=args.var_floor, **({"states": S} if S > 1 else {}))
+    al = A.PhoneAligner(K=args.mcep, n_classes=args.n_classes, var_floor=args.var_floor, **({"states": S} if S > 1 else {}),
+                        **({"mixtures": M} if M > 1 else {}))
     limit = A.max_tokens()
     failed = 0
     todo = []
@@ -151,7 +175,8 @@ def main(argv=None) -> int:
         sdurs = [r["state_durations"] for r in recs] if S > 1 else None
         score = sum(r["score"] for r in recs if r["feasible"])
     else:
-        model, durs, scores = al.fit(mels, ids, args.optional_id, iters=args.iters, batch_size=args.batch_size)
+        model, durs, scores = al.fit(mels, ids, args.optional_id, iters=args.iters, batch_size=args.batch_size,
+                                     **({"mix_iters": args.mix_iters} if hasattr(args, "mix_iters") else {}))
         how, score, sdurs = f"{len(scores)} passes", scores[-1], al.state_durations
         if args.model_out:
             al.save(model, args.model_out)

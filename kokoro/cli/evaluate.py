@@ -7,7 +7,7 @@
                 [--vocoder PATH [--vocoder-config JSON] [--vocoder-math bf16|f32] [--denoise [S]]]
                 [--griffin-lim [--griffin-lim-iters N] [--griffin-lim-seed S]] [--gpe-ratio F]
                 [--wavs DIR [--copy-synthesis]]
-                [--pronunciation [MODEL] [--align-iters N] [--align-states S] [--optional-id ID ...] [--pronunciation-tokens]]
+                [--pronunciation [MODEL] [--align-iters N] [--align-states S] [--align-mixtures M] [--optional-id ID ...] [--pronunciation-tokens]]
 
 Synthesizes every selected utterance with the stop rule deciding its length (continuous batching in a pool of --slots rows, or with
 --no-stream in batches of --batch-size), aligns each mel with the cached ground truth by dynamic time warping on K mel cepstra and
@@ -50,7 +50,8 @@ ref_logpost, ref_phone_acc (the recording) and gop_gap, phone_acc_gap (synthesis
 aligned has null there and is counted.  The model was fitted on recordings, so the recording's score is the ceiling: read the gap.
 --pronunciation-tokens adds the per-token lists (pron_tokens, ref_pron_tokens) to the records of --output.  A MODEL of 2 or 3 states
 per phoneme (kokoro-align --states) is taken as it is; --align-states S gives the model fitted here that many (default 1).  A frame's
-phoneme likelihood is then that of the phoneme's best state."""
+phoneme likelihood is then that of the phoneme's best state.  A MODEL of 2 or 4 Gaussians per state (kokoro-align --mixtures) is taken as
+it is too; --align-mixtures M gives the model fitted here that many (default 1)."""
 from __future__ import annotations
 
 import argparse
@@ -104,6 +105,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="passes of Viterbi training when --pronunciation fits its model (default 6)")
     p.add_argument("--align-states", type=int, default=argparse.SUPPRESS, metavar="S",
                    help="states per phoneme (1..3, default 1) of the model --pronunciation fits")
+    p.add_argument("--align-mixtures", type=int, default=argparse.SUPPRESS, metavar="M",
+                   help="Gaussians per state (1, 2 or 4, default 1) of the model --pronunciation fits")
     p.add_argument("--optional-id", type=int, action="append", default=argparse.SUPPRESS, metavar="ID",
                    help="a phoneme id whose tokens may get no frame (with --pronunciation; may be repeated)")
     p.add_argument("--pronunciation-tokens", action="store_true", default=argparse.SUPPRESS,
@@ -156,7 +159,7 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
     elif args.checkpoint is None:
         p.error("the following arguments are required: --checkpoint")
     if not hasattr(args, "pronunciation"):
-        for flag in ("align_iters", "align_states", "optional_id", "pronunciation_tokens"):
+        for flag in ("align_iters", "align_states", "align_mixtures", "optional_id", "pronunciation_tokens"):
             if hasattr(args, flag):
                 p.error(f"--{flag.replace('_', '-')} needs --pronunciation")
         return
@@ -170,6 +173,10 @@ def check_args(p: argparse.ArgumentParser, args) -> None:
         p.error("--align-states is for fitting a model: not with --pronunciation MODEL (the file's states hold)")
     if not (1 <= getattr(args, "align_states", 1) <= 3):
         p.error("--align-states must be 1, 2 or 3")
+    if hasattr(args, "align_mixtures") and args.pronunciation:
+        p.error("--align-mixtures is for fitting a model: not with --pronunciation MODEL (the file's mixtures hold)")
+    if getattr(args, "align_mixtures", 1) not in (1, 2, 4):
+        p.error("--align-mixtures must be 1, 2 or 4")
     if any(o < 0 for o in getattr(args, "optional_id", [])):
         p.error("--optional-id must be a phoneme id >= 0")
 
@@ -283,7 +290,8 @@ def phone_scoring(args, device, n_classes: int, mels, ids):
     if any(o >= n_classes for o in opt):
         raise ValueError(f"--optional-id must be a phoneme id below the checkpoint's {n_classes}")
     S = PhoneAligner.file_states(args.pronunciation) if args.pronunciation else getattr(args, "align_states", 1)
-    al = PhoneAligner(device=device, n_classes=n_classes, **({"states": S} if S > 1 else {}))
+    M = PhoneAligner.file_mixtures(args.pronunciation) if args.pronunciation else getattr(args, "align_mixtures", 1)
+    al = PhoneAligner(device=device, n_classes=n_classes, **({"states": S} if S > 1 else {}), **({"mixtures": M} if M > 1 else {}))
     if args.pronunciation:
         model, how = al.load(args.pronunciation), f"model {args.pronunciation}"
     else:

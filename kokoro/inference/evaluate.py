@@ -76,7 +76,7 @@ def _pron_records(phone_aligner, phone_model, optional_ids, device, mels, ref_me
     if phone_aligner is None:
         from kokoro_ruslan_amd.align import PhoneAligner
         phone_aligner = PhoneAligner(device=device, K=int(phone_model["K"]), n_classes=int(phone_model["n_classes"]),
-                                     states=int(phone_model.get("states", 1)))
+                                     states=int(phone_model.get("states", 1)), mixtures=int(phone_model.get("mixtures", 1)))
     syn = phone_aligner.score(list(mels), list(ids), optional_ids, phone_model)
     ref = phone_aligner.score(list(ref_mels), list(ids), optional_ids, phone_model)
     out = []

@@ -9,6 +9,11 @@ accuracy, per token and per utterance).  align_torch is the fp64 oracle of every
 
 `PhoneAligner(states=S)`, S = 2 or 3, gives every phoneme a left-to-right chain of S states, each with its own Gaussian (class v S + j):
 a token that has frames has at least S, one per state.  Everything follows the aligner's `states`; 1 is the default and changes nothing.
+
+`PhoneAligner(mixtures=M)`, M = 2 or 4, gives every class (state) a mixture of M diagonal Gaussians, Gaussian c M + m component m of
+class c, with weights [C, M]: L(c, t) is the log of the weighted sum of its components (kk_align_loglik_mix).  `fit` trains the single
+Gaussians as always, then mixes up: split every component in two, a few passes that assign every frame to the best component of its
+class, double again.  Alignment and scores see only L [C, T]; 1 is the default and changes nothing.
 """
 from __future__ import annotations
 
@@ -18,7 +23,7 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import torch
 
 from kokoro_ruslan_amd import lib as kk
-from kokoro_ruslan_amd.align_torch import VAR_MIN, even_split
+from kokoro_ruslan_amd.align_torch import SPLIT, VAR_MIN, even_split
 from kokoro_ruslan_amd.dtw_torch import dct_table
 
 MAX_FRAMES = 4096                        # the longest utterance the kernels take (the positional table's order)
@@ -26,11 +31,18 @@ MAX_MEL = 128                            # kk_mcep stages 64 frames of at most t
 MAX_CLASSES = 256                        # kk_align_loglik
 MAX_DIM = 64
 MAX_STATES = 3                           # kk_align_viterbi
+MIXTURES = (1, 2, 4)                     # components per class: kk_align_loglik_mix
+MAX_GAUSSIANS = 1024                     # classes x components
 
 
 def max_tokens() -> int:
     """Tokens of an utterance the Viterbi kernel takes: the size of its workgroup."""
     return int(kk.load().kk_align_max_tokens())
+
+
+def mix_frames() -> int:
+    """Frames per workgroup of the mixture kernels."""
+    return int(kk.load().kk_align_mix_frames())
 
 
 def code_words(P: int, T: int, S: int = 1) -> int:
@@ -50,7 +62,8 @@ def flat_start(ids: torch.Tensor, d: torch.Tensor, S: int):
 class PhoneAligner:
     """Batched Viterbi alignment and Viterbi training on the MI355X."""
 
-    def __init__(self, device: str = "cuda", K: int = 13, n_classes: int = 59, var_floor: float = 0.01, states: int = 1):
+    def __init__(self, device: str = "cuda", K: int = 13, n_classes: int = 59, var_floor: float = 0.01, states: int = 1,
+                 mixtures: int = 1):
         if int(K) != K or not (0 <= K <= MAX_DIM // 2 - 1):
             raise ValueError(f"K must be an integer in 0..{MAX_DIM // 2 - 1}, not {K!r}")
         if int(n_classes) != n_classes or not (1 <= n_classes <= MAX_CLASSES):
@@ -59,10 +72,15 @@ class PhoneAligner:
             raise ValueError(f"var_floor must be in [0, 1), not {var_floor!r}")
         if int(states) != states or not (1 <= states <= MAX_STATES):
             raise ValueError(f"states must be an integer in 1..{MAX_STATES}, not {states!r}")
+        if mixtures not in MIXTURES:
+            raise ValueError(f"mixtures must be 1, 2 or 4, not {mixtures!r}")
+        if n_classes * states * mixtures > MAX_GAUSSIANS:
+            raise ValueError(f"{n_classes} phoneme ids of {states} states and {mixtures} components are {n_classes * states * mixtures} "
+                             f"Gaussians; at most {MAX_GAUSSIANS}")
         if n_classes * states > MAX_CLASSES:
             raise ValueError(f"{n_classes} phoneme ids of {states} states are {n_classes * states} classes; at most {MAX_CLASSES}")
         self.device, self.K, self.n_classes, self.var_floor = torch.device(device), int(K), int(n_classes), float(var_floor)
-        self.states = int(states)
+        self.states, self.mixtures = int(states), int(mixtures)
         self.state_durations: Optional[List[Optional[torch.Tensor]]] = None      # of the last fit(), when states > 1
         self._tables: Dict[int, torch.Tensor] = {}
 
@@ -72,8 +90,13 @@ class PhoneAligner:
 
     @property
     def classes(self) -> int:
-        """Gaussians of the model: `states` per phoneme id, class v states + j."""
+        """Classes of the model: `states` per phoneme id, class v states + j."""
         return self.n_classes * self.states
+
+    @property
+    def gaussians(self) -> int:
+        """Gaussians of the model: `mixtures` per class, Gaussian c mixtures + m."""
+        return self.classes * self.mixtures
 
     # ---- guards: everything is checked before anything is launched --------------------------------------------------------------
     def _check(self, mels, ids, feats) -> None:
@@ -108,9 +131,13 @@ class PhoneAligner:
     def _check_model(self, model: Dict, D: int) -> None:
         if int(model.get("states", 1)) != self.states:
             raise ValueError(f"the model has states = {int(model.get('states', 1))}; this aligner has states = {self.states}")
+        if int(model.get("mixtures", 1)) != self.mixtures:
+            raise ValueError(f"the model has mixtures = {int(model.get('mixtures', 1))}; this aligner has mixtures = {self.mixtures}")
         for k in ("mean", "var"):
-            if tuple(model[k].shape) != (self.classes, D):
-                raise ValueError(f"the model's {k} is {tuple(model[k].shape)}; this aligner and these features need ({self.classes}, {D})")
+            if tuple(model[k].shape) != (self.gaussians, D):
+                raise ValueError(f"the model's {k} is {tuple(model[k].shape)}; this aligner and these features need ({self.gaussians}, {D})")
+        if self.mixtures > 1 and tuple(model["weight"].shape) != (self.classes, self.mixtures):
+            raise ValueError(f"the model's weight is {tuple(model['weight'].shape)}; this aligner needs ({self.classes}, {self.mixtures})")
 
     # ---- pieces ------------------------------------------------------------------------------------------------------------------
     def table(self, M: int) -> torch.Tensor:
@@ -136,9 +163,12 @@ class PhoneAligner:
         return self._features_packed(x, foff, len(mels))
 
     def params(self, model: Dict):
-        """(a = -1/2 / var, mu, c = -1/2 sum ln(2 pi var)) as the device takes them: evaluated in fp64, rounded once."""
+        """(a = -1/2 / var, mu, c = -1/2 sum ln(2 pi var)) as the device takes them: evaluated in fp64, rounded once.  A mixture model
+        has these per Gaussian [G], and c is k = ln w + c (a weight of 0 gives -inf: the component is dropped)."""
         mean, var = model["mean"].to(torch.float64), model["var"].to(torch.float64)
         a, c = -0.5 / var, -0.5 * (math.log(2.0 * math.pi) + var.log()).sum(1)
+        if "weight" in model:
+            c = model["weight"].to(c.device, torch.float64).log().reshape(-1) + c
         return tuple(t.to(torch.float32).to(self.device).contiguous() for t in (a, mean, c))
 
     def loglik(self, feat: torch.Tensor, model: Dict) -> torch.Tensor:
@@ -147,8 +177,30 @@ class PhoneAligner:
         self._check_model(model, D)
         a, mu, c = self.params(model)
         L = torch.empty(self.classes, T, dtype=torch.float32, device=self.device)
-        kk.call("kk_align_loglik", feat, T, D, self.classes, a, mu, c, L)
+        if self.mixtures > 1:
+            kk.call("kk_align_loglik_mix", feat, T, D, self.classes, self.mixtures, a, mu, c, L)
+        else:
+            kk.call("kk_align_loglik", feat, T, D, self.classes, a, mu, c, L)
         return L
+
+    def mix_labels(self, feat: torch.Tensor, model: Dict, label: torch.Tensor) -> torch.Tensor:
+        """int32 [T_total]: label[t] M + the best component of class label[t] at frame t (the lowest on a tie), -1 where label is."""
+        D, T = feat.shape
+        self._check_model(model, D)
+        a, mu, k = self.params(model)
+        out = torch.empty(T, dtype=torch.int32, device=self.device)
+        kk.call("kk_align_mix_labels", feat, T, D, self.classes, self.mixtures, a, mu, k, label, out)
+        return out
+
+    def accumulate_mix(self, feat: torch.Tensor, mixlabel: torch.Tensor, G: Optional[int] = None):
+        """accumulate() over G Gaussians (default: this aligner's) by a counting sort of the frames: (count [G], sum x, sum x^2 [G, D])."""
+        D, T = feat.shape
+        G = self.gaussians if G is None else int(G)
+        count = torch.empty(G, dtype=torch.int64, device=self.device)
+        sums = torch.empty(2, G, D, dtype=torch.float64, device=self.device)
+        ws = torch.empty(max(int(kk.load().kk_align_accumulate_mix_ws_bytes(T, G)), 4), dtype=torch.uint8, device=self.device)
+        kk.call("kk_align_accumulate_mix", feat, mixlabel, T, D, G, count, sums[0], sums[1], ws, ws.numel())
+        return count, sums[0], sums[1]
 
     def accumulate(self, feat: torch.Tensor, label: torch.Tensor):
         """(count int64 [V], sum x fp64 [V, D], sum x^2 fp64 [V, D]) of packed features [D, T_total] under frame labels int32 [T_total]."""
@@ -172,6 +224,46 @@ class PhoneAligner:
         mean, var = torch.where(few, gmean, mean), torch.where(few, gvar, var)
         var = torch.maximum(torch.maximum(var, self.var_floor * gvar), torch.full_like(var, VAR_MIN))
         return self._tag({"mean": mean, "var": var, "K": self.K, "n_classes": self.n_classes})
+
+    def split(self, model: Dict) -> Dict:
+        """M -> 2 M (align_torch.split_mixtures): component m becomes 2 m at mu - SPLIT sqrt(var) and 2 m + 1 at mu + SPLIT sqrt(var),
+        the variance copied, the weight halved.  The aligner's `mixtures` is not consulted: fit() walks 1 -> 2 -> 4 with it."""
+        mu, var = model["mean"].to(torch.float64), model["var"].to(torch.float64)
+        w = model["weight"].to(mu.device, torch.float64) if "weight" in model else torch.ones(mu.shape[0], 1, dtype=torch.float64, device=mu.device)
+        step = SPLIT * var.sqrt()
+        out = {"mean": torch.stack([mu - step, mu + step], 1).reshape(2 * mu.shape[0], -1), "var": var.repeat_interleave(2, 0),
+               "weight": (w / 2.0).repeat_interleave(2, 1), "K": self.K, "n_classes": self.n_classes}
+        if self.states > 1:
+            out["states"] = self.states
+        out["mixtures"] = 2 * int(model.get("mixtures", 1))
+        return out
+
+    def estimate_mix(self, count: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, M: int) -> Dict:
+        """The mixture model of the Gaussians' statistics (align_torch.model_from_mix_stats, in fp64 torch)."""
+        G, D = s1.shape
+        C = G // M
+        n = count.to(torch.float64)
+        N = n.sum().clamp(min=1.0)
+        gmean = s1.sum(0) / N
+        gvar = (s2.sum(0) / N - gmean ** 2).clamp(min=0.0)
+        nc = n.view(C, M).sum(1)
+        safe = nc.clamp(min=1.0)[:, None]
+        cmean = s1.view(C, M, D).sum(1) / safe
+        cvar = (s2.view(C, M, D).sum(1) / safe - cmean ** 2).clamp(min=0.0)
+        lone = (nc < 2)[:, None]
+        cmean, cvar = torch.where(lone, gmean, cmean).repeat_interleave(M, 0), torch.where(lone, gvar, cvar).repeat_interleave(M, 0)
+        safe = n.clamp(min=1.0)[:, None]
+        mean = s1 / safe
+        var = s2 / safe - mean ** 2
+        sign = torch.where(torch.arange(G, device=s1.device) % 2 == 0, -1.0, 1.0).to(torch.float64)[:, None]
+        few = (n < 2)[:, None]
+        mean, var = torch.where(few, cmean + sign * SPLIT * cvar.sqrt(), mean), torch.where(few, cvar, var)
+        var = torch.maximum(torch.maximum(var, self.var_floor * gvar), torch.full_like(var, VAR_MIN))
+        out = {"mean": mean, "var": var, "weight": (n.view(C, M) + 1.0) / (nc[:, None] + M), "K": self.K, "n_classes": self.n_classes}
+        if self.states > 1:
+            out["states"] = self.states
+        out["mixtures"] = int(M)
+        return out
 
     def _tag(self, model: Dict) -> Dict:
         """A multi-state model says so; a 1-state model stays the dictionary it always was."""
@@ -343,14 +435,22 @@ class PhoneAligner:
         return out
 
     def fit(self, mels: Optional[Sequence[torch.Tensor]], ids: Sequence[torch.Tensor], optional_ids: Iterable[int] = (), iters: int = 6,
-            batch_size: int = 64, feats: Optional[Sequence[torch.Tensor]] = None):
+            batch_size: int = 64, feats: Optional[Sequence[torch.Tensor]] = None, mix_iters: int = 4, on_mix_pass=None):
         """Viterbi training from the even split: `iters` passes of estimate -> align over the corpus in batches of batch_size, the
         class statistics accumulated batch by batch in that order; stops once no duration changes.  Returns (model, durations: list of
         LongTensor [P] | None, scores: the corpus score of each pass).  With states = S > 1 the flat start spreads every token's frames
         of the even split evenly over its S states (flat_start), the passes stop once no STATE duration changes, and the
-        state durations of the last pass are in `self.state_durations` (list of LongTensor [P, S] | None)."""
+        state durations of the last pass are in `self.state_durations` (list of LongTensor [P, S] | None).
+        With mixtures = M > 1 that training runs first, all of it, with one Gaussian per class; then, for each doubling 1 -> 2 (-> 4),
+        every component is split in two (split) and up to mix_iters passes follow, each: align with the current model, assign every
+        frame to a component of its class (mix_labels), accumulate batch by batch, estimate (estimate_mix).  A doubling's passes stop
+        once no state duration and no count changes.  One closing alignment with the last estimate gives the durations returned, so
+        that they are the model's own; `scores` gains one entry per mixture alignment, the closing one included.  on_mix_pass(model,
+        runs), if given, is called with every mixture alignment's model and its batches' run_packed() results."""
         if int(iters) != iters or iters < 1:
             raise ValueError(f"iters must be an integer >= 1, not {iters!r}")
+        if int(mix_iters) != mix_iters or mix_iters < 1:
+            raise ValueError(f"mix_iters must be an integer >= 1, not {mix_iters!r}")
         if int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size must be an integer >= 1, not {batch_size!r}")
         self._check(mels, ids, feats)
@@ -360,6 +460,66 @@ class PhoneAligner:
             e = s + batch_size
             packs.append(self._pack(None if feats is not None else x[s:e], ids[s:e], optional_ids, None if feats is None else x[s:e]))
         flat = [torch.from_numpy(even_split(int(t.shape[0]), int(m.shape[0]))) for m, t in zip(x, ids)]
+        if self.mixtures > 1:
+            return self._fit_mix(packs, flat, int(iters), int(mix_iters), on_mix_pass)
+        return self._fit_single(packs, flat, int(iters))
+
+    def _stage(self, mixtures: int) -> "PhoneAligner":
+        """This aligner with another number of components (fit's stages 1 -> 2 -> 4), on the same tables."""
+        if mixtures == self.mixtures:
+            return self
+        al = PhoneAligner(self.device, self.K, self.n_classes, self.var_floor, self.states, mixtures)
+        al._tables = self._tables
+        return al
+
+    @staticmethod
+    def _same(old, new) -> bool:
+        return all((d is None and e is None) or (d is not None and e is not None and torch.equal(d.reshape(-1), e.reshape(-1)))
+                   for d, e in zip(old, new))
+
+    def _align_corpus(self, packs, model):
+        """One alignment of every batch: (runs, the frame labels per batch, what has to stop changing per utterance, the phone
+        durations per utterance, the corpus score)."""
+        runs, new, phone, total = [], [], [], 0.0
+        for pk in packs:
+            runs.append(self._align_packed(pk, model))
+            for r in self._records(runs[-1]):
+                new.append(r.get("state_durations", r["durations"]))
+                phone.append(r["durations"])
+                total += r["score"] if r["feasible"] else 0.0
+        return runs, [r["label"] for r in runs], new, phone, total
+
+    def _fit_mix(self, packs, flat, iters: int, mix_iters: int, on_mix_pass):
+        model, _, scores = self._stage(1)._fit_single(packs, flat, iters)
+        durs = phone = None
+        m = 1
+        while m < self.mixtures:
+            m *= 2
+            al = self._stage(m)
+            model, counts = al.split(model), None
+            for _ in range(mix_iters):
+                runs, labels, new, phone, total = al._align_corpus(packs, model)
+                scores.append(total)
+                if on_mix_pass is not None:
+                    on_mix_pass(model, runs)
+                stats = None
+                for pk, lab in zip(packs, labels):
+                    part = al.accumulate_mix(pk["feat"], al.mix_labels(pk["feat"], model, lab))
+                    stats = part if stats is None else tuple(a + b for a, b in zip(stats, part))
+                model = al.estimate_mix(*stats, m)
+                n = stats[0].cpu()
+                same = counts is not None and durs is not None and torch.equal(n, counts) and self._same(durs, new)
+                durs, counts = new, n
+                if same:
+                    break
+        runs, _, durs, phone, total = self._align_corpus(packs, model)
+        scores.append(total)
+        if on_mix_pass is not None:
+            on_mix_pass(model, runs)
+        self.state_durations = durs if self.states > 1 else None
+        return model, phone, scores
+
+    def _fit_single(self, packs, flat, iters: int):
         S, labels, n = self.states, [], 0
         durs: List[Optional[torch.Tensor]] = []                                   # state durations [P, S]
         for pk in packs:
@@ -394,16 +554,27 @@ class PhoneAligner:
 
     # ---- the model on disk -------------------------------------------------------------------------------------------------------
     def save(self, model: Dict, path: str) -> None:
-        """A multi-state model's file also has "states"; a 1-state model's file stays what it was (a file without the field is S = 1)."""
+        """A multi-state model's file also has "states"; a 1-state model's file stays what it was (a file without the field is S = 1).
+        The same holds for "mixtures", with which "weight" [C, M] comes."""
         if int(model.get("states", 1)) != self.states:
             raise ValueError(f"the model has states = {int(model.get('states', 1))}; this aligner has states = {self.states}")
-        torch.save(self._tag({"mean": model["mean"].detach().to("cpu", torch.float64), "var": model["var"].detach().to("cpu", torch.float64),
-                              "K": self.K, "n_classes": self.n_classes}), path)
+        if int(model.get("mixtures", 1)) != self.mixtures:
+            raise ValueError(f"the model has mixtures = {int(model.get('mixtures', 1))}; this aligner has mixtures = {self.mixtures}")
+        out = self._tag({"mean": model["mean"].detach().to("cpu", torch.float64), "var": model["var"].detach().to("cpu", torch.float64),
+                         "K": self.K, "n_classes": self.n_classes})
+        if self.mixtures > 1:
+            out.update(weight=model["weight"].detach().to("cpu", torch.float64), mixtures=self.mixtures)
+        torch.save(out, path)
 
     @staticmethod
     def file_states(path: str) -> int:
         """The states per phoneme of a saved model: 1 for a file without the field."""
         return int(torch.load(path, map_location="cpu", weights_only=True).get("states", 1))
+
+    @staticmethod
+    def file_mixtures(path: str) -> int:
+        """The components per class of a saved model: 1 for a file without the field."""
+        return int(torch.load(path, map_location="cpu", weights_only=True).get("mixtures", 1))
 
     def load(self, path: str) -> Dict:
         m = torch.load(path, map_location="cpu", weights_only=True)
@@ -413,6 +584,18 @@ class PhoneAligner:
         S = int(m.get("states", 1))
         if S != self.states:
             raise ValueError(f"{path}: a model of states = {S}; this aligner has states = {self.states}")
+        M = int(m.get("mixtures", 1))
+        if M != self.mixtures:
+            raise ValueError(f"{path}: a model of mixtures = {M}; this aligner has mixtures = {self.mixtures}")
+        if M > 1:
+            if tuple(m["mean"].shape[:1]) != (self.gaussians,) or tuple(m["var"].shape[:1]) != (self.gaussians,) or \
+                    tuple(m["weight"].shape) != (self.classes, M):
+                raise ValueError(f"{path}: a model of {int(m['mean'].shape[0])} Gaussians and weights {tuple(m['weight'].shape)}; "
+                                 f"{self.n_classes} classes of {S} states and {M} components need {self.gaussians} and ({self.classes}, {M})")
+            out = self._tag({"mean": m["mean"].to(self.device), "var": m["var"].to(self.device), "weight": m["weight"].to(self.device),
+                             "K": self.K, "n_classes": self.n_classes})
+            out["mixtures"] = M
+            return out
         if tuple(m["mean"].shape[:1]) != (self.classes,) or tuple(m["var"].shape[:1]) != (self.classes,):
             raise ValueError(f"{path}: a model of {int(m['mean'].shape[0])} Gaussians; {self.n_classes} classes of {S} states need {self.classes}")
         return self._tag({"mean": m["mean"].to(self.device), "var": m["var"].to(self.device), "K": self.K, "n_classes": self.n_classes})

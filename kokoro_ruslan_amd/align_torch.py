@@ -392,3 +392,176 @@ def synthetic_corpus_parts(seed: int, parts: int = 2, optional: bool = False, n_
         feats.append((means.reshape(V * parts, D)[lab] + g.normal(0.0, noise, (lab.shape[0], D))).astype(np.float32))
         ids.append(i.astype(np.int64)), opts.append(o), durs.append(d.astype(np.int64)), sdurs.append(sd)
     return feats, ids, opts, durs, means, sdurs
+
+
+# ---- Gaussian mixtures per state: M = 2 or 4 diagonal components per class (DESIGN §5 "Forced alignment", "Mixtures") -----------------
+# C = V S classes as above, G = C M Gaussians: Gaussian c M + m is component m of class c.  A model is {"mean", "var"} [G, D],
+# "weight" [C, M] (rows summing to 1) and "mixtures": M, plus "states" as above; a model without "mixtures" is M = 1.
+#     l_m(t) = sum over ascending d of a[g][d] (x_d - mu[g][d])^2, plus k[g], k[g] = ln w_cm - 1/2 sum_d ln(2 pi var)
+#     L(c, t) = mx + log sum over ascending m of exp(l_m - mx), mx = max_m l_m
+# Training assigns every frame to ONE component of its class (the largest l_m, the lowest m on a tie), as Viterbi training assigns
+# it to one class.
+
+SPLIT = 0.2                                                                     # a split moves the two children by -/+ SPLIT sqrt(var)
+
+
+def mixtures_of(model: Dict) -> int:
+    return int(model.get("mixtures", 1))
+
+
+def loglik_mix_params(model: Dict) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a [G, D], mu [G, D], k [G] = ln w - 1/2 sum_d ln(2 pi var)) in fp64; without "weight" (M = 1) k is loglik_params' c."""
+    a, mu, c = loglik_params(model)
+    if "weight" not in model:
+        return a, mu, c
+    with np.errstate(divide="ignore"):
+        return a, mu, np.log(_f64(model["weight"])).reshape(-1) + c
+
+
+def mix_components(feats, a, mu, k) -> np.ndarray:
+    """l [G, T]: every component's value, weight included."""
+    return loglik_from_params(feats, a, mu, k)
+
+
+def loglik_mix_from_params(feats, a, mu, k, M: int) -> np.ndarray:
+    """L [C, T] of features [T, D] from the G = C M components' parameters.  A class needs one finite component at least."""
+    l = mix_components(feats, a, mu, k)
+    if int(M) == 1:
+        return l
+    l = l.reshape(l.shape[0] // int(M), int(M), l.shape[1])
+    mx = l.max(1)
+    s = np.zeros_like(mx)
+    for m in range(int(M)):                                                     # ascending m
+        s = s + np.exp(l[:, m] - mx)
+    return mx + np.log(s)
+
+
+def loglik_mix(feats, model: Dict) -> np.ndarray:
+    return loglik_mix_from_params(feats, *loglik_mix_params(model), mixtures_of(model))
+
+
+def mix_labels_from_params(feats, labels, a, mu, k, M: int) -> np.ndarray:
+    """[T]: label M + the component of the frame's class `label` with the largest value (the lowest on a tie); -1 where label < 0."""
+    M, lab = int(M), np.asarray(labels, dtype=np.int64)
+    l = mix_components(feats, a, mu, k)
+    l = l.reshape(l.shape[0] // M, M, l.shape[1])
+    t = np.arange(lab.shape[0])
+    best = l[np.maximum(lab, 0), :, t].argmax(1)                                # (argmax: the first, so the lowest, maximiser)
+    return np.where(lab >= 0, lab * M + best, -1)
+
+
+def split_mixtures(model: Dict) -> Dict:
+    """M -> 2 M: component m of a class becomes 2 m at mu - SPLIT sqrt(var) and 2 m + 1 at mu + SPLIT sqrt(var), each with the
+    variance copied and half the weight.  A model without "weight" is M = 1 with weight 1."""
+    mu, var = _f64(model["mean"]), _f64(model["var"])
+    M = mixtures_of(model)
+    w = _f64(model["weight"]) if "weight" in model else np.ones((mu.shape[0], 1))
+    step = SPLIT * np.sqrt(var)
+    out = {k: v for k, v in model.items() if k not in ("mean", "var", "weight", "mixtures")}
+    out.update(mean=np.stack([mu - step, mu + step], 1).reshape(2 * mu.shape[0], -1), var=np.repeat(var, 2, 0),
+               weight=np.repeat(w / 2.0, 2, 1), mixtures=2 * M)
+    return out
+
+
+def model_from_mix_stats(n, s1, s2, M: int, var_floor: float = 0.01) -> Dict:
+    """{"mean", "var" [G, D], "weight" [C, M], "mixtures"} from the Gaussians' statistics n [G], s1, s2 [G, D].
+    weight: w_cm = (n_cm + 1) / (n_c + M), strictly positive.  A class's pooled mean and variance come from the sums over its
+    components, or, with n_c < 2, from the global ones.  A component with n_cm < 2 is seeded again from its class's pooled statistics
+    where its index stood at the split that made it: the pooled mean - SPLIT sqrt(pooled var) for an even m, + for an odd one, with the
+    pooled variance.  Every variance is floored at var_floor times the global variance and at VAR_MIN."""
+    M = int(M)
+    n, s1, s2 = np.asarray(n, dtype=np.float64), _f64(s1), _f64(s2)
+    G, D = s1.shape
+    C = G // M
+    N = max(n.sum(), 1.0)
+    gmean = s1.sum(0) / N
+    gvar = np.maximum(s2.sum(0) / N - gmean ** 2, 0.0)
+    nc = n.reshape(C, M).sum(1)
+    safe = np.maximum(nc, 1.0)[:, None]
+    cmean = s1.reshape(C, M, D).sum(1) / safe
+    cvar = np.maximum(s2.reshape(C, M, D).sum(1) / safe - cmean ** 2, 0.0)
+    cmean[nc < 2], cvar[nc < 2] = gmean, gvar
+    safe = np.maximum(n, 1.0)[:, None]
+    mean = s1 / safe
+    var = s2 / safe - mean ** 2
+    sign = np.where(np.arange(G) % 2 == 0, -1.0, 1.0)[:, None]
+    few = n < 2
+    mean[few] = (np.repeat(cmean, M, 0) + sign * SPLIT * np.sqrt(np.repeat(cvar, M, 0)))[few]
+    var[few] = np.repeat(cvar, M, 0)[few]
+    return {"mean": mean, "var": np.maximum(np.maximum(var, var_floor * gvar), VAR_MIN),
+            "weight": (n.reshape(C, M) + 1.0) / (nc[:, None] + M), "mixtures": M}
+
+
+def fit_mix(feats: Sequence, ids: Sequence, optional: Optional[Sequence] = None, V: int = 59, S: int = 1, M: int = 2, iters: int = 6,
+            mix_iters: int = 4, var_floor: float = 0.01, models: Optional[List] = None):
+    """fit_states (the single-Gaussian training, all of it), then mixing up: for each doubling 1 -> 2 (-> 4) split_mixtures, then up
+    to mix_iters passes of
+        align with the current model (loglik_mix -> viterbi_states), assign components (mix_labels), accumulate, estimate,
+    a doubling's passes ending early once no state duration and no count changes; at the end one closing alignment with the last
+    estimate, so that the durations returned are the model's own.  Returns (model, state durations: list of int64 [P, S] | None,
+    scores: fit_states' and then one per mixture alignment, the closing one included).  models: receives the model every mixture
+    alignment used."""
+    if M not in (1, 2, 4):
+        raise ValueError(f"mixtures must be 1, 2 or 4, not {M!r}")
+    ids = [np.asarray(i, dtype=np.int64) for i in ids]
+    optional = [None] * len(ids) if optional is None else list(optional)
+    model, durs, scores = fit_states(feats, ids, optional, V=V, S=S, iters=iters, var_floor=var_floor)
+    if M == 1:
+        return model, durs, scores
+    C = V * int(S)
+
+    def align_all(model):
+        a, mu, k = loglik_mix_params(model)
+        new, total = [], 0.0
+        for x, i, o in zip(feats, ids, optional):
+            d, _, s = viterbi_states(loglik_mix_from_params(x, a, mu, k, model["mixtures"]), i, S, o)
+            new.append(d)
+            total += s if d is not None else 0.0
+        if models is not None:
+            models.append(model)
+        scores.append(total)
+        return new, (a, mu, k)
+
+    while mixtures_of(model) < M:
+        model = dict(split_mixtures(model), states=int(S))
+        m, counts = model["mixtures"], None
+        for _ in range(mix_iters):
+            new, prm = align_all(model)
+            labels = [mix_labels_from_params(x, state_labels(i, d, S), *prm, m) if d is not None else np.full(_f64(x).shape[0], -1)
+                      for x, i, d in zip(feats, ids, new)]
+            n, s1, s2 = accumulate(feats, labels, C * m)
+            model = dict(model_from_mix_stats(n, s1, s2, m, var_floor=var_floor), states=int(S))
+            same = counts is not None and np.array_equal(n, counts) and all(
+                (d is None and e is None) or (d is not None and e is not None and np.array_equal(d, e)) for d, e in zip(durs, new))
+            durs, counts = new, n
+            if same:
+                break
+    durs, _ = align_all(model)
+    return model, durs, scores
+
+
+def synthetic_corpus_modes(seed: int, modes: int = 2, optional: bool = False, n_utts: int = 40, V: int = 12, D: int = 8,
+                           mean_std: float = 2.0, noise: float = 1.0, max_frames: int = 12):
+    """synthetic_corpus with phones that have allophones: every class has `modes` means drawn independently, N(0, mean_std^2) per
+    dimension (well separated against `noise`), every token draws one of its class's modes and emits all its frames around that mean.
+    One Gaussian over such a class has the spread of its modes as its variance.  Returns (feats, ids, optional, durations, means [V,
+    modes, D], modes: list of int64 [P], the mode of every token)."""
+    g = np.random.default_rng(seed)
+    means = g.normal(0.0, mean_std, (V, modes, D))
+    feats, ids, opts, durs, picks = [], [], [], [], []
+    for _ in range(n_utts):
+        P = int(g.integers(5, 21))
+        i = g.integers(1 if optional else 0, V, P)
+        o = np.zeros(P, dtype=bool)
+        d = g.integers(1, max_frames + 1, P)
+        k = g.integers(0, modes, P)
+        if optional:
+            for p in range(1, P - 1):
+                if not o[p - 1] and g.random() < 0.25:
+                    o[p], i[p] = True, 0
+                    if g.random() < 0.5:
+                        d[p] = 0
+        lab = np.repeat(i * modes + k, d)
+        feats.append((means.reshape(V * modes, D)[lab] + g.normal(0.0, noise, (lab.shape[0], D))).astype(np.float32))
+        ids.append(i.astype(np.int64)), opts.append(o), durs.append(d.astype(np.int64)), picks.append(k.astype(np.int64))
+    return feats, ids, opts, durs, means, picks

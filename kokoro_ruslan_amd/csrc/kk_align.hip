@@ -286,6 +286,212 @@ __global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const floa
     if (tid == 0 && blockIdx.y == 0) count[v] = cnt[0];
 }
 
+// ---- Gaussian mixtures: M = 2 or 4 components per class (align_torch.loglik_mix, mix_labels, accumulate) -----------------------------
+// G = C M Gaussians, Gaussian c M + m component m of class c; a, mu [G][D] and k [G] = ln w - 1/2 sum_d ln(2 pi var) from the host.
+//   loglik_mix      thread = frame, its D features in registers; a workgroup takes 256 frames and MIX_GC Gaussians (MIX_GC / M whole
+//                   classes), whose parameters it stages in LDS as loglik_kernel does.  Every component value is mix_component(): the
+//                   fmaf chain of loglik_kernel plus k.  L = mx + logf(sum over ascending m of expf(l_m - mx)), mx = max_m l_m; the
+//                   component values stay in registers, only L [C][T_total] is written.  M = 1 writes l_0: kk_align_loglik's bits.
+//   mix_labels      thread = frame: the M components of the frame's own class through the same mix_component(), read from global
+//                   memory (a wave's frames are runs of few classes: the lines stay in L1/L2); the largest wins, the lowest m on a tie.
+//   accumulate_mix  a stable counting sort of the frame indices by label, then one workgroup per (Gaussian, four dimensions) over
+//                   its own list: hist counts the labels of every 256 frames per Gaussian (integer adds in LDS), scan turns every
+//                   Gaussian's row of block counts into an exclusive prefix and its total, starts scans the totals, scatter gives
+//                   frame t the slot start[g] + prefix[g][block] + (frames of the block before t with the same label): ascending t
+//                   inside every list, whatever ran first.  sums is accumulate_kernel on a list: thread i takes the entries i, i +
+//                   256, ... in order, then the fixed tree.  No floating-point atomics: two runs give the same bits.
+constexpr int MIX_GC = 16;                    // Gaussians per workgroup of loglik_mix_kernel: 16 / M classes
+constexpr int MIX_MAXG = 1024;                // Gaussians of a model
+
+// One component's value at a frame: as, ms point at its D parameters (LDS or global), x holds the frame's features.
+template <int DM>
+__device__ __forceinline__ float mix_component(const float (&x)[DM], const float *as, const float *ms, float k, int D) {
+    float acc = 0.f;
+#pragma unroll
+    for (int d = 0; d < DM; ++d)
+        if (d < D) {
+            const float diff = x[d] - ms[d];
+            acc = fmaf(diff * diff, as[d], acc);
+        }
+    return acc + k;
+}
+
+template <int DM, int M>
+__global__ __launch_bounds__(AL_THREADS) void align_loglik_mix_kernel(const float *__restrict__ feat, int64_t T_total, int D, int C,
+                                                                      const float *__restrict__ a, const float *__restrict__ mu,
+                                                                      const float *__restrict__ k, float *__restrict__ L) {
+    constexpr int CC = MIX_GC / M;                                    // classes per workgroup
+    __shared__ float as[MIX_GC * DM], ms[MIX_GC * DM], ks[MIX_GC];
+    const int tid = threadIdx.x, c0 = blockIdx.y * CC, nc = min(CC, C - c0), ng = nc * M, g0 = c0 * M;
+    for (int e = tid; e < ng * D; e += AL_THREADS) {
+        const int gg = e / D, d = e % D;
+        as[gg * DM + d] = a[(int64_t)(g0 + gg) * D + d];
+        ms[gg * DM + d] = mu[(int64_t)(g0 + gg) * D + d];
+    }
+    if (tid < ng) ks[tid] = k[g0 + tid];
+    __syncthreads();
+    const int64_t t = (int64_t)blockIdx.x * AL_THREADS + tid;
+    if (t >= T_total) return;
+    float x[DM];
+#pragma unroll
+    for (int d = 0; d < DM; ++d) x[d] = feat[(int64_t)min(d, D - 1) * T_total + t];
+    for (int cc = 0; cc < nc; ++cc) {
+        float l[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) l[m] = mix_component<DM>(x, as + (cc * M + m) * DM, ms + (cc * M + m) * DM, ks[cc * M + m], D);
+        float out = l[0];
+        if (M > 1) {
+            float mx = l[0];
+#pragma unroll
+            for (int m = 1; m < M; ++m) mx = fmaxf(mx, l[m]);
+            if (mx > -__builtin_inff()) {                             // (a class with no finite component stays -inf)
+                float s = 0.f;
+#pragma unroll
+                for (int m = 0; m < M; ++m) s += expf(l[m] - mx);
+                out = mx + logf(s);
+            } else out = mx;
+        }
+        L[(int64_t)(c0 + cc) * T_total + t] = out;
+    }
+}
+
+template <int DM, int M>
+__global__ __launch_bounds__(AL_THREADS) void align_mix_labels_kernel(const float *__restrict__ feat, int64_t T_total, int D, int C,
+                                                                      const float *__restrict__ a, const float *__restrict__ mu,
+                                                                      const float *__restrict__ k, const int *__restrict__ label,
+                                                                      int *__restrict__ mixlabel) {
+    const int64_t t = (int64_t)blockIdx.x * AL_THREADS + threadIdx.x;
+    if (t >= T_total) return;
+    const int c = label[t];
+    if (c < 0 || c >= C) {
+        mixlabel[t] = -1;
+        return;
+    }
+    float x[DM];
+#pragma unroll
+    for (int d = 0; d < DM; ++d) x[d] = feat[(int64_t)min(d, D - 1) * T_total + t];
+    int best = 0;
+    float top = 0.f;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const int g = c * M + m;
+        const float l = mix_component<DM>(x, a + (int64_t)g * D, mu + (int64_t)g * D, k[g], D);
+        if (m == 0 || l > top) top = l, best = m;                     // ascending m, strictly greater: the lowest component wins a tie
+    }
+    mixlabel[t] = c * M + best;
+}
+
+// The workspace of accumulate_mix, in 32-bit words: prefix [G][NB] (hist's counts, then scan's exclusive prefixes), start [G], order
+// [T_total]; NB = ceil(T_total / 256).
+__global__ __launch_bounds__(AL_THREADS) void align_mix_hist_kernel(const int *__restrict__ label, int64_t T_total, int G, int NB,
+                                                                    int *__restrict__ prefix) {
+    __shared__ int h[MIX_MAXG];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    for (int g = tid; g < G; g += AL_THREADS) h[g] = 0;
+    __syncthreads();
+    const int64_t t = (int64_t)b * AL_THREADS + tid;
+    const int lab = t < T_total ? label[t] : -1;
+    if (lab >= 0 && lab < G) atomicAdd(&h[lab], 1);                   // (integers: the count does not depend on the order)
+    __syncthreads();
+    for (int g = tid; g < G; g += AL_THREADS) prefix[(int64_t)g * NB + b] = h[g];
+}
+
+// The inclusive scan of one value per thread over a 256-thread workgroup (wave shuffles, then the waves' totals in LDS).
+__device__ __forceinline__ int mix_block_scan(int v, int *wave_sum, int &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int h = 1; h < 64; h <<= 1) {
+        const int up = __shfl_up(v, h);
+        if (lane >= h) v += up;
+    }
+    __syncthreads();                                                  // (wave_sum of the call before has been read)
+    if (lane == 63) wave_sum[wave] = v;
+    __syncthreads();
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < AL_THREADS / 64; ++w) {
+        if (w < wave) v += wave_sum[w];
+        total += wave_sum[w];
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(AL_THREADS) void align_mix_scan_kernel(int *__restrict__ prefix, int NB, long long *__restrict__ count) {
+    __shared__ int wave_sum[AL_THREADS / 64];
+    int *row = prefix + (int64_t)blockIdx.x * NB;
+    int carry = 0;
+    for (int b0 = 0; b0 < NB; b0 += AL_THREADS) {
+        const int b = b0 + threadIdx.x, v = b < NB ? row[b] : 0;
+        int total;
+        const int incl = mix_block_scan(v, wave_sum, total);
+        if (b < NB) row[b] = carry + incl - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0) count[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(AL_THREADS) void align_mix_starts_kernel(const long long *__restrict__ count, int G, int *__restrict__ start) {
+    __shared__ int wave_sum[AL_THREADS / 64];
+    int carry = 0;
+    for (int g0 = 0; g0 < G; g0 += AL_THREADS) {
+        const int g = g0 + threadIdx.x, v = g < G ? (int)count[g] : 0;
+        int total;
+        const int incl = mix_block_scan(v, wave_sum, total);
+        if (g < G) start[g] = carry + incl - v;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(AL_THREADS) void align_mix_scatter_kernel(const int *__restrict__ label, int64_t T_total, int G, int NB,
+                                                                       const int *__restrict__ prefix, const int *__restrict__ start,
+                                                                       int *__restrict__ order) {
+    __shared__ int lab[AL_THREADS];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int64_t t = (int64_t)b * AL_THREADS + tid;
+    const int mine = t < T_total ? label[t] : -1;
+    lab[tid] = mine;
+    __syncthreads();
+    if (mine < 0 || mine >= G) return;
+    int rank = 0;
+    for (int j = 0; j < tid; ++j) rank += lab[j] == mine;             // the frames of this block before t with its label
+    order[start[mine] + prefix[(int64_t)mine * NB + b] + rank] = (int)t;           // (< count's total <= T_total: inside order)
+}
+
+__global__ __launch_bounds__(AL_THREADS) void align_mix_sums_kernel(const float *__restrict__ feat, int64_t T_total, int D,
+                                                                    const long long *__restrict__ count, const int *__restrict__ start,
+                                                                    const int *__restrict__ order, double *__restrict__ sum,
+                                                                    double *__restrict__ sumsq) {
+    __shared__ double red[2 * ACC_DG][AL_THREADS];
+    const int g = blockIdx.x, d0 = blockIdx.y * ACC_DG, tid = threadIdx.x;
+    const int n = (int)count[g];
+    const int *list = order + start[g];
+    double s1[ACC_DG] = {}, s2[ACC_DG] = {};
+    for (int i = tid; i < n; i += AL_THREADS) {
+        const int64_t t = list[i];
+#pragma unroll
+        for (int u = 0; u < ACC_DG; ++u)
+            if (d0 + u < D) {
+                const double x = (double)feat[(int64_t)(d0 + u) * T_total + t];
+                s1[u] += x;
+                s2[u] += x * x;
+            }
+    }
+#pragma unroll
+    for (int u = 0; u < ACC_DG; ++u) red[u][tid] = s1[u], red[ACC_DG + u][tid] = s2[u];
+    __syncthreads();
+    for (int h = AL_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int u = 0; u < 2 * ACC_DG; ++u) red[u][tid] += red[u][tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid < ACC_DG && d0 + tid < D) {
+        sum[(int64_t)g * D + d0 + tid] = red[tid][0];
+        sumsq[(int64_t)g * D + d0 + tid] = red[ACC_DG + tid][0];
+    }
+}
+
 // ---- pronunciation scores of an alignment (align_torch.scores) ------------------------------------------------------------------------
 // Two launches, nothing read by the host in between.
 //   score_frames  thread = frame, so a wave reads 64 consecutive floats of every row of L [V][T_total]; L is read once.  SC_VC rows
@@ -477,6 +683,82 @@ extern "C" int kk_align_accumulate(const float *feat, const int *label, int64_t 
     hipLaunchKernelGGL(align_accumulate_kernel, dim3(V, kk_cdiv(D, ACC_DG)), dim3(AL_THREADS), 0, (hipStream_t)stream, feat, label, T_total,
                        D, (long long *)count, sum, sumsq);
     KK_LAUNCH_CHECK("kk_align_accumulate");
+    return 0;
+}
+
+extern "C" int kk_align_mix_frames(void) { return AL_THREADS; }
+
+// The one place that turns the run-time D and M into the template parameters of loglik_mix_kernel and mix_labels_kernel.
+#define AL_LAUNCH_MIX_D(kernel, D, MM, ...)                                              \
+    do {                                                                                 \
+        if ((D) <= 8) hipLaunchKernelGGL((kernel<8, MM>), __VA_ARGS__);                  \
+        else if ((D) <= 32) hipLaunchKernelGGL((kernel<32, MM>), __VA_ARGS__);           \
+        else hipLaunchKernelGGL((kernel<64, MM>), __VA_ARGS__);                          \
+    } while (0)
+#define AL_LAUNCH_MIX(kernel, D, M, ...)                                \
+    do {                                                                \
+        if ((M) == 1) AL_LAUNCH_MIX_D(kernel, D, 1, __VA_ARGS__);       \
+        else if ((M) == 2) AL_LAUNCH_MIX_D(kernel, D, 2, __VA_ARGS__);  \
+        else AL_LAUNCH_MIX_D(kernel, D, 4, __VA_ARGS__);                \
+    } while (0)
+
+static bool mix_shape_ok(int D, int C, int M) {
+    return D >= 1 && D <= 64 && (M == 1 || M == 2 || M == 4) && C >= 1 && (int64_t)C * M <= MIX_MAXG;
+}
+
+extern "C" int kk_align_loglik_mix(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu,
+                                   const float *k, float *L, void *stream) {
+    KK_REQUIRE(feat && a && mu && k && L && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_loglik_mix: bad args");
+    KK_REQUIRE(mix_shape_ok(D, C, M), "kk_align_loglik_mix: D = %d, C = %d, M = %d; needs 1 <= D <= 64, M in {1, 2, 4} and 1 <= C M <= %d",
+               D, C, M, MIX_MAXG);
+    const dim3 grid(kk_cdiv(T_total, AL_THREADS), kk_cdiv(C, MIX_GC / M));
+    kk_note_kernel("align_loglik_mix");
+    AL_LAUNCH_MIX(align_loglik_mix_kernel, D, M, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, C, a, mu, k, L);
+    KK_LAUNCH_CHECK("kk_align_loglik_mix");
+    return 0;
+}
+
+extern "C" int kk_align_mix_labels(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu,
+                                   const float *k, const int *label, int *mixlabel, void *stream) {
+    KK_REQUIRE(feat && a && mu && k && label && mixlabel && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_mix_labels: bad args");
+    KK_REQUIRE(mix_shape_ok(D, C, M), "kk_align_mix_labels: D = %d, C = %d, M = %d; needs 1 <= D <= 64, M in {1, 2, 4} and 1 <= C M <= %d",
+               D, C, M, MIX_MAXG);
+    kk_note_kernel("align_mix_labels");
+    AL_LAUNCH_MIX(align_mix_labels_kernel, D, M, dim3(kk_cdiv(T_total, AL_THREADS)), dim3(AL_THREADS), 0, (hipStream_t)stream, feat,
+                  T_total, D, C, a, mu, k, label, mixlabel);
+    KK_LAUNCH_CHECK("kk_align_mix_labels");
+    return 0;
+}
+
+extern "C" int64_t kk_align_accumulate_mix_ws_bytes(int64_t T_total, int G) {
+    if (T_total < 1 || T_total >= ((int64_t)1 << 31) || G < 1 || G > MIX_MAXG) return 0;
+    return ((int64_t)G * kk_cdiv(T_total, AL_THREADS) + G + T_total) * (int64_t)sizeof(int);
+}
+
+extern "C" int kk_align_accumulate_mix(const float *feat, const int *mixlabel, int64_t T_total, int D, int G, int64_t *count,
+                                       double *sum, double *sumsq, void *ws, int64_t ws_bytes, void *stream) {
+    KK_REQUIRE(feat && mixlabel && count && sum && sumsq && ws && T_total > 0 && T_total < ((int64_t)1 << 31),
+               "kk_align_accumulate_mix: bad args");
+    KK_REQUIRE(D >= 1 && D <= 64 && G >= 1 && G <= MIX_MAXG, "kk_align_accumulate_mix: D = %d, G = %d; needs 1 <= D <= 64 and 1 <= G <= %d",
+               D, G, MIX_MAXG);
+    const int64_t need = kk_align_accumulate_mix_ws_bytes(T_total, G);
+    KK_REQUIRE(ws_bytes >= need, "kk_align_accumulate_mix: a workspace of %lld bytes; needs %lld (kk_align_accumulate_mix_ws_bytes)",
+               (long long)ws_bytes, (long long)need);
+    const int NB = (int)kk_cdiv(T_total, AL_THREADS);
+    int *prefix = (int *)ws, *start = prefix + (int64_t)G * NB, *order = start + G;
+    hipStream_t s = (hipStream_t)stream;
+    kk_note_kernel("align_accumulate_mix");
+    hipLaunchKernelGGL(align_mix_hist_kernel, dim3(NB), dim3(AL_THREADS), 0, s, mixlabel, T_total, G, NB, prefix);
+    KK_LAUNCH_CHECK("kk_align_accumulate_mix (hist)");
+    hipLaunchKernelGGL(align_mix_scan_kernel, dim3(G), dim3(AL_THREADS), 0, s, prefix, NB, (long long *)count);
+    KK_LAUNCH_CHECK("kk_align_accumulate_mix (scan)");
+    hipLaunchKernelGGL(align_mix_starts_kernel, dim3(1), dim3(AL_THREADS), 0, s, (const long long *)count, G, start);
+    KK_LAUNCH_CHECK("kk_align_accumulate_mix (starts)");
+    hipLaunchKernelGGL(align_mix_scatter_kernel, dim3(NB), dim3(AL_THREADS), 0, s, mixlabel, T_total, G, NB, prefix, start, order);
+    KK_LAUNCH_CHECK("kk_align_accumulate_mix (scatter)");
+    hipLaunchKernelGGL(align_mix_sums_kernel, dim3(G, kk_cdiv(D, ACC_DG)), dim3(AL_THREADS), 0, s, feat, T_total, D,
+                       (const long long *)count, start, order, sum, sumsq);
+    KK_LAUNCH_CHECK("kk_align_accumulate_mix (sums)");
     return 0;
 }
 

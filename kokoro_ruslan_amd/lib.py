@@ -279,6 +279,10 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_align_backtrack": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "kk_align_accumulate": [_P, _P, _L, _I, _I, _P, _P, _P, _P],
     "kk_align_scores": [_P, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "kk_align_mix_frames": [],
+    "kk_align_loglik_mix": [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P],
+    "kk_align_mix_labels": [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "kk_align_accumulate_mix": [_P, _P, _L, _I, _I, _P, _P, _P, _P, _L, _P],
     "kk_mel_finish": [_P, _P, _I, _L, _I, _F, _F, _D, _D, _I, _I, _P, _P, _P, _P],
     "kk_wave_join": [_P, _P, _P, _I, _P, _I, _L, _P, _P, _P],
     "kk_losses_fwd": [_P] * 12 + [_I, _I, _I, _I, C.POINTER(KkLossCfg), _P, _P, _P, _P, _P, _I, _P],
@@ -363,6 +367,8 @@ def load() -> C.CDLL:
     lib.kk_attn_warm_next.restype = C.c_int
     lib.kk_seg_sumsq_ws_bytes.argtypes = [_L]
     lib.kk_seg_sumsq_ws_bytes.restype = C.c_int64
+    lib.kk_align_accumulate_mix_ws_bytes.argtypes = [_L, _I]
+    lib.kk_align_accumulate_mix_ws_bytes.restype = C.c_int64
     lib.kk_seg_sumsq_rec_offset.argtypes = []
     lib.kk_seg_sumsq_rec_offset.restype = C.c_int64
     lib.kk_seg_sumsq_rec_capacity.argtypes = []

@@ -10,11 +10,17 @@ once per size on 16 utterances.  One JSON line at the end.
 
     python tools/align_bench.py [repeats=5]
     python tools/align_bench.py [repeats=5] --states S
+    python tools/align_bench.py [repeats=5] --mixtures M
 
 With --states S (1, 2 or 3) the same two sizes are aligned with S states per phoneme instead: PhoneAligner(states=S).align as above, and
 the Viterbi and the backtrack launch alone (device events) -- kk_align_viterbi with S states on L [V S, T] beside the same entry point
 with 1 state on the same box and the same frames (on the maximum over each phoneme's states), interleaved inside every repeat; medians,
-with the spread."""
+with the spread.
+
+With --mixtures M (2 or 4) the three mixture launches alone (device events) on 64 x 600 and 64 x 1800 frames of 28 dimensions, for 59
+classes (1 state) and 177 classes (3 states) of M Gaussians: kk_align_loglik_mix beside kk_align_loglik on the G = C M rows followed by
+torch.logsumexp over each class's M rows, kk_align_mix_labels, and kk_align_accumulate_mix beside kk_align_accumulate on G classes; the
+two comparisons only where G <= 256, which kk_align_loglik and kk_align_accumulate take.  Interleaved inside every repeat; medians."""
 import argparse
 import json
 import os
@@ -32,8 +38,9 @@ from kokoro_ruslan_amd.align import PhoneAligner
 _ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
 _ap.add_argument("repeats", nargs="?", type=int, default=5)
 _ap.add_argument("--states", type=int, choices=(1, 2, 3), default=None, metavar="S", help="states per phoneme: 1, 2 or 3")
+_ap.add_argument("--mixtures", type=int, choices=(2, 4), default=None, metavar="M", help="Gaussians per class: 2 or 4")
 _args = _ap.parse_args()
-REPEATS, STATES = _args.repeats, _args.states
+REPEATS, STATES, MIXTURES = _args.repeats, _args.states, _args.mixtures
 SIZES, B, FIT_B, M, V = ((100, 600), (300, 1800)), 64, 256, 80, 59
 al = PhoneAligner(n_classes=V)
 
@@ -126,8 +133,57 @@ def states_bench(S):
     print(json.dumps(out))
 
 
+def mixtures_bench(M):
+    """--mixtures M: the likelihood, labels and accumulate launches of a mixture model, beside the single-Gaussian entry points."""
+    from kokoro_ruslan_amd import lib as kk
+    D, out, todo = 28, {"repeats": REPEATS, "mixtures": M, "launches": {}}, []
+    g = torch.Generator().manual_seed(11)
+    for S in (1, 3):
+        for _, T in SIZES:
+            C, Tt = V * S, B * T
+            G = C * M
+            alm = PhoneAligner(n_classes=V, states=S, mixtures=M)
+            w = torch.rand(C, M, generator=g, dtype=torch.float64) + 0.1
+            model = {"mean": torch.randn(G, D, generator=g, dtype=torch.float64) * 2.0, "var": torch.rand(G, D, generator=g, dtype=torch.float64) + 0.5,
+                     "weight": w / w.sum(1, keepdim=True), "mixtures": M, **({"states": S} if S > 1 else {})}
+            a, mu, k = alm.params(model)
+            feat = (torch.randn(D, Tt, generator=g) * 2.0).cuda().contiguous()
+            label = torch.repeat_interleave(torch.randint(0, C, (Tt // 6,), generator=g), 6).to(torch.int32).cuda()     # runs of 6 frames
+            L, rows = torch.empty(C, Tt, device="cuda"), torch.empty(G, Tt, device="cuda") if G <= 256 else None
+            mixlabel = alm.mix_labels(feat, model, label)
+            count, sums = torch.empty(G, dtype=torch.int64, device="cuda"), torch.empty(2, G, D, dtype=torch.float64, device="cuda")
+            ws = torch.empty(kk.load().kk_align_accumulate_mix_ws_bytes(Tt, G), dtype=torch.uint8, device="cuda")
+            fns = {"loglik_mix_ms": lambda feat=feat, Tt=Tt, C=C, a=a, mu=mu, k=k, L=L: kk.call("kk_align_loglik_mix", feat, Tt, D, C, M, a, mu, k, L),
+                   "mix_labels_ms": lambda feat=feat, Tt=Tt, C=C, a=a, mu=mu, k=k, label=label, mixlabel=mixlabel:
+                       kk.call("kk_align_mix_labels", feat, Tt, D, C, M, a, mu, k, label, mixlabel),
+                   "accumulate_mix_ms": lambda feat=feat, mixlabel=mixlabel, Tt=Tt, G=G, count=count, sums=sums, ws=ws:
+                       kk.call("kk_align_accumulate_mix", feat, mixlabel, Tt, D, G, count, sums[0], sums[1], ws, ws.numel())}
+            if G <= 256:
+                def rows_then_logsumexp(feat=feat, Tt=Tt, G=G, C=C, a=a, mu=mu, k=k, rows=rows):
+                    kk.call("kk_align_loglik", feat, Tt, D, G, a, mu, k, rows)
+                    return torch.logsumexp(rows.view(C, M, Tt), 1)
+                fns["loglik_rows_logsumexp_ms"] = rows_then_logsumexp
+                fns["accumulate_ms"] = lambda feat=feat, mixlabel=mixlabel, Tt=Tt, G=G, count=count, sums=sums: \
+                    kk.call("kk_align_accumulate", feat, mixlabel, Tt, D, G, count, sums[0], sums[1])
+            for fn in fns.values():
+                fn()                                                    # warm-up
+            todo.append((f"C{C}xM{M}_T{Tt}", fns, {name: [] for name in fns}))
+    for _ in range(REPEATS):
+        for _, fns, r in todo:
+            for name, fn in fns.items():
+                r[name].append(device_ms(fn))
+    for key, fns, r in todo:
+        med = {name.replace("_ms", "_median_ms"): statistics.median(v) for name, v in r.items()}
+        out["launches"][key] = dict(r, **med)
+        print(f"{key}: " + " | ".join(f"{name[:-3]} {statistics.median(v):.3f} ms [{min(v):.3f}, {max(v):.3f}]" for name, v in r.items()))
+    print(json.dumps(out))
+
+
 if STATES is not None:
     states_bench(STATES)
+    sys.exit(0)
+if MIXTURES is not None:
+    mixtures_bench(MIXTURES)
     sys.exit(0)
 result = {"repeats": REPEATS, "align": {}, "fit": {}}
 cases = {}
