@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define KK_ABI_VERSION 4 /* 4: kk_align_viterbi and kk_align_backtrack take `states` (backtrack also `state_durations`, may be NULL at 1
+#define KK_ABI_VERSION 5 /* 5: kk_align_loglik takes `M` (components per class); kk_align_loglik_mix is gone;
+                          4: kk_align_viterbi and kk_align_backtrack take `states` (backtrack also `state_durations`, may be NULL at 1
                           state); kk_align_viterbi_states and kk_align_backtrack_states are gone;
                           3: kk_im2col3_fwd, kk_groupnorm_relu_fwd and kk_rowdot_fwd take the rows' lengths (`lens`, may be NULL); the
                           per-row variants of the first two and the row-mask entry point of batched synthesis are gone;
@@ -635,9 +636,12 @@ int kk_align_max_tokens(void);
  * K+1..2K+1 their first differences (x(t+1) - x(t-1)) / 2, the edge frames replicated */
 int kk_align_feats(const float *cep, const float *mel, int64_t T_total, int M, int K, const int *foff, int B, float *feat,
                    void *stream);
-/* L[v][t] = sum over ascending d of a[v][d] (feat[d][t] - mu[v][d])^2 (one fp32 fmaf chain) + c[v]; a = -1/2 / var, mu, c = -1/2
- * sum_d ln(2 pi var): [V][D], [V][D], [V] from the HOST (fp64, rounded once).  D <= 64, V <= 256; L: [V][T_total] */
-int kk_align_loglik(const float *feat, int64_t T_total, int D, int V, const float *a, const float *mu, const float *c, float *L,
+/* a class is a mixture of M in {1, 2, 4} Gaussians, G = C M <= 1024 of them, Gaussian c M + m component m of class c; a = -1/2 / var,
+ * mu: [G][D], k: [G] = ln w - 1/2 sum_d ln(2 pi var) (M = 1: no weight), from the HOST (fp64, rounded once); D <= 64.
+ * l_m = sum over ascending d of a[g][d] (feat[d][t] - mu[g][d])^2 (one fp32 fmaf chain) + k[g], g = c M + m; L[c][t] = mx + logf(sum
+ * over ascending m of expf(l_m - mx)), mx = max_m l_m, and l_0 itself at M = 1.  The component values stay in registers: only L
+ * [C][T_total] is written.  A k of -inf drops its component (L is finite while one component of the class is) */
+int kk_align_loglik(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu, const float *k, float *L,
                     void *stream);
 /* states per phoneme kk_align_viterbi and kk_align_backtrack take */
 int kk_align_max_states(void);
@@ -660,17 +664,11 @@ int kk_align_backtrack(const uint32_t *codes, const int64_t *coff, const int *fo
  * fixed-order partial sums and a fixed tree (no atomics: two runs give the same bits) */
 int kk_align_accumulate(const float *feat, const int *label, int64_t T_total, int D, int V, int64_t *count, double *sum,
                         double *sumsq, void *stream);
-/* Gaussian mixtures: M in {1, 2, 4} components per class, G = C M <= 1024 Gaussians, Gaussian c M + m component m of class c; a, mu:
- * [G][D], k: [G] = ln w - 1/2 sum_d ln(2 pi var), from the HOST (fp64, rounded once); D <= 64.  The entry points above stay as they are.
- * frames per workgroup of kk_align_loglik_mix, kk_align_mix_labels and kk_align_accumulate_mix's counting passes */
+/* training a mixture model: a, mu, k, C and M as kk_align_loglik takes them.
+ * frames per workgroup of kk_align_loglik, kk_align_mix_labels and kk_align_accumulate_mix's counting passes */
 int kk_align_mix_frames(void);
-/* L[c][t] = mx + logf(sum over ascending m of expf(l_m - mx)), mx = max_m l_m, l_m = sum over ascending d of a[g][d] (feat[d][t] -
- * mu[g][d])^2 (kk_align_loglik's fp32 fmaf chain) + k[g], g = c M + m.  The component values stay in registers: only L [C][T_total] is
- * written.  A k of -inf drops its component (L is finite while one component of the class is); M = 1 gives kk_align_loglik's bits */
-int kk_align_loglik_mix(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu, const float *k,
-                        float *L, void *stream);
 /* mixlabel[t] = label[t] M + m*, m* the component of class label[t] with the largest l_m (the same device function, so the same bits,
- * as in kk_align_loglik_mix; the lowest m on a tie); -1 where label[t] is outside 0..C-1.  Every element of mixlabel [T_total] is
+ * as in kk_align_loglik; the lowest m on a tie); -1 where label[t] is outside 0..C-1.  Every element of mixlabel [T_total] is
  * written */
 int kk_align_mix_labels(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu, const float *k,
                         const int *label, int *mixlabel, void *stream);

@@ -11,7 +11,7 @@ accuracy, per token and per utterance).  align_torch is the fp64 oracle of every
 a token that has frames has at least S, one per state.  Everything follows the aligner's `states`; 1 is the default and changes nothing.
 
 `PhoneAligner(mixtures=M)`, M = 2 or 4, gives every class (state) a mixture of M diagonal Gaussians, Gaussian c M + m component m of
-class c, with weights [C, M]: L(c, t) is the log of the weighted sum of its components (kk_align_loglik_mix).  `fit` trains the single
+class c, with weights [C, M]: L(c, t) is the log of the weighted sum of its components (kk_align_loglik).  `fit` trains the single
 Gaussians as always, then mixes up: split every component in two, a few passes that assign every frame to the best component of its
 class, double again.  Alignment and scores see only L [C, T]; 1 is the default and changes nothing.
 """
@@ -31,7 +31,7 @@ MAX_MEL = 128                            # kk_mcep stages 64 frames of at most t
 MAX_CLASSES = 256                        # kk_align_loglik
 MAX_DIM = 64
 MAX_STATES = 3                           # kk_align_viterbi
-MIXTURES = (1, 2, 4)                     # components per class: kk_align_loglik_mix
+MIXTURES = (1, 2, 4)                     # components per class: kk_align_loglik
 MAX_GAUSSIANS = 1024                     # classes x components
 
 
@@ -128,11 +128,13 @@ class PhoneAligner:
             if int(t.min()) < 0 or int(t.max()) >= self.n_classes:
                 raise ValueError(f"utterance {i}: phoneme ids must lie in 0..{self.n_classes - 1}")
 
+    def _check_tags(self, model: Dict) -> None:
+        for k, mine in (("states", self.states), ("mixtures", self.mixtures)):
+            if int(model.get(k, 1)) != mine:
+                raise ValueError(f"the model has {k} = {int(model.get(k, 1))}; this aligner has {k} = {mine}")
+
     def _check_model(self, model: Dict, D: int) -> None:
-        if int(model.get("states", 1)) != self.states:
-            raise ValueError(f"the model has states = {int(model.get('states', 1))}; this aligner has states = {self.states}")
-        if int(model.get("mixtures", 1)) != self.mixtures:
-            raise ValueError(f"the model has mixtures = {int(model.get('mixtures', 1))}; this aligner has mixtures = {self.mixtures}")
+        self._check_tags(model)
         for k in ("mean", "var"):
             if tuple(model[k].shape) != (self.gaussians, D):
                 raise ValueError(f"the model's {k} is {tuple(model[k].shape)}; this aligner and these features need ({self.gaussians}, {D})")
@@ -177,10 +179,7 @@ class PhoneAligner:
         self._check_model(model, D)
         a, mu, c = self.params(model)
         L = torch.empty(self.classes, T, dtype=torch.float32, device=self.device)
-        if self.mixtures > 1:
-            kk.call("kk_align_loglik_mix", feat, T, D, self.classes, self.mixtures, a, mu, c, L)
-        else:
-            kk.call("kk_align_loglik", feat, T, D, self.classes, a, mu, c, L)
+        kk.call("kk_align_loglik", feat, T, D, self.classes, self.mixtures, a, mu, c, L)
         return L
 
     def mix_labels(self, feat: torch.Tensor, model: Dict, label: torch.Tensor) -> torch.Tensor:
@@ -223,7 +222,7 @@ class PhoneAligner:
         few = (n < 2)[:, None]
         mean, var = torch.where(few, gmean, mean), torch.where(few, gvar, var)
         var = torch.maximum(torch.maximum(var, self.var_floor * gvar), torch.full_like(var, VAR_MIN))
-        return self._tag({"mean": mean, "var": var, "K": self.K, "n_classes": self.n_classes})
+        return self._model(mean, var)
 
     def split(self, model: Dict) -> Dict:
         """M -> 2 M (align_torch.split_mixtures): component m becomes 2 m at mu - SPLIT sqrt(var) and 2 m + 1 at mu + SPLIT sqrt(var),
@@ -231,12 +230,8 @@ class PhoneAligner:
         mu, var = model["mean"].to(torch.float64), model["var"].to(torch.float64)
         w = model["weight"].to(mu.device, torch.float64) if "weight" in model else torch.ones(mu.shape[0], 1, dtype=torch.float64, device=mu.device)
         step = SPLIT * var.sqrt()
-        out = {"mean": torch.stack([mu - step, mu + step], 1).reshape(2 * mu.shape[0], -1), "var": var.repeat_interleave(2, 0),
-               "weight": (w / 2.0).repeat_interleave(2, 1), "K": self.K, "n_classes": self.n_classes}
-        if self.states > 1:
-            out["states"] = self.states
-        out["mixtures"] = 2 * int(model.get("mixtures", 1))
-        return out
+        return self._model(torch.stack([mu - step, mu + step], 1).reshape(2 * mu.shape[0], -1), var.repeat_interleave(2, 0),
+                           (w / 2.0).repeat_interleave(2, 1), 2 * int(model.get("mixtures", 1)))
 
     def estimate_mix(self, count: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, M: int) -> Dict:
         """The mixture model of the Gaussians' statistics (align_torch.model_from_mix_stats, in fp64 torch)."""
@@ -259,16 +254,16 @@ class PhoneAligner:
         few = (n < 2)[:, None]
         mean, var = torch.where(few, cmean + sign * SPLIT * cvar.sqrt(), mean), torch.where(few, cvar, var)
         var = torch.maximum(torch.maximum(var, self.var_floor * gvar), torch.full_like(var, VAR_MIN))
-        out = {"mean": mean, "var": var, "weight": (n.view(C, M) + 1.0) / (nc[:, None] + M), "K": self.K, "n_classes": self.n_classes}
-        if self.states > 1:
-            out["states"] = self.states
-        out["mixtures"] = int(M)
-        return out
+        return self._model(mean, var, (n.view(C, M) + 1.0) / (nc[:, None] + M), M)
 
-    def _tag(self, model: Dict) -> Dict:
-        """A multi-state model says so; a 1-state model stays the dictionary it always was."""
+    def _model(self, mean: torch.Tensor, var: torch.Tensor, weight: Optional[torch.Tensor] = None, mixtures: int = 1) -> Dict:
+        """A model's dictionary.  A multi-state model says so, and "mixtures" comes with the weights [C, M]; a 1-state model of
+        single Gaussians stays the dictionary it always was."""
+        model = {"mean": mean, "var": var, "K": self.K, "n_classes": self.n_classes}
         if self.states > 1:
             model["states"] = self.states
+        if weight is not None:
+            model.update(weight=weight, mixtures=int(mixtures))
         return model
 
     # ---- one batch on the device -------------------------------------------------------------------------------------------------
@@ -477,17 +472,20 @@ class PhoneAligner:
         return all((d is None and e is None) or (d is not None and e is not None and torch.equal(d.reshape(-1), e.reshape(-1)))
                    for d, e in zip(old, new))
 
-    def _align_corpus(self, packs, model):
-        """One alignment of every batch: (runs, the frame labels per batch, what has to stop changing per utterance, the phone
-        durations per utterance, the corpus score)."""
-        runs, new, phone, total = [], [], [], 0.0
+    def _align_corpus(self, packs, model, keep_runs: bool = False):
+        """One alignment of every batch: (the batches' runs if they are to be kept, the frame labels per batch, what has to stop
+        changing per utterance (1 state: the durations), the phone durations per utterance, the corpus score)."""
+        runs, labels, new, phone, total = [], [], [], [], 0.0
         for pk in packs:
-            runs.append(self._align_packed(pk, model))
-            for r in self._records(runs[-1]):
+            run = self._align_packed(pk, model)
+            labels.append(run["label"])
+            if keep_runs:
+                runs.append(run)
+            for r in self._records(run):
                 new.append(r.get("state_durations", r["durations"]))
                 phone.append(r["durations"])
                 total += r["score"] if r["feasible"] else 0.0
-        return runs, [r["label"] for r in runs], new, phone, total
+        return runs, labels, new, phone, total
 
     def _fit_mix(self, packs, flat, iters: int, mix_iters: int, on_mix_pass):
         model, _, scores = self._stage(1)._fit_single(packs, flat, iters)
@@ -498,7 +496,7 @@ class PhoneAligner:
             al = self._stage(m)
             model, counts = al.split(model), None
             for _ in range(mix_iters):
-                runs, labels, new, phone, total = al._align_corpus(packs, model)
+                runs, labels, new, phone, total = al._align_corpus(packs, model, on_mix_pass is not None)
                 scores.append(total)
                 if on_mix_pass is not None:
                     on_mix_pass(model, runs)
@@ -512,7 +510,7 @@ class PhoneAligner:
                 durs, counts = new, n
                 if same:
                     break
-        runs, _, durs, phone, total = self._align_corpus(packs, model)
+        runs, _, durs, phone, total = self._align_corpus(packs, model, on_mix_pass is not None)
         scores.append(total)
         if on_mix_pass is not None:
             on_mix_pass(model, runs)
@@ -535,17 +533,9 @@ class PhoneAligner:
                 part = self.accumulate(pk["feat"], lab)
                 stats = part if stats is None else tuple(a + b for a, b in zip(stats, part))
             model = self.estimate(*stats)
-            new, phone, labels, total = [], [], [], 0.0
-            for pk in packs:
-                run = self._align_packed(pk, model)
-                labels.append(run["label"])
-                for r in self._records(run):
-                    new.append(r.get("state_durations", r["durations"]))          # what has to stop changing (1 state: the durations)
-                    phone.append(r["durations"])
-                    total += r["score"] if r["feasible"] else 0.0
+            _, labels, new, phone, total = self._align_corpus(packs, model)
             scores.append(total)
-            same = all((d is None and e is None) or (d is not None and e is not None and torch.equal(d.reshape(-1), e.reshape(-1)))
-                       for d, e in zip(durs, new))
+            same = self._same(durs, new)
             durs = new
             if same:
                 break
@@ -556,15 +546,9 @@ class PhoneAligner:
     def save(self, model: Dict, path: str) -> None:
         """A multi-state model's file also has "states"; a 1-state model's file stays what it was (a file without the field is S = 1).
         The same holds for "mixtures", with which "weight" [C, M] comes."""
-        if int(model.get("states", 1)) != self.states:
-            raise ValueError(f"the model has states = {int(model.get('states', 1))}; this aligner has states = {self.states}")
-        if int(model.get("mixtures", 1)) != self.mixtures:
-            raise ValueError(f"the model has mixtures = {int(model.get('mixtures', 1))}; this aligner has mixtures = {self.mixtures}")
-        out = self._tag({"mean": model["mean"].detach().to("cpu", torch.float64), "var": model["var"].detach().to("cpu", torch.float64),
-                         "K": self.K, "n_classes": self.n_classes})
-        if self.mixtures > 1:
-            out.update(weight=model["weight"].detach().to("cpu", torch.float64), mixtures=self.mixtures)
-        torch.save(out, path)
+        self._check_tags(model)
+        host = lambda k: model[k].detach().to("cpu", torch.float64)
+        torch.save(self._model(host("mean"), host("var"), host("weight") if self.mixtures > 1 else None, self.mixtures), path)
 
     @staticmethod
     def file_states(path: str) -> int:
@@ -587,15 +571,10 @@ class PhoneAligner:
         M = int(m.get("mixtures", 1))
         if M != self.mixtures:
             raise ValueError(f"{path}: a model of mixtures = {M}; this aligner has mixtures = {self.mixtures}")
-        if M > 1:
-            if tuple(m["mean"].shape[:1]) != (self.gaussians,) or tuple(m["var"].shape[:1]) != (self.gaussians,) or \
-                    tuple(m["weight"].shape) != (self.classes, M):
-                raise ValueError(f"{path}: a model of {int(m['mean'].shape[0])} Gaussians and weights {tuple(m['weight'].shape)}; "
-                                 f"{self.n_classes} classes of {S} states and {M} components need {self.gaussians} and ({self.classes}, {M})")
-            out = self._tag({"mean": m["mean"].to(self.device), "var": m["var"].to(self.device), "weight": m["weight"].to(self.device),
-                             "K": self.K, "n_classes": self.n_classes})
-            out["mixtures"] = M
-            return out
-        if tuple(m["mean"].shape[:1]) != (self.classes,) or tuple(m["var"].shape[:1]) != (self.classes,):
-            raise ValueError(f"{path}: a model of {int(m['mean'].shape[0])} Gaussians; {self.n_classes} classes of {S} states need {self.classes}")
-        return self._tag({"mean": m["mean"].to(self.device), "var": m["var"].to(self.device), "K": self.K, "n_classes": self.n_classes})
+        weight = m["weight"] if M > 1 else None
+        if tuple(m["mean"].shape[:1]) != (self.gaussians,) or tuple(m["var"].shape[:1]) != (self.gaussians,) or \
+                (M > 1 and tuple(weight.shape) != (self.classes, M)):
+            have, want = f"{path}: a model of {int(m['mean'].shape[0])} Gaussians", f"{self.n_classes} classes of {S} states"
+            raise ValueError(f"{have} and weights {tuple(weight.shape)}; {want} and {M} components need {self.gaussians} and "
+                             f"({self.classes}, {M})" if M > 1 else f"{have}; {want} need {self.classes}")
+        return self._model(m["mean"].to(self.device), m["var"].to(self.device), None if weight is None else weight.to(self.device), M)

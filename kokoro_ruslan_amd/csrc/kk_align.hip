@@ -7,9 +7,12 @@
 //               the mel channels), each minus the utterance's own mean over time, then rows K+1..2K+1 their first differences
 //               (x(t+1) - x(t-1)) / 2 with the edge frames replicated.  One workgroup per (utterance, row); the mean is a fixed-order
 //               sum (thread i takes the frames i, i + 256, ..., then a fixed tree), in fp64 from the fp32 values.
-//   loglik      L[v][t] = sum over ascending d of a[v][d] (x[d][t] - mu[v][d])^2 (one fmaf chain), plus c[v]: a = -1/2 / var, mu and
-//               c = -1/2 sum_d ln(2 pi var) come from the HOST (fp64, rounded once).  A workgroup takes 256 frames and 16 classes,
-//               whose parameters it stages in LDS (read wave-uniformly); a thread holds its frame's features in registers.
+//   loglik      a class is a mixture of M = 1, 2 or 4 Gaussians, Gaussian c M + m component m of class c.  A component's value is
+//               l_m = sum over ascending d of a[g][d] (x[d][t] - mu[g][d])^2 (one fmaf chain: mix_component()), plus k[g]: a = -1/2
+//               / var, mu and k = ln w - 1/2 sum_d ln(2 pi var) come from the HOST (fp64, rounded once).  L[c][t] = mx + logf(sum
+//               over ascending m of expf(l_m - mx)), mx = max_m l_m; M = 1 writes l_0 (no weight: k is the constant alone).  A
+//               workgroup takes 256 frames and LL_GC Gaussians (LL_GC / M whole classes), whose parameters it stages in LDS (read
+//               wave-uniformly); a thread holds its frame's features and its class's component values in registers.
 //   viterbi     a phoneme is a left-to-right chain of NS states (1..3; align_torch.viterbi_states), class v NS + j for state j of
 //               phoneme v.  One workgroup per utterance, thread p = token p, which keeps its NS scores in registers:
 //               S(p, j, t) = L[ids[p] NS + j][t] + max(S(p, j, t-1), S(p, j-1, t-1)) for j > 0, and for j = 0 the maximum of
@@ -26,8 +29,8 @@
 //               writes the state durations and their row sums, the durations, out.  An infeasible utterance (no finite path) gets
 //               durations 0 and labels -1.
 //   accumulate  per class the count and, in fp64, sum x and sum x^2 over the frames labelled with it: one workgroup per (class, four
-//               dimensions), thread i sums the frames i, i + 256, ... in order, then a fixed tree.  No atomics: two runs give the
-//               same bits.
+//               dimensions), thread i sums the frames i, i + 256, ... in order (acc_frame), then a fixed tree (acc_finish).  No
+//               atomics: two runs give the same bits.
 // Nothing an utterance computes in feats, viterbi or backtrack depends on the other utterances, and a frame's L on that frame alone.
 // kk_align_scores (two more launches, described where they stand) turns L and an alignment into pronunciation scores.
 // feats, loglik, accumulate and scores know nothing of states: they take V NS classes.
@@ -40,14 +43,53 @@ constexpr int AL_MAXT = 4096;                 // frames of an utterance (the pos
 constexpr int AL_MAXS = 3;                    // states per phoneme
 constexpr int AL_PRE = 8;                     // frames of L a state loads ahead
 constexpr int AL_THREADS = 256;
-constexpr int LL_VC = 16;                     // classes per workgroup of loglik_kernel
-constexpr int ACC_DG = 4;                     // dimensions per workgroup of accumulate_kernel
+constexpr int LL_GC = 16;                     // Gaussians per workgroup of loglik_kernel: 16 / M classes
+constexpr int ACC_DG = 4;                     // dimensions per workgroup of accumulate_kernel and mix_sums_kernel
+constexpr int MIX_MAXG = 1024;                // Gaussians of a model
+
+// The fixed tree over a workgroup's N rows of fp64 partial sums, and over cnt beside them if given: the totals end in column 0.
+template <int N>
+__device__ __forceinline__ void al_tree(double (*red)[AL_THREADS], int *cnt) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    for (int h = AL_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            double s[N];                                              // every row is read before any is written: paired LDS accesses
+#pragma unroll
+            for (int u = 0; u < N; ++u) s[u] = red[u][tid] + red[u][tid + h];
+#pragma unroll
+            for (int u = 0; u < N; ++u) red[u][tid] = s[u];
+            if (cnt) cnt[tid] += cnt[tid + h];
+        }
+        __syncthreads();
+    }
+}
+
+// The inclusive scan of one value per thread over a 256-thread workgroup (wave shuffles, then the waves' totals in LDS).
+__device__ __forceinline__ int al_block_scan(int v, int *wave_sum, int &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int h = 1; h < 64; h <<= 1) {
+        const int up = __shfl_up(v, h);
+        if (lane >= h) v += up;
+    }
+    __syncthreads();                                                  // (wave_sum of the call before has been read)
+    if (lane == 63) wave_sum[wave] = v;
+    __syncthreads();
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < AL_THREADS / 64; ++w) {
+        if (w < wave) v += wave_sum[w];
+        total += wave_sum[w];
+    }
+    return v;
+}
 
 __global__ __launch_bounds__(AL_THREADS) void align_feats_kernel(const float *__restrict__ cep, const float *__restrict__ mel,
                                                                  int64_t T_total, int M, int K, const int *__restrict__ foff,
                                                                  float *__restrict__ feat) {
     __shared__ float row[AL_MAXT];
-    __shared__ double red[AL_THREADS];
+    __shared__ double red[1][AL_THREADS];
     const int b = blockIdx.x / (K + 1), r = blockIdx.x % (K + 1), tid = threadIdx.x;
     const int f0 = foff[b], T = foff[b + 1] - f0;
     if (T < 1 || T > AL_MAXT) return;                                 // (the host checks; nothing is written past the LDS row)
@@ -64,13 +106,9 @@ __global__ __launch_bounds__(AL_THREADS) void align_feats_kernel(const float *__
         row[t] = v;
         part += (double)v;
     }
-    red[tid] = part;
-    __syncthreads();
-    for (int h = AL_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    const float mean = (float)(red[0] / (double)T);
+    red[0][tid] = part;
+    al_tree<1>(red, nullptr);
+    const float mean = (float)(red[0][0] / (double)T);
     float *stat = feat + (int64_t)r * T_total + f0, *delta = feat + (int64_t)(K + 1 + r) * T_total + f0;
     for (int t = tid; t < T; t += AL_THREADS) {
         stat[t] = row[t] - mean;
@@ -78,33 +116,69 @@ __global__ __launch_bounds__(AL_THREADS) void align_feats_kernel(const float *__
     }
 }
 
+// One component's value at a frame: as, ms point at its D parameters (LDS or global), x holds the frame's features.
 template <int DM>
-__global__ __launch_bounds__(AL_THREADS) void align_loglik_kernel(const float *__restrict__ feat, int64_t T_total, int D, int V,
+__device__ __forceinline__ float mix_component(const float (&x)[DM], const float *as, const float *ms, float k, int D) {
+    float acc = 0.f;
+#pragma unroll
+    for (int d = 0; d < DM; ++d)
+        if (d < D) {
+            const float diff = x[d] - ms[d];
+            acc = fmaf(diff * diff, as[d], acc);
+        }
+    return acc + k;
+}
+
+template <int DM, int M>
+__global__ __launch_bounds__(AL_THREADS) void align_loglik_kernel(const float *__restrict__ feat, int64_t T_total, int D, int C,
                                                                   const float *__restrict__ a, const float *__restrict__ mu,
-                                                                  const float *__restrict__ c, float *__restrict__ L) {
-    __shared__ float as[LL_VC * DM], ms[LL_VC * DM], cs[LL_VC];
-    const int tid = threadIdx.x, v0 = blockIdx.y * LL_VC, nv = min(LL_VC, V - v0);
-    for (int e = tid; e < nv * D; e += AL_THREADS) {
-        const int vv = e / D, d = e % D;
-        as[vv * DM + d] = a[(int64_t)(v0 + vv) * D + d];
-        ms[vv * DM + d] = mu[(int64_t)(v0 + vv) * D + d];
+                                                                  const float *__restrict__ k, float *__restrict__ L) {
+    constexpr int CC = LL_GC / M;                                     // classes per workgroup
+    __shared__ float as[LL_GC * DM], ms[LL_GC * DM], ks[LL_GC];
+    const int tid = threadIdx.x, c0 = blockIdx.y * CC, nc = min(CC, C - c0), ng = nc * M, g0 = c0 * M;
+    for (int e = tid; e < ng * D; e += AL_THREADS) {
+        const int gg = e / D, d = e % D;
+        as[gg * DM + d] = a[(int64_t)(g0 + gg) * D + d];
+        ms[gg * DM + d] = mu[(int64_t)(g0 + gg) * D + d];
     }
-    if (tid < nv) cs[tid] = c[v0 + tid];
+    if (tid < ng) ks[tid] = k[g0 + tid];
     __syncthreads();
     const int64_t t = (int64_t)blockIdx.x * AL_THREADS + tid;
     if (t >= T_total) return;
     float x[DM];
 #pragma unroll
     for (int d = 0; d < DM; ++d) x[d] = feat[(int64_t)min(d, D - 1) * T_total + t];
-    for (int vv = 0; vv < nv; ++vv) {
-        float acc = 0.f;
+    for (int cc = 0; cc < nc; ++cc) {
+        if (M == 1) {
+            // mix_component() written out with the class's index in the LDS subscripts: the same chain and the same bits, but through
+            // the call the compiler unrolls this loop less (gfx950: 3022 against 4079 instructions at DM = 64) and the M = 1 launch was
+            // 0.045 ms where this form takes 0.040 (59 classes x 38 400 frames, D = 28; docs/LAB_NOTES.md).
+            float acc = 0.f;
 #pragma unroll
-        for (int d = 0; d < DM; ++d)
-            if (d < D) {
-                const float diff = x[d] - ms[vv * DM + d];
-                acc = fmaf(diff * diff, as[vv * DM + d], acc);
-            }
-        L[(int64_t)(v0 + vv) * T_total + t] = acc + cs[vv];
+            for (int d = 0; d < DM; ++d)
+                if (d < D) {
+                    const float diff = x[d] - ms[cc * DM + d];
+                    acc = fmaf(diff * diff, as[cc * DM + d], acc);
+                }
+            L[(int64_t)(c0 + cc) * T_total + t] = acc + ks[cc];
+            continue;
+        }
+        float l[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) l[m] = mix_component<DM>(x, as + (cc * M + m) * DM, ms + (cc * M + m) * DM, ks[cc * M + m], D);
+        float out = l[0];
+        if (M > 1) {
+            float mx = l[0];
+#pragma unroll
+            for (int m = 1; m < M; ++m) mx = fmaxf(mx, l[m]);
+            if (mx > -__builtin_inff()) {                             // (a class with no finite component stays -inf)
+                float s = 0.f;
+#pragma unroll
+                for (int m = 0; m < M; ++m) s += expf(l[m] - mx);
+                out = mx + logf(s);
+            } else out = mx;
+        }
+        L[(int64_t)(c0 + cc) * T_total + t] = out;
     }
 }
 
@@ -248,6 +322,33 @@ __global__ __launch_bounds__(64) void align_backtrack_kernel(const uint32_t *__r
     } while (0)
 static_assert(AL_MAXS == 3, "AL_LAUNCH_NS instantiates 1..3");
 
+// The statistics of one Gaussian over the workgroup's ACC_DG dimensions from d0, shared by the dense path (accumulate_kernel: every
+// frame whose label is the Gaussian) and the list path (mix_sums_kernel: the Gaussian's own list of frames).  acc_frame adds frame t
+// to a thread's sums; acc_finish stages the threads' sums, reduces them (and cnt beside them if given) in the fixed tree and stores
+// the Gaussian's row.  The two paths add a Gaussian's frames in different orders, so their sums may differ in the last bits.
+__device__ __forceinline__ void acc_frame(const float *__restrict__ feat, int64_t T_total, int D, int d0, int64_t t,
+                                          double (&s1)[ACC_DG], double (&s2)[ACC_DG]) {
+#pragma unroll
+    for (int u = 0; u < ACC_DG; ++u)
+        if (d0 + u < D) {
+            const double x = (double)feat[(int64_t)(d0 + u) * T_total + t];
+            s1[u] += x;
+            s2[u] += x * x;
+        }
+}
+
+__device__ __forceinline__ void acc_finish(double (*red)[AL_THREADS], int *cnt, const double (&s1)[ACC_DG], const double (&s2)[ACC_DG],
+                                           int g, int D, int d0, double *__restrict__ sum, double *__restrict__ sumsq) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < ACC_DG; ++u) red[u][tid] = s1[u], red[ACC_DG + u][tid] = s2[u];
+    al_tree<2 * ACC_DG>(red, cnt);
+    if (tid < ACC_DG && d0 + tid < D) {
+        sum[(int64_t)g * D + d0 + tid] = red[tid][0];
+        sumsq[(int64_t)g * D + d0 + tid] = red[ACC_DG + tid][0];
+    }
+}
+
 __global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const float *__restrict__ feat, const int *__restrict__ label,
                                                                       int64_t T_total, int D, long long *__restrict__ count,
                                                                       double *__restrict__ sum, double *__restrict__ sumsq) {
@@ -259,40 +360,16 @@ __global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const floa
     for (int64_t t = tid; t < T_total; t += AL_THREADS)
         if (label[t] == v) {
             ++n;
-#pragma unroll
-            for (int u = 0; u < ACC_DG; ++u)
-                if (d0 + u < D) {
-                    const double x = (double)feat[(int64_t)(d0 + u) * T_total + t];
-                    s1[u] += x;
-                    s2[u] += x * x;
-                }
+            acc_frame(feat, T_total, D, d0, t, s1, s2);
         }
-#pragma unroll
-    for (int u = 0; u < ACC_DG; ++u) red[u][tid] = s1[u], red[ACC_DG + u][tid] = s2[u];
     cnt[tid] = n;
-    __syncthreads();
-    for (int h = AL_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int u = 0; u < 2 * ACC_DG; ++u) red[u][tid] += red[u][tid + h];
-            cnt[tid] += cnt[tid + h];
-        }
-        __syncthreads();
-    }
-    if (tid < ACC_DG && d0 + tid < D) {
-        sum[(int64_t)v * D + d0 + tid] = red[tid][0];
-        sumsq[(int64_t)v * D + d0 + tid] = red[ACC_DG + tid][0];
-    }
+    acc_finish(red, cnt, s1, s2, v, D, d0, sum, sumsq);
     if (tid == 0 && blockIdx.y == 0) count[v] = cnt[0];
 }
 
-// ---- Gaussian mixtures: M = 2 or 4 components per class (align_torch.loglik_mix, mix_labels, accumulate) -----------------------------
-// G = C M Gaussians, Gaussian c M + m component m of class c; a, mu [G][D] and k [G] = ln w - 1/2 sum_d ln(2 pi var) from the host.
-//   loglik_mix      thread = frame, its D features in registers; a workgroup takes 256 frames and MIX_GC Gaussians (MIX_GC / M whole
-//                   classes), whose parameters it stages in LDS as loglik_kernel does.  Every component value is mix_component(): the
-//                   fmaf chain of loglik_kernel plus k.  L = mx + logf(sum over ascending m of expf(l_m - mx)), mx = max_m l_m; the
-//                   component values stay in registers, only L [C][T_total] is written.  M = 1 writes l_0: kk_align_loglik's bits.
-//   mix_labels      thread = frame: the M components of the frame's own class through the same mix_component(), read from global
+// ---- Gaussian mixtures: training's two launches for M = 2 or 4 components per class (align_torch.mix_labels, accumulate) ------------
+// G = C M Gaussians; a, mu [G][D] and k [G] as loglik takes them.
+//   mix_labels      thread = frame: the M components of the frame's own class through loglik's mix_component(), read from global
 //                   memory (a wave's frames are runs of few classes: the lines stay in L1/L2); the largest wins, the lowest m on a tie.
 //   accumulate_mix  a stable counting sort of the frame indices by label, then one workgroup per (Gaussian, four dimensions) over
 //                   its own list: hist counts the labels of every 256 frames per Gaussian (integer adds in LDS), scan turns every
@@ -300,61 +377,6 @@ __global__ __launch_bounds__(AL_THREADS) void align_accumulate_kernel(const floa
 //                   frame t the slot start[g] + prefix[g][block] + (frames of the block before t with the same label): ascending t
 //                   inside every list, whatever ran first.  sums is accumulate_kernel on a list: thread i takes the entries i, i +
 //                   256, ... in order, then the fixed tree.  No floating-point atomics: two runs give the same bits.
-constexpr int MIX_GC = 16;                    // Gaussians per workgroup of loglik_mix_kernel: 16 / M classes
-constexpr int MIX_MAXG = 1024;                // Gaussians of a model
-
-// One component's value at a frame: as, ms point at its D parameters (LDS or global), x holds the frame's features.
-template <int DM>
-__device__ __forceinline__ float mix_component(const float (&x)[DM], const float *as, const float *ms, float k, int D) {
-    float acc = 0.f;
-#pragma unroll
-    for (int d = 0; d < DM; ++d)
-        if (d < D) {
-            const float diff = x[d] - ms[d];
-            acc = fmaf(diff * diff, as[d], acc);
-        }
-    return acc + k;
-}
-
-template <int DM, int M>
-__global__ __launch_bounds__(AL_THREADS) void align_loglik_mix_kernel(const float *__restrict__ feat, int64_t T_total, int D, int C,
-                                                                      const float *__restrict__ a, const float *__restrict__ mu,
-                                                                      const float *__restrict__ k, float *__restrict__ L) {
-    constexpr int CC = MIX_GC / M;                                    // classes per workgroup
-    __shared__ float as[MIX_GC * DM], ms[MIX_GC * DM], ks[MIX_GC];
-    const int tid = threadIdx.x, c0 = blockIdx.y * CC, nc = min(CC, C - c0), ng = nc * M, g0 = c0 * M;
-    for (int e = tid; e < ng * D; e += AL_THREADS) {
-        const int gg = e / D, d = e % D;
-        as[gg * DM + d] = a[(int64_t)(g0 + gg) * D + d];
-        ms[gg * DM + d] = mu[(int64_t)(g0 + gg) * D + d];
-    }
-    if (tid < ng) ks[tid] = k[g0 + tid];
-    __syncthreads();
-    const int64_t t = (int64_t)blockIdx.x * AL_THREADS + tid;
-    if (t >= T_total) return;
-    float x[DM];
-#pragma unroll
-    for (int d = 0; d < DM; ++d) x[d] = feat[(int64_t)min(d, D - 1) * T_total + t];
-    for (int cc = 0; cc < nc; ++cc) {
-        float l[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) l[m] = mix_component<DM>(x, as + (cc * M + m) * DM, ms + (cc * M + m) * DM, ks[cc * M + m], D);
-        float out = l[0];
-        if (M > 1) {
-            float mx = l[0];
-#pragma unroll
-            for (int m = 1; m < M; ++m) mx = fmaxf(mx, l[m]);
-            if (mx > -__builtin_inff()) {                             // (a class with no finite component stays -inf)
-                float s = 0.f;
-#pragma unroll
-                for (int m = 0; m < M; ++m) s += expf(l[m] - mx);
-                out = mx + logf(s);
-            } else out = mx;
-        }
-        L[(int64_t)(c0 + cc) * T_total + t] = out;
-    }
-}
-
 template <int DM, int M>
 __global__ __launch_bounds__(AL_THREADS) void align_mix_labels_kernel(const float *__restrict__ feat, int64_t T_total, int D, int C,
                                                                       const float *__restrict__ a, const float *__restrict__ mu,
@@ -396,26 +418,6 @@ __global__ __launch_bounds__(AL_THREADS) void align_mix_hist_kernel(const int *_
     for (int g = tid; g < G; g += AL_THREADS) prefix[(int64_t)g * NB + b] = h[g];
 }
 
-// The inclusive scan of one value per thread over a 256-thread workgroup (wave shuffles, then the waves' totals in LDS).
-__device__ __forceinline__ int mix_block_scan(int v, int *wave_sum, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int h = 1; h < 64; h <<= 1) {
-        const int up = __shfl_up(v, h);
-        if (lane >= h) v += up;
-    }
-    __syncthreads();                                                  // (wave_sum of the call before has been read)
-    if (lane == 63) wave_sum[wave] = v;
-    __syncthreads();
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < AL_THREADS / 64; ++w) {
-        if (w < wave) v += wave_sum[w];
-        total += wave_sum[w];
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(AL_THREADS) void align_mix_scan_kernel(int *__restrict__ prefix, int NB, long long *__restrict__ count) {
     __shared__ int wave_sum[AL_THREADS / 64];
     int *row = prefix + (int64_t)blockIdx.x * NB;
@@ -423,7 +425,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_mix_scan_kernel(int *__restr
     for (int b0 = 0; b0 < NB; b0 += AL_THREADS) {
         const int b = b0 + threadIdx.x, v = b < NB ? row[b] : 0;
         int total;
-        const int incl = mix_block_scan(v, wave_sum, total);
+        const int incl = al_block_scan(v, wave_sum, total);
         if (b < NB) row[b] = carry + incl - v;
         carry += total;
     }
@@ -436,7 +438,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_mix_starts_kernel(const long
     for (int g0 = 0; g0 < G; g0 += AL_THREADS) {
         const int g = g0 + threadIdx.x, v = g < G ? (int)count[g] : 0;
         int total;
-        const int incl = mix_block_scan(v, wave_sum, total);
+        const int incl = al_block_scan(v, wave_sum, total);
         if (g < G) start[g] = carry + incl - v;
         carry += total;
     }
@@ -466,30 +468,8 @@ __global__ __launch_bounds__(AL_THREADS) void align_mix_sums_kernel(const float 
     const int n = (int)count[g];
     const int *list = order + start[g];
     double s1[ACC_DG] = {}, s2[ACC_DG] = {};
-    for (int i = tid; i < n; i += AL_THREADS) {
-        const int64_t t = list[i];
-#pragma unroll
-        for (int u = 0; u < ACC_DG; ++u)
-            if (d0 + u < D) {
-                const double x = (double)feat[(int64_t)(d0 + u) * T_total + t];
-                s1[u] += x;
-                s2[u] += x * x;
-            }
-    }
-#pragma unroll
-    for (int u = 0; u < ACC_DG; ++u) red[u][tid] = s1[u], red[ACC_DG + u][tid] = s2[u];
-    __syncthreads();
-    for (int h = AL_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-#pragma unroll
-            for (int u = 0; u < 2 * ACC_DG; ++u) red[u][tid] += red[u][tid + h];
-        }
-        __syncthreads();
-    }
-    if (tid < ACC_DG && d0 + tid < D) {
-        sum[(int64_t)g * D + d0 + tid] = red[tid][0];
-        sumsq[(int64_t)g * D + d0 + tid] = red[ACC_DG + tid][0];
-    }
+    for (int i = tid; i < n; i += AL_THREADS) acc_frame(feat, T_total, D, d0, list[i], s1, s2);
+    acc_finish(red, nullptr, s1, s2, g, D, d0, sum, sumsq);
 }
 
 // ---- pronunciation scores of an alignment (align_torch.scores) ------------------------------------------------------------------------
@@ -500,8 +480,8 @@ __global__ __launch_bounds__(AL_THREADS) void align_mix_sums_kernel(const float 
 //                 per SC_VC rows.  The value of the frame's own class (label[t]) is picked up as its row goes by.  Per frame:
 //                 margin = L(label) - fmax and lpost = margin - log(sum), both fp64, and amax.  A frame without a class (label
 //                 outside 0..V-1: the -1 of an infeasible utterance) gets 0 and 0.
-//   score_tokens  one workgroup per utterance.  A thread owns SC_TPT consecutive tokens; an exclusive scan of the durations (wave
-//                 shuffles, then the waves' totals in LDS) gives every token its first frame.  A token's sums run over its frames in
+//   score_tokens  one workgroup per utterance.  A thread owns SC_TPT consecutive tokens; an exclusive scan of the durations
+//                 (al_block_scan) gives every token its first frame.  A token's sums run over its frames in
 //                 ascending order from 0.0, its hits count amax == ids[p]; the utterance's totals run over the tokens' values (kept
 //                 in LDS) in ascending token order, one lane per total.  An utterance outside the limits, or whose durations are not
 //                 all in 0..T with the sum T (the zeros of an infeasible one), gets zeros everywhere: every output is written.
@@ -551,7 +531,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_score_tokens_kernel(const do
                                                                         int *__restrict__ utt_hits) {
     __shared__ double tok[2][AL_MAXP];                                // the tokens' gop_sum and lpost_sum, for the totals
     __shared__ int wave_sum[AL_THREADS / 64], bad, hit_total;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int f0 = foff[b], T = foff[b + 1] - f0, p0 = poff[b], P = poff[b + 1] - p0;
     if (P < 1 || P > AL_MAXP || T < 1 || T > AL_MAXT) {               // (the host checks) zeros, whatever its durations hold
         for (int q = tid; q < P; q += AL_THREADS) gop_sum[p0 + q] = 0.0, lpost_sum[p0 + q] = 0.0, hits[p0 + q] = 0;
@@ -569,21 +549,8 @@ __global__ __launch_bounds__(AL_THREADS) void align_score_tokens_kernel(const do
         if (d[u] < 0 || d[u] > T) wrong = true, d[u] = 0;
         mine += d[u];                                                 // (at most AL_MAXP * AL_MAXT: no overflow)
     }
-    int incl = mine;                                                  // inclusive scan over the wave, then over the waves
-#pragma unroll
-    for (int h = 1; h < 64; h <<= 1) {
-        const int up = __shfl_up(incl, h);
-        if (lane >= h) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
     if (wrong) bad = 1;
-    __syncthreads();
-    int first = incl - mine, total = 0;
-#pragma unroll
-    for (int w = 0; w < AL_THREADS / 64; ++w) {
-        if (w < wave) first += wave_sum[w];
-        total += wave_sum[w];
-    }
+    int total, first = al_block_scan(mine, wave_sum, total) - mine;   // (its barriers also publish bad)
     const bool valid = !bad && total == T;                            // (so no span leaves the utterance's frames)
     int nh = 0;
 #pragma unroll
@@ -634,19 +601,6 @@ extern "C" int kk_align_feats(const float *cep, const float *mel, int64_t T_tota
     return 0;
 }
 
-extern "C" int kk_align_loglik(const float *feat, int64_t T_total, int D, int V, const float *a, const float *mu, const float *c,
-                               float *L, void *stream) {
-    KK_REQUIRE(feat && a && mu && c && L && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_loglik: bad args");
-    KK_REQUIRE(D >= 1 && D <= 64 && V >= 1 && V <= 256, "kk_align_loglik: D = %d, V = %d; needs 1 <= D <= 64 and 1 <= V <= 256", D, V);
-    const dim3 grid(kk_cdiv(T_total, AL_THREADS), kk_cdiv(V, LL_VC));
-    kk_note_kernel("align_loglik");
-    if (D <= 8) hipLaunchKernelGGL(align_loglik_kernel<8>, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, V, a, mu, c, L);
-    else if (D <= 32) hipLaunchKernelGGL(align_loglik_kernel<32>, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, V, a, mu, c, L);
-    else hipLaunchKernelGGL(align_loglik_kernel<64>, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, V, a, mu, c, L);
-    KK_LAUNCH_CHECK("kk_align_loglik");
-    return 0;
-}
-
 extern "C" int kk_align_max_states(void) { return AL_MAXS; }
 
 extern "C" int kk_align_viterbi(const float *L, int64_t T_total, const int *ids, const unsigned char *opt, const int *foff,
@@ -688,7 +642,7 @@ extern "C" int kk_align_accumulate(const float *feat, const int *label, int64_t 
 
 extern "C" int kk_align_mix_frames(void) { return AL_THREADS; }
 
-// The one place that turns the run-time D and M into the template parameters of loglik_mix_kernel and mix_labels_kernel.
+// The one place that turns the run-time D and M into the template parameters of loglik_kernel and mix_labels_kernel.
 #define AL_LAUNCH_MIX_D(kernel, D, MM, ...)                                              \
     do {                                                                                 \
         if ((D) <= 8) hipLaunchKernelGGL((kernel<8, MM>), __VA_ARGS__);                  \
@@ -706,15 +660,15 @@ static bool mix_shape_ok(int D, int C, int M) {
     return D >= 1 && D <= 64 && (M == 1 || M == 2 || M == 4) && C >= 1 && (int64_t)C * M <= MIX_MAXG;
 }
 
-extern "C" int kk_align_loglik_mix(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu,
+extern "C" int kk_align_loglik(const float *feat, int64_t T_total, int D, int C, int M, const float *a, const float *mu,
                                    const float *k, float *L, void *stream) {
-    KK_REQUIRE(feat && a && mu && k && L && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_loglik_mix: bad args");
-    KK_REQUIRE(mix_shape_ok(D, C, M), "kk_align_loglik_mix: D = %d, C = %d, M = %d; needs 1 <= D <= 64, M in {1, 2, 4} and 1 <= C M <= %d",
+    KK_REQUIRE(feat && a && mu && k && L && T_total > 0 && T_total < ((int64_t)1 << 31), "kk_align_loglik: bad args");
+    KK_REQUIRE(mix_shape_ok(D, C, M), "kk_align_loglik: D = %d, C = %d, M = %d; needs 1 <= D <= 64, M in {1, 2, 4} and 1 <= C M <= %d",
                D, C, M, MIX_MAXG);
-    const dim3 grid(kk_cdiv(T_total, AL_THREADS), kk_cdiv(C, MIX_GC / M));
-    kk_note_kernel("align_loglik_mix");
-    AL_LAUNCH_MIX(align_loglik_mix_kernel, D, M, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, C, a, mu, k, L);
-    KK_LAUNCH_CHECK("kk_align_loglik_mix");
+    const dim3 grid(kk_cdiv(T_total, AL_THREADS), kk_cdiv(C, LL_GC / M));
+    kk_note_kernel("align_loglik");
+    AL_LAUNCH_MIX(align_loglik_kernel, D, M, grid, dim3(AL_THREADS), 0, (hipStream_t)stream, feat, T_total, D, C, a, mu, k, L);
+    KK_LAUNCH_CHECK("kk_align_loglik");
     return 0;
 }
 

@@ -273,14 +273,13 @@ SIGNATURES: Dict[str, List[Any]] = {
     "kk_dtw_spectral_stats": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "kk_align_max_tokens": [],
     "kk_align_feats": [_P, _P, _L, _I, _I, _P, _I, _P, _P],
-    "kk_align_loglik": [_P, _L, _I, _I, _P, _P, _P, _P, _P],
+    "kk_align_loglik": [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "kk_align_max_states": [],
     "kk_align_viterbi": [_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "kk_align_backtrack": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "kk_align_accumulate": [_P, _P, _L, _I, _I, _P, _P, _P, _P],
     "kk_align_scores": [_P, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "kk_align_mix_frames": [],
-    "kk_align_loglik_mix": [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "kk_align_mix_labels": [_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "kk_align_accumulate_mix": [_P, _P, _L, _I, _I, _P, _P, _P, _P, _L, _P],
     "kk_mel_finish": [_P, _P, _I, _L, _I, _F, _F, _D, _D, _I, _I, _P, _P, _P, _P],
@@ -331,7 +330,7 @@ def profile_stop():
     return [(n, a, s.elapsed_time(e)) for n, a, s, e in rec]
 
 
-ABI_VERSION = 4        # include/kokoro_hip.h: KK_ABI_VERSION
+ABI_VERSION = 5        # include/kokoro_hip.h: KK_ABI_VERSION
 
 
 def use_library(flavour: str) -> None:

@@ -5,8 +5,9 @@ PhoneAligner.align (features, log-likelihoods, Viterbi, backtrack and the read o
 utterances of 100 tokens x 600 frames and of 300 x 1800, and one PhoneAligner.fit pass (accumulate, estimate, align) over 256 utterances
 of 100 x 600, against two baselines: the same recurrence written with torch ops on the same GPU (all utterances of the batch per op,
 one frame at a time, the recurrence alone: L given, no codes, no path), and the fp64 oracle (kokoro_ruslan_amd.align_torch) on the host
-in 16 threads.  Five repeats with the device paths interleaved inside every repeat; medians, with the spread.  The host oracle runs
-once per size on 16 utterances.  One JSON line at the end.
+in 16 threads.  Beside every align call the kk_align_loglik (M = 1) and kk_align_accumulate launches alone (device events) on that
+batch's features and labels.  Five repeats with the device paths interleaved inside every repeat; medians, with the spread.  The host
+oracle runs once per size on 16 utterances.  One JSON line at the end.
 
     python tools/align_bench.py [repeats=5]
     python tools/align_bench.py [repeats=5] --states S
@@ -18,9 +19,9 @@ with 1 state on the same box and the same frames (on the maximum over each phone
 with the spread.
 
 With --mixtures M (2 or 4) the three mixture launches alone (device events) on 64 x 600 and 64 x 1800 frames of 28 dimensions, for 59
-classes (1 state) and 177 classes (3 states) of M Gaussians: kk_align_loglik_mix beside kk_align_loglik on the G = C M rows followed by
-torch.logsumexp over each class's M rows, kk_align_mix_labels, and kk_align_accumulate_mix beside kk_align_accumulate on G classes; the
-two comparisons only where G <= 256, which kk_align_loglik and kk_align_accumulate take.  Interleaved inside every repeat; medians."""
+classes (1 state) and 177 classes (3 states) of M Gaussians: kk_align_loglik at M beside kk_align_loglik at M = 1 on the G = C M rows
+followed by torch.logsumexp over each class's M rows, kk_align_mix_labels, and kk_align_accumulate_mix beside kk_align_accumulate on G
+classes; the two comparisons only where G <= 256, which kk_align_accumulate takes.  Interleaved inside every repeat; medians."""
 import argparse
 import json
 import os
@@ -33,6 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from kokoro_ruslan_amd import align_torch as R
+from kokoro_ruslan_amd import lib as kk
 from kokoro_ruslan_amd.align import PhoneAligner
 
 _ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
@@ -88,7 +90,6 @@ def device_ms(fn):
 
 def states_bench(S):
     """--states S: the whole alignment with S states, and the S-state Viterbi and backtrack launches beside the 1-state Viterbi."""
-    from kokoro_ruslan_amd import lib as kk
     from kokoro_ruslan_amd.align import code_words
     als = PhoneAligner(n_classes=V, states=S)
     out, todo = {"repeats": REPEATS, "states": S, "align": {}}, []
@@ -135,7 +136,6 @@ def states_bench(S):
 
 def mixtures_bench(M):
     """--mixtures M: the likelihood, labels and accumulate launches of a mixture model, beside the single-Gaussian entry points."""
-    from kokoro_ruslan_amd import lib as kk
     D, out, todo = 28, {"repeats": REPEATS, "mixtures": M, "launches": {}}, []
     g = torch.Generator().manual_seed(11)
     for S in (1, 3):
@@ -153,14 +153,14 @@ def mixtures_bench(M):
             mixlabel = alm.mix_labels(feat, model, label)
             count, sums = torch.empty(G, dtype=torch.int64, device="cuda"), torch.empty(2, G, D, dtype=torch.float64, device="cuda")
             ws = torch.empty(kk.load().kk_align_accumulate_mix_ws_bytes(Tt, G), dtype=torch.uint8, device="cuda")
-            fns = {"loglik_mix_ms": lambda feat=feat, Tt=Tt, C=C, a=a, mu=mu, k=k, L=L: kk.call("kk_align_loglik_mix", feat, Tt, D, C, M, a, mu, k, L),
+            fns = {"loglik_mix_ms": lambda feat=feat, Tt=Tt, C=C, a=a, mu=mu, k=k, L=L: kk.call("kk_align_loglik", feat, Tt, D, C, M, a, mu, k, L),
                    "mix_labels_ms": lambda feat=feat, Tt=Tt, C=C, a=a, mu=mu, k=k, label=label, mixlabel=mixlabel:
                        kk.call("kk_align_mix_labels", feat, Tt, D, C, M, a, mu, k, label, mixlabel),
                    "accumulate_mix_ms": lambda feat=feat, mixlabel=mixlabel, Tt=Tt, G=G, count=count, sums=sums, ws=ws:
                        kk.call("kk_align_accumulate_mix", feat, mixlabel, Tt, D, G, count, sums[0], sums[1], ws, ws.numel())}
             if G <= 256:
                 def rows_then_logsumexp(feat=feat, Tt=Tt, G=G, C=C, a=a, mu=mu, k=k, rows=rows):
-                    kk.call("kk_align_loglik", feat, Tt, D, G, a, mu, k, rows)
+                    kk.call("kk_align_loglik", feat, Tt, D, G, 1, a, mu, k, rows)
                     return torch.logsumexp(rows.view(C, M, Tt), 1)
                 fns["loglik_rows_logsumexp_ms"] = rows_then_logsumexp
                 fns["accumulate_ms"] = lambda feat=feat, mixlabel=mixlabel, Tt=Tt, G=G, count=count, sums=sums: \
@@ -187,6 +187,18 @@ if MIXTURES is not None:
     sys.exit(0)
 result = {"repeats": REPEATS, "align": {}, "fit": {}}
 cases = {}
+
+
+def launches(run, model):
+    """The likelihood and the statistics launch of a batch, each alone: (loglik, accumulate)."""
+    feat, label, (D, Tt) = run["feat"], run["label"], run["feat"].shape
+    a, mu, c = al.params(model)
+    L, count = torch.empty(V, Tt, device="cuda"), torch.empty(V, dtype=torch.int64, device="cuda")
+    sums = torch.empty(2, V, D, dtype=torch.float64, device="cuda")
+    return (lambda: kk.call("kk_align_loglik", feat, Tt, D, V, 1, a, mu, c, L),
+            lambda: kk.call("kk_align_accumulate", feat, label, Tt, D, V, count, sums[0], sums[1]))
+
+
 for P, T in SIZES:
     mels, ids = corpus(B, P, T, 1000 + P)
     model, _, _ = al.fit(mels, ids, iters=2)                    # warm-up, and a model worth aligning with
@@ -197,28 +209,34 @@ for P, T in SIZES:
     gap = float(((ours - base).abs() / base.abs()).max())      # both sum T fp32 terms along a best path
     print(f"{P} x {T}: kernels against torch ops, largest relative difference of the scores {gap:.2e}"
           + ("" if gap <= T * 2.0 ** -22 else "  <-- MORE than two fp32 sums of T terms explain"))
-    cases[(P, T)] = (mels, ids, model, L, idt, {"kernel_s": [], "torch_s": [], "scores_rel_gap": gap})
+    cases[(P, T)] = (mels, ids, model, L, idt, launches(run, model), {"kernel_s": [], "torch_s": [], "loglik_ms": [], "accumulate_ms": [],
+                                                                      "scores_rel_gap": gap})
 fit_mels, fit_ids = corpus(FIT_B, *SIZES[0], 7)
 al.fit(fit_mels, fit_ids, iters=1)
 fit_s = []
 for _ in range(REPEATS):
-    for key, (mels, ids, model, L, idt, r) in cases.items():
+    for key, (mels, ids, model, L, idt, (ll, acc), r) in cases.items():
         r["kernel_s"].append(timed(lambda: al.align(mels, ids, (), model))[1])
         r["torch_s"].append(timed(lambda: torch_viterbi(L, idt))[1])
+        r["loglik_ms"].append(device_ms(ll))
+        r["accumulate_ms"].append(device_ms(acc))
     fit_s.append(timed(lambda: al.fit(fit_mels, fit_ids, iters=1))[1])
 torch.set_num_threads(1)                                        # 16 utterances side by side, one thread each
 for P, T in SIZES:
-    mels, ids, model, L, idt, r = cases[(P, T)]
+    mels, ids, model, L, idt, _, r = cases[(P, T)]
     Lh, ih = L[:, :16].double().cpu().numpy(), [i.numpy() for i in ids[:16]]
     with ThreadPoolExecutor(16) as ex:
         t0 = time.perf_counter()
         list(ex.map(lambda n: R.align(Lh[:, n], ih[n])[1], range(16)))
         host = time.perf_counter() - t0
     tk, tt = statistics.median(r["kernel_s"]), statistics.median(r["torch_s"])
-    r.update(kernel_median_s=tk, torch_median_s=tt, utterances_per_s=B / tk, cells_per_s=B * P * T / tk, host_oracle_16_threads_utterances_per_s=16 / host)
+    tl, tc = statistics.median(r["loglik_ms"]), statistics.median(r["accumulate_ms"])
+    r.update(kernel_median_s=tk, torch_median_s=tt, loglik_median_ms=tl, accumulate_median_ms=tc, utterances_per_s=B / tk, cells_per_s=B * P * T / tk, host_oracle_16_threads_utterances_per_s=16 / host)
     result["align"][f"{P}x{T}"] = r
     print(f"{P} x {T}, B = {B}: align {tk * 1e3:8.2f} ms [{min(r['kernel_s']) * 1e3:.2f}, {max(r['kernel_s']) * 1e3:.2f}] = {B / tk:8.0f} utterances/s = "
           f"{B * P * T / tk / 1e9:6.2f} G cells/s | torch ops (recurrence only) {tt * 1e3:8.1f} ms [{min(r['torch_s']) * 1e3:.1f}, {max(r['torch_s']) * 1e3:.1f}] | x{tt / tk:.1f} "
+          f"| loglik launch {tl:.3f} ms [{min(r['loglik_ms']):.3f}, {max(r['loglik_ms']):.3f}] "
+          f"| accumulate launch {tc:.3f} ms [{min(r['accumulate_ms']):.3f}, {max(r['accumulate_ms']):.3f}] "
           f"| fp64 oracle on the host (recurrence and path, L given), 16 utterances in 16 threads: {host:.2f} s = {16 / host:.1f} utterances/s")
 tf = statistics.median(fit_s)
 P, T = SIZES[0]
