@@ -358,7 +358,7 @@ int kk_ids_eq_zero(const int64_t *ids, uint8_t *mask, int64_t n, void *stream);
 int kk_shift_right(const float *mel, float *out, int B, int T, int M, void *stream);
 
 /* ---- autoregressive decode (KokoroGenerator.generate, model/generator.py:24-127; incremental attention with a KV cache,
- * transformers.py:237-253): the per-frame launches take the frame index t from DEVICE memory (*t_dev), so that ONE captured
+ * transformers.py:237-253; kk_decode.hip): the per-frame launches take the frame index t from DEVICE memory (*t_dev), so that ONE captured
  * hipGraph of a decoder step is replayed for every frame.
  * prologue: frame_in[B,M] = mel_all[:, t, :] (mel_all [B, L1, M]: row 0 = the all-zero first input, row t+1 = frame t's output),
  *   pe_row[H] = pe[t], cos_row / sin_row [64] = the RoPE tables' row t (the step's K is rotated by its absolute position,
@@ -371,7 +371,7 @@ int kk_decode_cache_append(const void *nrm, void *q, void *kcache, void *vcache,
 int kk_decode_epilogue(const float *frame_out, const float *stop, float *mel_all, float *stop_all, int *t_dev, int B, int L1, int M,
                        void *stream);
 
-/* ---- batched synthesis (KokoroEngine.generate_batch; kk_synth.hip): row b of a padded batch gets what the B = 1 path gives
+/* ---- batched synthesis (KokoroEngine.generate_batch; kk_decode.hip): row b of a padded batch gets what the B = 1 path gives
  * utterance b alone.  (Its variance predictors: kk_im2col3_fwd, kk_groupnorm_relu_fwd and kk_rowdot_fwd with `lens`, above.)
  * decode_epilogue_rows: kk_decode_epilogue for the rows with done[b] == 0, then the stop rule of model/generator.py:67-88 applied to
  *   row b alone: from t >= min_b[b], stop when sigmoid(stop[b]) > (t < expected_b[b] ? thr : min(thr, post_thr)), else, once 30
@@ -381,7 +381,7 @@ int kk_decode_epilogue_rows(const float *frame_out, const float *stop, float *me
                             int *frames, int *live, const int *min_b, const int *expected_b, const int *max_b, int B, int L1, int M,
                             float stop_threshold, float post_expected_stop_threshold, void *stream);
 
-/* ---- continuous batching of the decode (KokoroEngine.generate_stream; kk_stream.hip): a pool of S slots of `cap` frames, every slot
+/* ---- continuous batching of the decode (KokoroEngine.generate_stream; kk_decode.hip, the attention kk_attn_fwd.hip): a pool of S slots of `cap` frames, every slot
  * with its own frame index, so that a finished row's slot is refilled while the others go on.  All state is int32 [S]: t_rows (the
  * slot's frame index), done, frames, klen (self-attention keys), clen (cross-attention keys), min_b / expected_b / max_b.  H = heads*64.
  * attn_decode_rows: kk_attn_fwd's Sq = 1 kernel with a key count per row.  q, out [S, H]; K / V: key j of slot s at

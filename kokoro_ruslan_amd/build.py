@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libkokoro_hip.so")
-SOURCES = ["kk_core.hip", "kk_gemm.hip", "kk_gemm16.hip", "kk_gemm16x.hip", "kk_attn.hip", "kk_attn_fwd.hip", "kk_attn_bwd.hip", "kk_norm.hip", "kk_elem.hip", "kk_loss.hip", "kk_optim.hip", "kk_dropout.hip", "kk_comm.hip", "kk_encstack.hip", "kk_chain.hip", "kk_synth.hip", "kk_stream.hip", "kk_prosody.hip", "kk_vocoder.hip", "kk_griffinlim.hip", "kk_denoise.hip", "kk_loudness.hip", "kk_features.hip", "kk_resample.hip", "kk_dtw.hip", "kk_spectral.hip", "kk_align.hip", "kk_longform.hip"]
+SOURCES = ["kk_core.hip", "kk_gemm.hip", "kk_gemm16.hip", "kk_gemm16x.hip", "kk_attn.hip", "kk_attn_fwd.hip", "kk_attn_bwd.hip", "kk_norm.hip", "kk_elem.hip", "kk_loss.hip", "kk_optim.hip", "kk_dropout.hip", "kk_comm.hip", "kk_encstack.hip", "kk_chain.hip", "kk_decode.hip", "kk_prosody.hip", "kk_vocoder.hip", "kk_griffinlim.hip", "kk_denoise.hip", "kk_loudness.hip", "kk_features.hip", "kk_resample.hip", "kk_dtw.hip", "kk_spectral.hip", "kk_align.hip", "kk_longform.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
 
 
@@ -61,7 +61,7 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         if os.path.exists(stamp):
             os.remove(stamp)
     headers = [os.path.join(CSRC, "kk_common.h"), os.path.join(os.path.dirname(HERE), "include", "kokoro_hip.h")]
-    headers += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h") and not f.startswith(("kk_common", "kk_attn", "kk_gemm16_", "kk_gemm16x_", "kk_stop_rule", "kk_fft"))]      # included widely
+    headers += [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h") and not f.startswith(("kk_common", "kk_attn", "kk_gemm16_", "kk_gemm16x_", "kk_fft"))]      # included widely
     attn_h, incs = ["kk_attn.h", "kk_attn_host.h"], [f for f in sorted(os.listdir(CSRC)) if f.endswith(".inc")]
     gemm_dev = ["kk_gemm16_dev.h"]      # device code shared by the two bf16 GEMM bodies
     extra_deps = {      # what single sources include besides the headers above
@@ -70,8 +70,6 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         "kk_attn.hip": attn_h,
         "kk_attn_fwd.hip": attn_h + ["kk_attn_fwd3.h"],
         "kk_attn_bwd.hip": attn_h + incs,      # the .inc files: bodies of the DMA-staged backward kernels
-        "kk_synth.hip": ["kk_stop_rule.h"],      # the stop rule of a row, shared by the two decode epilogues
-        "kk_stream.hip": ["kk_stop_rule.h"],
         "kk_features.hip": ["kk_fft.h"],      # the 1024-point real STFT of one wave, shared by the three audio sources
         "kk_griffinlim.hip": ["kk_fft.h"],
         "kk_denoise.hip": ["kk_fft.h"],

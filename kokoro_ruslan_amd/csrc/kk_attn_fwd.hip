@@ -537,19 +537,39 @@ __global__ __launch_bounds__(256) void attn_keep_gen_kernel(const KeepGenArgs g)
     }
 }
 
-// ------------------------------------------------------------------ decode: one query per (batch, head)
+// ------------------------------------------------------------------ decode: one query per (row, head)
 // Sq == 1 (the incremental path of transformers.py:237-253: a decoder step against the KV cache / against the memory), no dropout.
-// The tiled kernels above would run one live row of a 128-row block; here a workgroup is one (batch, head): 16 waves = 256 key groups
+// The tiled kernels above would run one live row of a 128-row block; here a workgroup is one (row, head): 16 waves = 256 key groups
 // x 4 lanes (16 of the 64 dims each), scores kept in LDS between the two passes (max, then exp / sum / P.V), fp32 throughout.
+// Two callers: kk_attn_fwd at Sq = 1 (every row over all Sk keys, rows Sk * ld apart) and kk_attn_decode_rows (row b over its first
+// klen[b] keys, explicit slot strides; nothing at or past klen[b] is loaded).  One kernel, so a key count and the equivalent key mask
+// give the same bits.
+constexpr int DECODE_MAX_KEYS = 8192;                                     // (the LDS score array holds Sk floats)
+struct DecodeArgs {
+    const void *Q, *K, *V;
+    void *Out;
+    float *LSEo;
+    const int *klen;                                                      // keys of row b, clamped to [0, Sk]; nullptr: Sk for every row
+    const uint8_t *key_mask;
+    int heads, Sk;
+    int64_t ldq, k_slot, ldk, v_slot, ldv, ldout;                         // row b of Q / K / V / Out at b * ldq / k_slot / v_slot / ldout
+    float scale;
+};
+
 template <typename T>
-__global__ __launch_bounds__(1024) void attn_decode_kernel(AttnArgs a) {
+__global__ __launch_bounds__(1024) void attn_decode_kernel(DecodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float dsm[];          // [Sk] scores | [16 waves][64] partial outputs | [32] reductions
     float *sc = dsm, *part = dsm + ((a.Sk + 3) & ~3), *red = part + 16 * 64;
     const int b = blockIdx.x / a.heads, hh = blockIdx.x % a.heads;
     const int tid = threadIdx.x, kg = tid >> 2, dq = (tid & 3) * 16, lane = tid & 63, wave = tid >> 6;
+    int n = a.Sk;                                                         // (the same in every lane of the workgroup)
+    if (a.klen) {
+        n = a.klen[b];
+        n = n < 0 ? 0 : (n > a.Sk ? a.Sk : n);
+    }
     const T *Q = static_cast<const T *>(a.Q) + (int64_t)b * a.ldq + hh * 64 + dq;
-    const T *Kb = static_cast<const T *>(a.K) + (int64_t)b * a.Sk * a.ldk + hh * 64 + dq;
-    const T *Vb = static_cast<const T *>(a.V) + (int64_t)b * a.Sk * a.ldv + hh * 64 + dq;
+    const T *Kb = static_cast<const T *>(a.K) + (int64_t)b * a.k_slot + hh * 64 + dq;
+    const T *Vb = static_cast<const T *>(a.V) + (int64_t)b * a.v_slot + hh * 64 + dq;
     const uint8_t *km = a.key_mask ? a.key_mask + (int64_t)b * a.Sk : nullptr;
     float qv[16];
 #pragma unroll
@@ -560,7 +580,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(AttnArgs a) {
     const float c2 = a.scale * 1.4426950408889634f;
     float mx = -INFINITY;
 #pragma unroll 2
-    for (int j = kg; j < a.Sk; j += 256) {                                // 256 key groups x 4 lanes (16 of the 64 dims each)
+    for (int j = kg; j < n; j += 256) {                                   // 256 key groups x 4 lanes (16 of the 64 dims each)
         const bool masked = km && km[j];
         float d = 0.f;
         if (!masked) {
@@ -588,7 +608,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(AttnArgs a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll 2
-    for (int j = kg; j < a.Sk; j += 256) {
+    for (int j = kg; j < n; j += 256) {
         const float s = sc[j];
         if (s == -INFINITY) continue;
         const T *vr = Vb + (int64_t)j * a.ldv;
@@ -624,6 +644,12 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(AttnArgs a) {
         *out = (T)o;
         if (tid == 0) a.LSEo[(int64_t)b * a.heads + hh] = lt > 0.f ? (mm + __builtin_amdgcn_logf(lt)) * 0.6931471805599453f : INFINITY;
     }
+}
+
+void launch_decode(const DecodeArgs &a, int rows, int bf16, hipStream_t s) {
+    const size_t lds = (size_t)(((a.Sk + 3) & ~3) + 16 * 64 + 32) * sizeof(float);          // (as the kernel carves dsm)
+    if (bf16) hipLaunchKernelGGL(attn_decode_kernel<__bf16>, dim3(rows * a.heads), dim3(1024), lds, s, a);
+    else hipLaunchKernelGGL(attn_decode_kernel<float>, dim3(rows * a.heads), dim3(1024), lds, s, a);
 }
 
 }  // namespace
@@ -662,11 +688,13 @@ static int attn_fwd_impl(const float *Q, const float *K, const float *V, float *
 #ifdef KK_TUNING_HOOKS
     if (a.dbg & (256 | 4096)) a.DeltaOut = static_cast<float *>(g_attn_trace);
 #endif
-    if (Sq == 1 && a.seed == nullptr && !causal && Sk <= 8192 && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 &&
+    if (Sq == 1 && a.seed == nullptr && !causal && Sk <= DECODE_MAX_KEYS && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 &&
         (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V) & 15) == 0) {  // a decoder step of the incremental path: one (batch, head) per workgroup
-        const size_t lds = (size_t)(((Sk + 3) & ~3) + 16 * 64 + 32) * sizeof(float);
-        if (io_bf16) hipLaunchKernelGGL(attn_decode_kernel<__bf16>, dim3(B * heads), dim3(1024), lds, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(attn_decode_kernel<float>, dim3(B * heads), dim3(1024), lds, (hipStream_t)stream, a);
+        DecodeArgs d;
+        d.Q = Q; d.K = K; d.V = V; d.Out = O; d.LSEo = LSE; d.klen = nullptr; d.key_mask = key_mask;
+        d.heads = heads; d.Sk = Sk; d.ldq = ldq; d.k_slot = (int64_t)Sk * ldk; d.ldk = ldk; d.v_slot = (int64_t)Sk * ldv; d.ldv = ldv;
+        d.ldout = ldo; d.scale = scale;
+        launch_decode(d, B, io_bf16, (hipStream_t)stream);
         KK_LAUNCH_CHECK("kk_attn_fwd");
         return 0;
     }
@@ -742,6 +770,25 @@ extern "C" int kk_attn_fwd_rb(const float *Q, const float *K, const float *V, fl
                "kk_attn_fwd_rb: needs dropout, bf16 storage and a keep-bit array of a shape that has one (kk_attn_keep_bytes)");
     return attn_fwd_impl(Q, K, V, O, LSE, B, heads, Sq, Sk, ldq, ldk, ldv, ldo, key_mask, causal, scale, seed, site, p_drop, math, io_bf16,
                          const_cast<void *>(keep), stream, 1);
+}
+
+// The decode kernel of kk_attn_fwd's Sq = 1 path with a key count per row and explicit slot strides (KokoroEngine.generate_stream: slot s
+// of a pool at its own frame): q, out [S, heads * 64].
+extern "C" int kk_attn_decode_rows(const void *q, const void *K, const void *V, void *out, float *lse, const int *klen,
+                                   const uint8_t *key_mask, int S, int heads, int Sk, int64_t k_slot, int64_t ldk, int64_t v_slot,
+                                   int64_t ldv, float scale, int bf16, void *stream) {
+    static_assert(DECODE_MAX_KEYS == 8192, "the message below names the limit");
+    KK_REQUIRE(q && K && V && out && lse && klen && S > 0 && heads > 0 && Sk > 0 && Sk <= DECODE_MAX_KEYS, "kk_attn_decode_rows: bad args (Sk <= 8192)");
+    KK_REQUIRE(ldk % 4 == 0 && ldv % 4 == 0 && k_slot % 4 == 0 && v_slot % 4 == 0 && ldk >= (int64_t)heads * 64 && ldv >= (int64_t)heads * 64,
+               "kk_attn_decode_rows: strides must be multiples of 4 elements and hold a frame");
+    KK_REQUIRE((((uintptr_t)q | (uintptr_t)K | (uintptr_t)V | (uintptr_t)out) & 15) == 0, "kk_attn_decode_rows: operands must be 16-byte aligned");
+    DecodeArgs d;
+    d.Q = q; d.K = K; d.V = V; d.Out = out; d.LSEo = lse; d.klen = klen; d.key_mask = key_mask;
+    d.heads = heads; d.Sk = Sk; d.ldq = d.ldout = (int64_t)heads * 64; d.k_slot = k_slot; d.ldk = ldk; d.v_slot = v_slot; d.ldv = ldv;
+    d.scale = scale;
+    launch_decode(d, S, bf16, (hipStream_t)stream);
+    KK_LAUNCH_CHECK("kk_attn_decode_rows");
+    return 0;
 }
 
 // The keep bits of n <= 16 attention launches in one launch (see attn_keep_gen_kernel); sites: HOST array read during the call.

@@ -2176,7 +2176,7 @@ class KokoroEngine:
 
     def _stream_step(self, S, cap, stop_threshold, post_expected_stop_threshold):
         """One decoder step of a pool of S slots of `cap` frames, slot s at its own frame t_s: kk_decode_prologue_rows, _decoder_step
-        with the row kernels of kk_stream.hip, kk_decode_epilogue_slots.  Self-attention: kk_attn_decode_rows over the slot-major
+        with the row kernels of kk_decode.hip, kk_decode_epilogue_slots.  Self-attention: kk_attn_decode_rows over the slot-major
         caches [S][cap][H] with klen[s] = t_s + 1 keys (0 for a finished slot), no mask and no zero-filled cache.  Cross-attention:
         the same kernel over the slot's rows of the K|V pool [S*cap, 2H*layers] with clen[s] = the admitted group's frame count and
         the slot frame mask [S, cap].  The plain GEMMs are one k-slice each (split_k = 1: no fp32 atomics), so a replayed step

@@ -1,6 +1,8 @@
-"""GPU suite, kernel level: the continuous-batching kernels of kk_stream.hip (KokoroEngine.generate_stream).  The row attention
-against a float64 softmax and, bit for bit, against kk_attn_fwd at Sq = 1 over the same live keys; prologue, cache append, epilogue
-and slot admission against plain torch indexing."""
+"""GPU suite, kernel level: the decode step's state kernels of kk_decode.hip in both forms, lockstep (KokoroEngine.generate,
+generate_batch) and per slot (generate_stream), and the row form of the decode attention (kk_attn_decode_rows, kk_attn_fwd.hip).  The row
+attention against a float64 softmax and, bit for bit, against kk_attn_fwd at Sq = 1 over the same live keys: a key count and the
+equivalent key mask select the same arithmetic in one kernel.  Prologue, cache append, epilogue and slot admission against plain torch
+indexing.  (The lockstep epilogue with the stop rule: test_synth_kernels_gpu.py.)"""
 import pytest
 import torch
 
@@ -121,6 +123,26 @@ def _i32(x):
     return torch.tensor(x, dtype=torch.int32).cuda()
 
 
+@pytest.mark.parametrize("t", [0, 5, 7])                       # 7 = L1 - 2, the last legal frame
+def test_decode_prologue(kk, t):
+    """The lockstep form, one workgroup: B * M = 280 and H = 320 reach the second pass of its 256-thread loops."""
+    n_pos, l1, m, h, b = 16, 9, 20, 320, 14
+    g = torch.Generator().manual_seed(2)
+    mel_all = torch.randn(b, l1, m, generator=g).cuda()
+    pe, cos, sin = (torch.randn(n_pos, n, generator=g).cuda() for n in (h, 64, 64))
+    frame_in, pe_row, cos_row, sin_row = (torch.full(sh, 9.0, device="cuda") for sh in ((b, m), (h,), (64,), (64,)))
+    mask0 = torch.arange(1, l1, dtype=torch.uint8)              # every key still hidden, each byte its own value
+    key_mask, t_dev = mask0.clone().cuda(), _i32([t])
+    kk.call("kk_decode_prologue", mel_all, frame_in, pe, pe_row, cos, sin, cos_row, sin_row, key_mask, t_dev, b, l1, m, h)
+    torch.cuda.synchronize()
+    assert torch.equal(frame_in, mel_all[:, t]) and torch.equal(pe_row, pe[t])
+    assert torch.equal(cos_row, cos[t]) and torch.equal(sin_row, sin[t])
+    want_mask = mask0.clone()
+    want_mask[t] = 0
+    assert torch.equal(key_mask.cpu(), want_mask)
+    assert t_dev.item() == t
+
+
 def test_decode_prologue_rows(kk):
     g = torch.Generator().manual_seed(3)
     mel_all = torch.randn(S2, L1, M, generator=g).cuda()
@@ -138,6 +160,23 @@ def test_decode_prologue_rows(kk):
     assert t.tolist() == T_ROWS and done.tolist() == DONE
 
 
+@pytest.mark.parametrize("t", [0, 5])
+@pytest.mark.parametrize("bf16", [False, True])
+def test_decode_cache_append(kk, bf16, t):
+    """The lockstep form over time-major caches [L][B * H]: B * H = 384 takes two workgroups."""
+    b, h, rows = 3, 128, 6
+    dt = torch.bfloat16 if bf16 else torch.float32
+    nrm = torch.randn(b, 3 * h, generator=torch.Generator().manual_seed(9)).cuda().to(dt)
+    q, Kc, Vc = (torch.full(sh, 7.0, device="cuda", dtype=dt) for sh in ((b * h,), (rows, b * h), (rows, b * h)))
+    kk.call("kk_decode_cache_append", nrm, q, Kc, Vc, _i32([t]), b, h, 1 if bf16 else 0)
+    torch.cuda.synchronize()
+    assert torch.equal(q, nrm[:, :h].reshape(-1))
+    for cache, lo in ((Kc, h), (Vc, 2 * h)):
+        want = torch.full_like(cache, 7.0)                     # every other row still holds the sentinel
+        want[t] = nrm[:, lo:lo + h].reshape(-1)
+        assert torch.equal(cache, want)
+
+
 @pytest.mark.parametrize("bf16", [False, True])
 def test_decode_cache_append_rows(kk, bf16):
     g = torch.Generator().manual_seed(4)
@@ -152,6 +191,22 @@ def test_decode_cache_append_rows(kk, bf16):
         if not d:
             wq[s], wk[s, ts], wv[s, ts] = nrm[s, :HS], nrm[s, HS:2 * HS], nrm[s, 2 * HS:]
     assert torch.equal(q, wq) and torch.equal(Kc, wk) and torch.equal(Vc, wv)       # (the finished row 4: byte-identical)
+
+
+def test_decode_epilogue(kk):
+    """The lockstep form without a stop rule, one workgroup: B = 260 reaches the second pass of the stop-logit loop (and B * M = 520
+    the third of the frame loop)."""
+    b, m, l1, t = 260, 2, 5, 2
+    g = torch.Generator().manual_seed(7)
+    frame_out, stop = torch.randn(b, m, generator=g).cuda(), torch.randn(b, generator=g).cuda()
+    mel_all, stop_all = torch.full((b, l1, m), 7.0, device="cuda"), torch.full((l1 - 1, b), 7.0, device="cuda")
+    t_dev = _i32([t])
+    kk.call("kk_decode_epilogue", frame_out, stop, mel_all, stop_all, t_dev, b, l1, m)
+    torch.cuda.synchronize()
+    want_mel, want_stop = torch.full_like(mel_all, 7.0), torch.full_like(stop_all, 7.0)
+    want_mel[:, t + 1], want_stop[t] = frame_out, stop
+    assert torch.equal(mel_all, want_mel) and torch.equal(stop_all, want_stop)
+    assert t_dev.item() == t + 1
 
 
 def test_decode_epilogue_slots(kk):

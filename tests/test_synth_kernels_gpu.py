@@ -1,5 +1,5 @@
 """GPU suite, kernel level: the batched-synthesis kernels (KokoroEngine.generate_batch: the variance predictors' kernels with the rows'
-lengths, the decode epilogue of kk_synth.hip) against plain torch restatements of what each row would get at B = 1."""
+lengths, the decode epilogue of kk_decode.hip) against plain torch restatements of what each row would get at B = 1."""
 import math
 
 import pytest
