@@ -11,7 +11,8 @@ and the kernel's error, normalised the same way, must be <= 4 E_ref + 2^-22 (4x:
 the restatement happens to be exact); a bf16 output gets one more bf16 rounding, 2^-8.  Every check prints both numbers
 (pytest -s); docs/LAB_NOTES.md "Norm kernels vs fp64" holds what was measured."""
 import functools
-import math
+import os
+import sys
 
 import pytest
 import torch
@@ -19,13 +20,14 @@ import torch.nn.functional as F
 
 from oracle import kokoro_oracle as O
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fp64_bounds as FB  # noqa: E402
+from fp64_bounds import BF16_ROUND, FLT_EPS, NAN, Guarded, gvec  # noqa: E402
+from fp64_bounds import ln_bwd_formula as _ln_formula, rms_bwd_formula as _rms_formula  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
-FLT_EPS = torch.finfo(torch.float32).eps
-FLOOR = 2.0 ** -22
-BF16_ROUND = 2.0 ** -8
-SENT = -1024.0               # guard value (exact in bf16 too); no kernel output of these tests equals it by construction of the guards
-NAN = float("nan")
+bounded = functools.partial(FB.bounded, tag="norm-fp64")     # kernel error <= 4 E_ref + 2^-22 (+ extra); prints "[norm-fp64] ..."
 
 
 @pytest.fixture(scope="module")
@@ -45,68 +47,11 @@ def _r16(t):
     return t.bfloat16().float()
 
 
-class Guarded:
-    """A [rows, cols] device view (row stride ld >= cols) inside a buffer of guard rows / columns that hold SENT."""
-
-    def __init__(self, rows, cols, dtype=torch.float32, fill=NAN, ld=None, pad=4):
-        self.rows, self.cols, self.pad = rows, cols, pad
-        self.ld = ld or cols
-        self.buf = torch.full((rows + 2 * pad, self.ld), SENT, dtype=dtype, device="cuda")
-        self.t = self.buf[pad:pad + rows, :cols]
-        if torch.is_tensor(fill):
-            self.t.copy_(fill)
-        else:
-            self.t.fill_(fill)
-
-    def intact(self):
-        b = self.buf.clone()
-        b[self.pad:self.pad + self.rows, :self.cols] = SENT
-        return bool((b == SENT).all())
-
-
-def gvec(n, fill):
-    return Guarded(1, n, fill=fill)
-
-
-def nerr(got, ref64):
-    got, ref64 = got.detach().double().cpu(), ref64.detach().double().cpu()
-    assert got.shape == ref64.shape, (got.shape, ref64.shape)
-    assert bool(torch.isfinite(got).all()), "non-finite values"
-    scale, err = float(ref64.abs().max()), float((got - ref64).abs().max())
-    if scale == 0.0:
-        return 0.0 if err == 0.0 else math.inf
-    return err / scale
-
-
-def bounded(what, got, ref32, ref64, extra=0.0):
-    """kernel error <= 4 E_ref + 2^-22 (+ extra), all normalised by max|fp64|."""
-    e_ref, e_k = nerr(ref32, ref64), nerr(got, ref64)
-    bound = 4.0 * e_ref + FLOOR + extra
-    ratio = e_k / e_ref if e_ref > 0 else (0.0 if e_k == 0 else math.inf)
-    print(f"[norm-fp64] {what}: E_ref={e_ref:.3e} kernel={e_k:.3e} kernel/E_ref={ratio:.2f} bound={bound:.3e} "
-          f"kernel/bound={e_k / bound:.2f}")
-    assert e_k <= bound, f"{what}: kernel error {e_k:.3e} > 4 x {e_ref:.3e} + 2^-22{' + 2^-8' if extra else ''} = {bound:.3e}"
-
-
 # ------------------------------------------------------------------ part 1: exact column sums
 # (rows, H): second trip with a ragged R-group at NV1/R4 | NV2, dead lanes in the last slab | NV4/R2 at nv = 3 | NV8/R1 begins, 4 live
 # columns in slab 5 | NV8/R1 | fewer rows than one workgroup, H < 256 | one wave, exactly one workgroup, one more
 EXACT_SHAPES = [(4096 + 5, 64), (4096 + 16 * 3 + 1, 320), (2048 + 3, 768), (2048 + 2, 1028), (1024 + 1, 2048), (7, 80), (1, 512),
                 (4, 512), (5, 512)]
-
-
-def _ln_formula(dy, x, gamma, mean, rstd):
-    xh = (x - mean[:, None]) * rstd[:, None]
-    dg = dy * gamma
-    s1, s2 = dg.mean(1, keepdim=True), (dg * xh).mean(1, keepdim=True)
-    return rstd[:, None] * (dg - s1 - xh * s2), dy * xh
-
-
-def _rms_formula(dy, x, gain, rstd):
-    rs = rstd[:, None]
-    dg = dy * gain
-    k = (dg * x).mean(1, keepdim=True) * rs * rs * rs
-    return rs * dg - x * k, dy * x * rs
 
 
 def _prove_exact(terms64, start64, what):
