@@ -28,6 +28,7 @@
 #define KK_QKV_AUX 16
 #endif
 #include "kk_gemm16.h"
+#include "kk_group_sync.h"
 #include <algorithm>
 #include <float.h>
 #include <math.h>
@@ -55,65 +56,13 @@ namespace {
 using chain_a::AttnArgs;
 using chain_t::SubOutArgs;
 
-// sync words (uint32): [0] error (a spin ran out), [1] placement mismatches seen, [32 + 32 g] arrivals of group g, [+16] exits.
-struct ChainSync {
-    unsigned *arrive_ctr, *leave, *err;
-    unsigned target, members;
-    bool dead, local;
-    __device__ __forceinline__ void init(unsigned *words, int group, int nmembers, bool xcd_local) {
-        err = words;
-        arrive_ctr = words + 32 + 32 * group;
-        leave = arrive_ctr + 16;
-        target = 0;
-        members = (unsigned)nmembers;
-        dead = false;
-        local = xcd_local;
-    }
-    __device__ __forceinline__ void barrier() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // each wave: its stores have been acknowledged by the L2
-        __syncthreads();
-        target += members;
-        if (threadIdx.x == 0 && !dead) {
-            // XCD-local form: the add executes in this XCD's L2 (no scope bits) and the poll is an L1-bypassing load of the same
-            // L2 line; the agent-scope form makes a round trip through the fabric (~1.2 - 2 us per barrier)
-            if (local) __hip_atomic_fetch_add(arrive_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else __hip_atomic_fetch_add(arrive_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            unsigned spins = 0;
-            while (__hip_atomic_load(arrive_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1u << 22)) {
-                    __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    dead = true;
-                    break;
-                }
-                if ((spins & 1023u) == 0u && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                    dead = true;
-                    break;
-                }
-            }
+// group barrier (sync words: kk_group_sync.h): XCD-local atomics unless the launch asks for agent scope; the A/B flavour with plain
+// loads takes the acquire fence behind every barrier
 #ifdef KK_CHAIN_PLAIN
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");        // this CU's L1 forgets what it holds: the plain loads below go to the L2
+struct ChainSyncPolicy { static constexpr bool XCD_LOCAL = true, ACQUIRE = true, SPLIT = false; };
+#else
+struct ChainSyncPolicy { static constexpr bool XCD_LOCAL = true, ACQUIRE = false, SPLIT = false; };
 #endif
-        }
-        __syncthreads();
-    }
-    __device__ __forceinline__ void exit() {
-        if (threadIdx.x == 0) {
-            unsigned old;
-            if (local) old = __hip_atomic_fetch_add(leave, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else old = __hip_atomic_fetch_add(leave, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old == members - 1u) {
-                if (local) {
-                    __hip_atomic_fetch_sub(arrive_ctr, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_sub(leave, members, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                } else {
-                    __hip_atomic_store(arrive_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(leave, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-    }
-};
 
 struct ChainSA {
     G16Args qkv;                 // phase 1: q|k|v projection + head norm (+ RoPE)
@@ -142,7 +91,7 @@ __global__ __launch_bounds__(512) void chain_sa_fwd_kernel(const ChainSA c) {
         if (tr) tr[15] = xcc;
         if ((int)xcc != item) __hip_atomic_fetch_add(c.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    ChainSync sy;
+    GroupSync<ChainSyncPolicy> sy;
     sy.init(c.sync, item, members, c.local_sync != 0);
 
     // ---- phase 1: the item's q|k|v tiles (the XCD sweep of g16x_body IS the item: 256 tiles, 32 per XCD, n fastest)

@@ -312,6 +312,52 @@ __device__ __forceinline__ void kk_drop_mul4(uint32_t seed, uint32_t site, uint6
     m[3] = (h1 >> 16) < t ? 0.f : inv_keep;
 }
 
+// Dropout on the probabilities.  The keep decision of element (b, head, q, key) is a 16-bit field of a 32-bit hash of
+// (q, key >> 1), keyed by (seed, site, b, head): lanes that own a query get two decisions (key, key^1) per hash, and
+// all three kernels evaluate the same function, so the backward regenerates the forward's mask exactly.  p is
+// quantised to 1/65536 and 1/(1-p) is taken from the quantised value, so the mask stays unbiased.
+struct ProbDrop {
+    uint32_t thr, key, sk2;      // thr == 0: dropout off
+    float inv_keep;
+    // p > 0 turns it on; bh = b * heads + head
+    __device__ __forceinline__ void init(uint32_t seed, uint32_t site, float p, int bh, int Sk) {
+        thr = 0u;
+        if (p > 0.f) {
+            thr = (uint32_t)(p * 65536.f + 0.5f);
+            thr = thr > 65535u ? 65535u : thr;
+        }
+        key = thr ? kk_hash(seed, site, (uint64_t)bh) : 0u;
+        inv_keep = thr ? 65536.f / (float)(65536u - thr) : 1.f;
+        sk2 = (uint32_t)(Sk + 1) >> 1;
+    }
+    // The same from an argument block of the library, whose seed is a device pointer that may be null (dropout off).  NOT a forward to the
+    // init above: the seed must be loaded behind the threshold test, and every way of saying so through the other init (a lazy seed, the
+    // null test as an argument) changed the code of the backward kernels (docs/LAB_NOTES.md, "Encoder stack: shared sources").
+    template <typename A> __device__ __forceinline__ void init(A &a, int b, int hh) {
+        thr = 0u;
+        if (a.seed && a.p_drop > 0.f) {
+            thr = (uint32_t)(a.p_drop * 65536.f + 0.5f);
+            thr = thr > 65535u ? 65535u : thr;
+        }
+        key = thr ? kk_hash(*a.seed, a.site, (uint64_t)(b * a.heads + hh)) : 0u;
+        inv_keep = thr ? 65536.f / (float)(65536u - thr) : 1.f;
+        sk2 = (uint32_t)(a.Sk + 1) >> 1;
+    }
+    __device__ __forceinline__ uint32_t row(int q, int key0) const { return (uint32_t)q * sk2 + ((uint32_t)key0 >> 1); }
+    // Two xorshift-multiply rounds with 24-bit multipliers: v_mul_u32_u24 is full rate, v_mul_lo_u32 quarter rate, and
+    // the hash is a third of the softmax VALU work.  On the (q, key/2) counter lattice it tests like "lowbias32"
+    // (keep rate, key/query/diagonal correlations at the 1e-3 noise floor, 8-bit pattern chi-square ~1; sweep in
+    // tools/dropout_hash_quality.py); injective on counters below 2^24 (S <= 4096), distinct (b, head) differ by `key`.
+    __device__ __forceinline__ uint32_t hash(uint32_t x) const {
+        x ^= key;
+        x ^= x >> 16; x = __umul24(x, 0xb5352du); x ^= x >> 13; x = __umul24(x, 0xca68b5u); x ^= x >> 16;
+        return x;
+    }
+    // keep decisions; the 1/(1-p) of the kept elements is folded into an operand or an output scale by each kernel
+    __device__ __forceinline__ bool keep_lo(uint32_t h) const { return (h & 0xFFFFu) >= thr; }   // even key
+    __device__ __forceinline__ bool keep_hi(uint32_t h) const { return (h >> 16) >= thr; }       // odd key
+};
+
 // per-head RMSNorm(64) (+ RoPE) of one (row, head) vector held by 16 lanes, one float4 each (sub = lane & 15): shared by
 // headnorm_rope_fwd_kernel and the q|k|v GEMM's epilogue so that the two give the same bits.
 // rotate_half(n)[d] = -n[d+32] (d<32), n[d-32] (d>=32)   (positional_encoding.py:152-157)

@@ -21,6 +21,7 @@
 // barrier, the next chunk's loads in flight under the current chunk's MFMAs) and runs the epilogue (head norm + RoPE,
 // bias, GLU gate + dropout) on its own row-major LDS tile; units are dealt workgroup-first, so a phase is one pass.
 #include "kk_common.h"
+#include "kk_group_sync.h"
 #include <algorithm>
 #include <float.h>
 #include <math.h>
@@ -56,60 +57,7 @@ __device__ __forceinline__ float4 unpack4(u32x2 u) {
     return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 
-// ---- group barrier ---------------------------------------------------------------------------------------------------
-// sync words (uint32): [0] = error flag (a spin ran out), [32 + 32 g] = arrivals of group g, [32 + 32 g + 16] = exits.
-// The counters are zero between launches: the last member to leave a launch resets them (every member has passed every
-// barrier by then), so a replayed hipGraph needs no memset node in front of the launch.
-struct GroupSync {
-    unsigned *arrive_ctr, *leave, *err;
-    unsigned target, members;
-    bool dead;
-    __device__ __forceinline__ void init(unsigned *words, int group, int nmembers) {
-        err = words;
-        arrive_ctr = words + 32 + 32 * group;
-        leave = arrive_ctr + 16;
-        target = 0;
-        members = (unsigned)nmembers;
-        dead = false;
-    }
-    // Split barrier: arrive() publishes this workgroup's stores (every store issued before it is visible to every member
-    // after its wait()); between the two a member does work that depends on nobody — it starts the DMA of the weights of
-    // its next GEMM phase there, so that the issue time of up to 96 KB hides behind the arrival of the slowest member.
-    __device__ __forceinline__ void arrive() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // each wave: its write-through stores have been acknowledged
-        __syncthreads();
-        target += members;
-        if (threadIdx.x == 0 && !dead) __hip_atomic_fetch_add(arrive_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __device__ __forceinline__ void wait() {
-        if (threadIdx.x == 0 && !dead) {
-            unsigned spins = 0;
-            while (__hip_atomic_load(arrive_ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1u << 22)) {                        // seconds: a member is not resident / died — give up loudly
-                    __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    dead = true;
-                    break;
-                }
-                if ((spins & 1023u) == 0u && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                    dead = true;
-                    break;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    __device__ __forceinline__ void barrier() { arrive(); wait(); }
-    __device__ __forceinline__ void exit() {
-        if (threadIdx.x == 0) {
-            const unsigned old = __hip_atomic_fetch_add(leave, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old == members - 1u) {
-                __hip_atomic_store(arrive_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(leave, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-};
+// (group barrier between phases, and the layout of the sync words: kk_group_sync.h)
 
 // ---- GEMM phases: operands staged into LDS by the buffer-load-to-LDS DMA, 16x16x32 MFMA tiles ----------------------------
 // A member's share of a phase is [rows of the item] x [its slice of the output columns]:  X (the item's activations,
@@ -301,28 +249,8 @@ __device__ __forceinline__ void phase_qkv(const Ctx &c, const KkEncLayer &L) {
 }
 
 // ---- phase 2: attention of one head (all S <= 128 keys in one pass) ----------------------------------------------------
-// Same orientation and dropout function as attn_fwd_kernel (kk_attn_fwd.hip) / ProbDrop (kk_attn.h): S^T = K.Q^T with a lane owning one
+// Same orientation as attn_fwd_kernel (kk_attn_fwd.hip) and its dropout function itself (ProbDrop, kk_common.h): S^T = K.Q^T with a lane owning one
 // query, so the softmax is in-lane + one xor-32 exchange and P feeds the second MFMA as it lies in the accumulators.
-struct ProbDropE {
-    uint32_t thr, key, sk2;
-    float inv_keep;
-    __device__ __forceinline__ void init(uint32_t seed, uint32_t site, float p, int bh, int Sk) {
-        thr = 0u;
-        if (p > 0.f) {
-            thr = (uint32_t)(p * 65536.f + 0.5f);
-            thr = thr > 65535u ? 65535u : thr;
-        }
-        key = thr ? kk_hash(seed, site, (uint64_t)bh) : 0u;
-        inv_keep = thr ? 65536.f / (float)(65536u - thr) : 1.f;
-        sk2 = (uint32_t)(Sk + 1) >> 1;
-    }
-    __device__ __forceinline__ uint32_t hash(uint32_t x) const {
-        x ^= key;
-        x ^= x >> 16; x = __umul24(x, 0xb5352du); x ^= x >> 13; x = __umul24(x, 0xca68b5u); x ^= x >> 16;
-        return x;
-    }
-};
-
 template <int NSUB>     // 32-key sub-tiles (S <= 32 NSUB)
 __device__ __forceinline__ void attn_head(const Ctx &c, const KkEncLayer &L, int hh, __bf16 *Ks, __bf16 *Vt) {
     constexpr int VP = NSUB * 32 + 8;                           // bf16 per row of the transposed V tile
@@ -377,7 +305,7 @@ __device__ __forceinline__ void attn_head(const Ctx &c, const KkEncLayer &L, int
             kmb[t] = __ballot(km != nullptr && key < S && km[key < S ? key : 0] != 0);
         }
         const float c2 = 0.125f * 1.4426950408889634f;
-        ProbDropE pd;
+        ProbDrop pd;
         pd.init(c.seed, L.site + 3, L.p, b * c.heads + hh, S);
         float p[NSUB][16];
         float mx = -INFINITY;
@@ -420,8 +348,8 @@ __device__ __forceinline__ void attn_head(const Ctx &c, const KkEncLayer &L, int
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
                     const uint32_t hsh = pd.hash(xb + (uint32_t)(frag_row(r, 0) >> 1));
-                    p[sub][r] = (hsh & 0xFFFFu) >= pd.thr ? p[sub][r] : 0.f;
-                    p[sub][r + 1] = (hsh >> 16) >= pd.thr ? p[sub][r + 1] : 0.f;
+                    p[sub][r] = pd.keep_lo(hsh) ? p[sub][r] : 0.f;
+                    p[sub][r + 1] = pd.keep_hi(hsh) ? p[sub][r + 1] : 0.f;
                 }
             }
 #pragma unroll
@@ -707,7 +635,7 @@ __global__ __launch_bounds__(NTHREADS) void enc_stack_fwd_kernel(const KkEncStac
     c.seed = a.seed ? *a.seed : 0u;
     c.smem = smem;
     const int group = a.placement ? blockIdx.x / c.members : blockIdx.x & 7;
-    GroupSync sy;
+    GroupSync<GroupSyncAgent> sy;
     sy.init(a.sync, group, c.members);
     uint64_t *tr = (a.trace && (int)blockIdx.x == a.trace_wg && threadIdx.x == 0) ? a.trace : nullptr;
     c.sub = tr ? tr + 2048 : nullptr;

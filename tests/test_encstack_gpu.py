@@ -2,6 +2,10 @@
 per-kernel sequence it replaces — every tensor the backward reads, for several batch shapes, both workgroup placements
 (groups inside an XCD / groups spread over all XCDs: the hand-offs must not depend on it), dropout on and off — and under
 load: hundreds of back-to-back graph replays beside the other branches of the step must give the same bits every time."""
+import hashlib
+import json
+import os
+
 import pytest
 import torch
 
@@ -157,6 +161,75 @@ def test_fused_encoder_train_steps_track_the_unfused_engine(mods):
             assert e.opt_stats()["skipped"] == 0
     assert torch.isfinite(losses[True]).all()
     assert torch.allclose(losses[True][:, 0], losses[False][:, 0], rtol=3e-2), (losses[True][:, 0], losses[False][:, 0])
+
+
+# ---- bit identity with the commit the digests were recorded at (tools/record_encstack_golden.py) ----------------------------------
+# The comparison above allows 6e-3 per layer (the two paths sum their GEMMs in different orders), so it cannot see a drift in the
+# code the fused launch shares with the library (sub-layer tail, probability dropout, group barrier).  These cases pin the bits of
+# everything the fused forward leaves behind, at the smallest shapes that reach every arm of that code:
+#   default dims, 3 x 50 ragged, dropout : enc_stack_fwd_kernel<512,1536>, attn_head<2>, padded keys, both tails with every mask live, no second item
+#   default dims, 2 x 97, dropout on/off : attn_head<4>; p = 0: thresholds 0, no seed read
+#   smallest dims the launch accepts, 9 x 33 ragged, dropout : enc_stack_fwd_kernel<0,0>, a group walking a second item (b + 8)
+# The last layer's FFN tail writes enc.norm.y in fp32 (the next_y arm without bf16) in every case.  DropPath is live in the layers
+# past the first; the recorder picks a seed at which one tail drops a sample and keeps another (row / S indexing).
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "encstack_parent_digests.json")
+SMALL = dict(hidden=128, heads=2, enc_layers=2, dec_layers=1, enc_ff=128, dec_ff=128, var_filter=32, var_bins=16)
+DIGEST_CASES = {      # id: (ModelDims arguments, B, T, P, ragged, dropout)
+    "default-3x50-ragged-drop": ({}, 3, 96, 50, True, True),
+    "default-2x97-drop": ({}, 2, 160, 97, False, True),
+    "default-2x97-nodrop": ({}, 2, 160, 97, False, False),
+    "small-9x33-ragged-drop": (SMALL, 9, 64, 33, True, True),
+}
+
+
+def _digest(t):
+    t = t.detach().cpu().contiguous()
+    raw = t.reshape(-1).view(torch.uint8).numpy().tobytes()
+    return {"sha256": hashlib.sha256(raw).hexdigest(), "shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+
+
+def fused_encoder_tensors(mods, engines, case, placement, seed):
+    """Everything the fused encoder forward of DIGEST_CASES[case] leaves behind (engines: a dict that keeps one engine per dims)."""
+    _, spec, synthetic = mods
+    kw, B, T, P, ragged, dropout = DIGEST_CASES[case]
+    key = tuple(sorted(kw.items()))
+    if key not in engines:
+        engines[key] = _engine(mods, spec.ModelDims(**kw))
+        engines[key].enc_fused_max_batch = 64
+    e = engines[key]
+    e.train_dropout = dropout
+    assert e._encoder_stack_ok(B, P), "the shape must be served by the fused launch"
+    batch = {k: v.cuda() for k, v in synthetic.synthetic_batch(B, T, P, mel=e.dims.mel, seed=5, ragged=ragged).items()}
+    got, _ = _forward(e, batch, fused=True, placement=placement, seed=seed)
+    assert e.encoder_stack_error() == 0, "a group barrier of the fused encoder timed out"
+    return got
+
+
+def droppath_is_exercised(got, layers, B):
+    """True when some sub-layer tail past the first layer dropped a whole sample (stream out == stream in) and kept another."""
+    for i in range(1, layers):
+        for x_in, x_out in ((got[f"enc{i - 1}.xo"], got[f"enc{i}.xm"]), (got[f"enc{i}.xm"], got[f"enc{i}.xo"])):
+            dropped = [torch.equal(a, b) for a, b in zip(x_in.view(B, -1), x_out.view(B, -1))]
+            if any(dropped) and not all(dropped):
+                return True
+    return False
+
+
+@pytest.fixture(scope="module")
+def digest_engines():
+    return {}
+
+
+@pytest.mark.parametrize("placement", [0, 1])
+@pytest.mark.parametrize("case", list(DIGEST_CASES))
+def test_fused_encoder_bits_match_the_recorded_parent(mods, digest_engines, case, placement):
+    with open(GOLDEN) as f:
+        want = json.load(f)["cases"][case]
+    got = fused_encoder_tensors(mods, digest_engines, case, placement, want["seed"])
+    have = {k: _digest(v) for k, v in got.items()}
+    assert sorted(have) == sorted(want["tensors"])
+    differ = [k for k in have if have[k] != want["tensors"][k]]
+    assert not differ, f"{case}, placement {placement}: {len(differ)} of {len(have)} tensors differ from the recorded bits: {differ[:8]}"
 
 
 def test_unsupported_shapes_fall_back(mods):
