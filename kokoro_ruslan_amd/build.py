@@ -74,8 +74,9 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False, vari
         "kk_griffinlim.hip": ["kk_fft.h"],
         "kk_denoise.hip": ["kk_fft.h"],
         "kk_spectral.hip": ["kk_fft.h"],
-        # bodies compiled into kk_chain.hip: the GEMM and attention forward bodies from their device headers, kk_dropout.hip under KK_BODIES_ONLY
-        "kk_chain.hip": gemm_dev + ["kk_gemm16x_body.h", "kk_gemm16_body.h", "kk_dropout.hip", "kk_attn.h", "kk_attn_fwd3.h"],
+        # bodies compiled into kk_chain.hip: the GEMM and attention forward bodies and the sub-layer tail's row, from their device headers
+        # (kk_tail.h is in the list above already: kk_dropout.hip includes it too)
+        "kk_chain.hip": gemm_dev + ["kk_gemm16x_body.h", "kk_gemm16_body.h", "kk_tail.h", "kk_attn.h", "kk_attn_fwd3.h"],
     }
 
     def compile_one(src: str) -> str:

@@ -9,8 +9,8 @@
 // in the XCD's L2), sc1 loads on the reading side (L1 bypass, served by that L2) — no write-through round trip, no fence.
 //
 // How it is built.  The phases ARE the library's kernels: their bodies (g16x_body, attn_fwd3_body, gemm16_body, sublayer_out_row)
-// are compiled into this translation unit from the same sources (the GEMM and attention bodies from their device headers; KK_BODIES_ONLY
-// drops the host code of kk_dropout.hip; KK_A_AUX / KK_QKV_AUX set the cache policy of the activation loads), and their
+// are compiled into this translation unit from the same device headers (the GEMM and attention bodies from theirs, the tail's row
+// from kk_tail.h; KK_A_AUX / KK_QKV_AUX set the cache policy of the activation loads), and their
 // ARGUMENT BLOCKS are the ones the library's own entry points build: between
 // kk_chain_begin() and kk_chain_launch() the entry points record the launch they would have made instead of making it (kk_common.h:
 // kk_capture).  Same tile policy, same arguments, same arithmetic in the same order — the chained launch stores the bits the four
@@ -19,7 +19,6 @@
 // Placement is an observation, not a contract (MICROARCH "Workgroup dispatch"): every workgroup reads HW_REG_XCC_ID and reports a
 // mismatch in the sync words; the results stay correct under any placement only with KK_CHAIN_SAFE loads / stores (sc1 both sides),
 // which kk_chain_launch selects when asked to (flags bit 0) — the probe measures both.
-#define KK_BODIES_ONLY 1
 #ifdef KK_CHAIN_PLAIN           // (A/B flavour: plain loads behind an agent-scope acquire — buffer_inv sc1 — after every group barrier)
 #define KK_A_AUX 0
 #define KK_QKV_AUX 0
@@ -29,6 +28,7 @@
 #endif
 #include "kk_gemm16.h"
 #include "kk_group_sync.h"
+#include "kk_tail.h"
 #include <algorithm>
 #include <float.h>
 #include <math.h>
@@ -44,9 +44,6 @@ namespace chain_a {
 #include "kk_attn.h"
 #include "kk_attn_fwd3.h"
 }
-namespace chain_t {
-#include "kk_dropout.hip"
-}
 
 KkLaunchCapture *kk_capture_begin();
 KkLaunchCapture *kk_capture_end();
@@ -54,7 +51,6 @@ KkLaunchCapture *kk_capture_end();
 namespace {
 
 using chain_a::AttnArgs;
-using chain_t::SubOutArgs;
 
 // group barrier (sync words: kk_group_sync.h): XCD-local atomics unless the launch asks for agent scope; the A/B flavour with plain
 // loads takes the acquire fence behind every barrier
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(512) void chain_sa_fwd_kernel(const ChainSA c) {
         const int per = c.S / members;                                                // rows of the item per member
         for (int r = wave; r < per; r += 8) {
             const int64_t row = (int64_t)item * c.S + member * per + r;
-            if (c.tail.n != nullptr) chain_t::sublayer_out_row<__bf16, __bf16, 2>(c.tail, row);
+            if (c.tail.n != nullptr) sublayer_out_row<__bf16, __bf16, 2>(c.tail, row);
         }
     }
     stamp(7);

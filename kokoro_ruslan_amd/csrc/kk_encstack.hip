@@ -528,8 +528,11 @@ __device__ __forceinline__ void phase_lin2(const Ctx &c, const KkEncLayer &L) {
     }
 }
 
-// ---- phases 4 and 7: sub-layer tail, one wave per row (the arithmetic of sublayer_out_fwd_kernel, kk_dropout.hip) ------
+// ---- phases 4 and 7: sub-layer tail, one wave per row ------
 //   x_out = res + masks * [RMSNorm](y);  n = LayerNorm(x_out)
+// tail_row MIRRORS sublayer_out_row of kk_tail.h (NV = 2) with sc1 buffer loads and stores; as one shared core this kernel gained
+// scalar spills (docs/LAB_NOTES.md "Sub-layer tail forward: one core").  Its bits are pinned by
+// tests/test_encstack_gpu.py::test_fused_encoder_bits_match_the_recorded_parent: a change to either copy goes into the other.
 template <bool FFN, typename TN, int NV>
 __device__ __forceinline__ void tail_row(const Ctx &c, const KkEncLayer &L, int64_t row) {
     const int lane = threadIdx.x & 63, H = c.H;

@@ -15,9 +15,14 @@ normalised by max|fp64|, E_ref being the error of an fp32 PyTorch restatement on
 prints E_ref, the kernel's error and their ratio (pytest -s); docs/LAB_NOTES.md "Tail kernels vs fp64" holds what was measured.
 Every output lives in a guarded buffer (sentinel rows around it, NaN inside before the launch).
 
-kk_linear_tail_fwd needs no case here: test_kernels_gpu.py::test_linear_tail_fwd_matches_two_launches ties it bit for bit to
+Part B2 — the bits of kk_sublayer_out_fwd and kk_linear_tail_fwd are the ones recorded at the parent of csrc/kk_tail.h.
+
+kk_linear_tail_fwd needs no fp64 case here: test_kernels_gpu.py::test_linear_tail_fwd_matches_two_launches ties it bit for bit to
 kk_gemm + kk_sublayer_out_fwd at eight shapes of H = 512, so anchoring kk_sublayer_out_fwd at H = 512 (below) anchors it too."""
 import functools
+import hashlib
+import itertools
+import json
 import os
 import sys
 
@@ -295,6 +300,109 @@ def test_sublayer_out_fwd_fp64(kk, rows, H, S, gain_on, ln, y_bf16, n_bf16, mi):
     if p1 > 0 or p2 > 0:
         drop = m64 == 0
         assert torch.equal(x_out.t.cpu()[drop], res[drop]), f"{tag}: x_out of a dropped element is the residual, bit for bit"
+
+
+# ------------------------------------------------------------------ part B2: the tail forward's bits are the recorded parent's
+# The forward tail is written three times (sublayer_out_row of csrc/kk_tail.h, the fused Linear's epilogue, the encoder stack's tail_row)
+# and the other tests only compare the copies with each other.  tests/golden/tail_parent_digests.json ties the first two to their own
+# past: the SHA-256 of every output of the launches below as the tree before kk_tail.h computed them (tools/record_tail_golden.py, which
+# calls tail_forward_digests too).
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tail_parent_digests.json")
+DIGEST_MASKS = [MASKS[0], (0.0, 0.0, 0.0)]
+# kk_linear_tail_fwd at H = 512: (rows, S, K, LayerNorm).  77 rows: the last workgroup holds 13, wave 3 one live row, waves 4 to 7 none;
+# K = 64 a single k-tile, 576 a short last chunk
+LT_SHAPES = [(77, 5, 64, 1), (77, 5, 576, 1), (45, 7, 512, 0)]
+LT_KEEPS = {(77, 5): "1101110010111101", (45, 7): "1101110"}     # DropPath per sample, from the host replica
+
+
+def _digest(t):
+    t = t.detach().cpu().contiguous()
+    raw = t.reshape(-1).view(torch.uint8).numpy().tobytes()
+    return {"sha256": hashlib.sha256(raw).hexdigest(), "shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+
+
+def _sublayer_out_digests(kk, out):
+    for (rows, H, S), (p1, p2, dp) in itertools.product(FWD_SHAPES, DIGEST_MASKS):
+        _masks(rows, H, S, p1, p2, dp)                                   # asserts that DropPath keeps one sample and drops another
+        g = torch.Generator().manual_seed(rows * 7 + H)
+        y = torch.randn(rows, H, generator=g) * 1.5 + 0.25
+        res = dev(torch.randn(rows, H, generator=g) * 2 + 0.5)
+        gain, gamma = dev(1 + 0.25 * torch.randn(H, generator=g)), dev(1 + 0.25 * torch.randn(H, generator=g))
+        beta = dev(torch.randn(H, generator=g))
+        for y_bf16, n_bf16, gain_on, ln in itertools.product((0, 1), repeat=4):
+            yd = dev(y).bfloat16() if y_bf16 else dev(y)
+            x_out, rstd_f = Guarded(rows, H), gvec(rows, NAN)
+            n = Guarded(rows, H, dtype=torch.bfloat16 if n_bf16 else torch.float32)
+            mean, rstd = gvec(rows, NAN), gvec(rows, NAN)
+            kk.call("kk_sublayer_out_fwd", yd, y_bf16, gain if gain_on else None, rstd_f.t if gain_on else None, res, x_out.t,
+                    gamma if ln else None, beta if ln else None, n.t if ln else None, n_bf16 if ln else 0, mean.t if ln else None,
+                    rstd.t if ln else None, rows, H, S, _seed(), SITE1, p1, SITE2, p2, SITE_DP, dp)
+            torch.cuda.synchronize()
+            got = {"x_out": x_out}
+            if gain_on:
+                got["rstd_f"] = rstd_f
+            if ln:
+                got.update(n=n, mean=mean, rstd=rstd)
+            _clean(*got.values())
+            out[f"out_fwd {rows}x{H} S={S} y_bf16={y_bf16} n_bf16={n_bf16} gain={gain_on} ln={ln} p={p1}/{p2}/{dp}"] = \
+                {k: _digest(b.t) for k, b in got.items()}
+
+
+def _linear_tail_digests(kk, out):
+    H = 512
+    for rows, S, K, ln in LT_SHAPES:
+        g = torch.Generator().manual_seed(rows + K)
+        x = dev(torch.randn(rows, K, generator=g)).bfloat16()
+        W = dev(torch.randn(H, K, generator=g) / K ** 0.5).bfloat16()
+        bias, res = dev(0.1 * torch.randn(H, generator=g)), dev(torch.randn(rows, H, generator=g) * 2 + 0.5)
+        gain, gamma = dev(1 + 0.25 * torch.randn(H, generator=g)), dev(1 + 0.25 * torch.randn(H, generator=g))
+        beta = dev(torch.randn(H, generator=g))
+        assert kk.load().kk_linear_tail_supported(rows, H, K) == 1
+        for ffn, n_bf16 in itertools.product((1, 0), (1, 0) if ln else (0,)):
+            p1, p2, dp = (0.2, 0.1, 0.25) if ffn else (0.2, 0.0, 0.25)
+            k1, k2, kd = DM.tail_keeps(SEED, rows, H, S, SITE1, p1, SITE2, p2, SITE_DP, dp)
+            assert "".join(str(int(v)) for v in kd[::S]) == LT_KEEPS[rows, S], "DropPath per sample is not what the case was chosen for"
+            if rows == 77:
+                assert kd[8] and kd[9] and not kd[10] and not kd[11], "rows 8 to 11, one wave's four, span a kept and a dropped sample"
+            k = k1 & k2
+            assert bool((k.any(1) & (~k).any(1)).all()), "a row without a kept or without a dropped element"
+            y_out = Guarded(rows, H, dtype=torch.bfloat16)
+            x_out, rstd_f = Guarded(rows, H), gvec(rows, NAN)
+            n = Guarded(rows, H, dtype=torch.bfloat16 if n_bf16 else torch.float32)
+            mean, rstd = gvec(rows, NAN), gvec(rows, NAN)
+            # FFN form: y rounded to bf16 and stored for the backward, RMSNorm gain; attention form: fp32 y, not stored
+            kk.call("kk_linear_tail_fwd", x, K, W, bias, K, y_out.t if ffn else None, ffn, gain if ffn else None, rstd_f.t if ffn else None,
+                    res, x_out.t, gamma if ln else None, beta if ln else None, n.t if ln else None, n_bf16, mean.t if ln else None,
+                    rstd.t if ln else None, rows, H, S, _seed(), SITE1, p1, SITE2, p2, SITE_DP, dp)
+            torch.cuda.synchronize()
+            assert kk.last_kernel() == "linear_tail_fwd"
+            got = {"x_out": x_out}
+            if ffn:
+                got.update(y_out=y_out, rstd_f=rstd_f)
+            if ln:
+                got.update(n=n, mean=mean, rstd=rstd)
+            _clean(*got.values())
+            for b in (y_out, rstd_f, n, mean, rstd):
+                if not any(b is u for u in got.values()):
+                    assert b.intact() and bool(torch.isnan(b.t.float()).all()), "an output that was not asked for was written"
+            out[f"linear_tail {rows}x{H} S={S} K={K} ffn={ffn} ln={ln} n_bf16={n_bf16}"] = {k: _digest(b.t) for k, b in got.items()}
+
+
+def tail_forward_digests(kk):
+    """{case: {output: digest}} of every forward tail launch whose bits are pinned (the recorder and the test below share this)."""
+    out = {}
+    _sublayer_out_digests(kk, out)
+    _linear_tail_digests(kk, out)
+    return out
+
+
+def test_tail_forward_bits_match_the_recorded_parent(kk):
+    with open(GOLDEN) as f:
+        want = json.load(f)["cases"]
+    have = tail_forward_digests(kk)
+    assert sorted(have) == sorted(want)
+    differ = [f"{c}: {k}" for c in have for k in sorted(set(have[c]) | set(want[c])) if have[c].get(k) != want[c].get(k)]
+    assert not differ, f"{len(differ)} outputs of {len(have)} launches differ from the recorded bits: {differ[:8]}"
 
 
 # ------------------------------------------------------------------ part C: kk_sublayer_in_bwd against float64
