@@ -365,7 +365,6 @@ extern "C" int kk_gemm_tune16(int enable, int thr128, int thr12864, int split_ta
     if (thr128 > 0) kk_gemm16_tune(thr128, thr12864, split_target);
     return 0;
 }
-extern "C" int kk_gemm_tune_group(int split) { kk_gemm16_tune_group(split); return 0; }
 #endif
 
 extern "C" int kk_gemm(int ta, int tb, int64_t M, int64_t N, int64_t K, float alpha, const float *A, int64_t lda,

@@ -21,12 +21,153 @@
 
 namespace {
 
+// ---- policy: every knob of the host dispatch below, one instance ---------------------------------------------------------------
+// Small tiles (by tile count): with four waves per workgroup the 64x64 tile wins on every shape of this model measured inside the
+// train step (the launches are latency-bound: more, smaller workgroups keep more DMAs in flight); with EIGHT waves the 128x64 tile is
+// level or better from 128 tiles on (the decoder's 4096-row GEMMs: +0.8 % on the 8x512 step, +2.2 % at 8x1024, interleaved A/B), so
+// those take it and the encoder's 512-row GEMMs stay on 64x64.
+// Split-K target: a small-tile launch with fewer than target / 2 tiles splits its reduction until it has ~target workgroups.  384 (fill
+// the chip 1.5 x) was chosen stand-alone in round 1; INSIDE the step the launches it applies to are the side branch's (the text
+// encoder's 512-row GEMMs), where more workgroups + a zero-fill launch + fp32 atomics per launch cost the critical chain beside them more
+// than the shorter launch returns: 128 is -0.9 % on the 8 x 512 step (3.722 -> 3.690 ms interleaved), level at 8 x 1024
+// (profiles/r05_splitk_target_ab.txt).
+// Large tiles (kk_gemm16x.hip): a CU's L2 -> LDS stream runs at ~20 B/clk whatever a kernel does, so a launch's floor
+// is the bytes that pass through its BUSIEST CU: rounds of workgroups x (BM + BN) x K x 2.  Every candidate tile is priced by that number
+// (g16_cost, in units of K x 2 bytes) and the cheapest one runs; ties go to the small tile (more workgroups in flight, shorter
+// prologue / epilogue).
+// Set ONCE when the library is loaded: from KK_GEMM16_TUNE="thr128,thr12864,code" (code = flags*100000 + stages*10000 + split target, as
+// tools/ encode it) and, in a tools build, from the KK_G16X* variables; afterwards only the tools hooks at the end of this section write it.
+struct G16Policy {
+    int thr128 = 4096, thr12864 = 128;                          // tiles from which 128x128 (four waves) / 128x64 (eight waves) run
+    int split_target = 128, stages = 3, split_major = 0;
+    int on = kk_tune_env("KK_G16X", 15);                        // large tiles: bit 0 plain, 1 head-norm, 2 GLU forward / backward, 3 grouped weight gradients
+    int min_k_plain = kk_tune_env("KK_G16X_PLAIN_MIN_K", 1024);
+    int min_k_group = kk_tune_env("KK_G16X_GROUP_MIN_K", 1024);
+    int min_n_hn = kk_tune_env("KK_G16X_HN_MIN_N", 1024);
+    int group_chunks = kk_tune_env("KK_G16X_GROUP_CHUNKS", 1);  // grouped launches: an XCD takes a contiguous eighth of ALL tiles (0: of every problem)
+    int force = kk_tune_env("KK_G16X_FORCE", -1);               // tools: forced large tile (-1 = by cost)
+    int dbg = kk_tune_env("KK_G16X_DBG", 0);                    // tools: probe bits of g16x_body (1 no epilogue, 4 no MFMAs, 8 DMA + barriers only)
+    void small_tiles(int t128, int t12864, int code) {
+        thr128 = t128;
+        thr12864 = t12864;
+        stages = (code / 10000) % 10 ? (code / 10000) % 10 : 3;
+        split_major = code / 100000 ? 1 : 0;                    // 1xxxxx: split-major split-K (A/B comparison)
+        split_target = code % 10000;
+    }
+    G16Policy() {
+        const char *e = getenv("KK_GEMM16_TUNE");
+        int a = 0, b = 0, c = 0;
+        if (e && sscanf(e, "%d,%d,%d", &a, &b, &c) == 3 && a > 0) small_tiles(a, b, c);
+    }
+} g16;
+
+int g16_cus() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) return v;
+        return 256;
+    }();
+    return n;
+}
+long g16_cost(int64_t tiles, int bm, int bn) { return (long)((tiles + g16_cus() - 1) / g16_cus()) * (bm + bn); }
+
+// ---- the tile choice: one function, one row of data per route --------------------------------------------------------------------
+struct G16Tile { int bm, bn; };                                 // (bn: columns of ONE B panel)
+enum { FORCE_NONE, FORCE_CANDIDATE, FORCE_ANY };
+struct G16Route {
+    // small tiles
+    bool thr128;                                                // 128x128 from policy.thr128 tiles on
+    int w8_ktiles;                                              // eight waves on 128x64 from policy.thr12864 tiles and this many k-tiles on; 0: never, -1: always
+    int ns;                                                     // stages of a reduction of >= 3 k-tiles (0: policy.stages)
+    int panels;                                                 // B panels per workgroup (linear1 + GLU: 2, its tile's width counts twice)
+    // large tiles
+    int on_bit, min_ktiles;                                     // gate: this bit of policy.on, this many k-tiles ...
+    bool min_k, min_n;                                          // ... K >= policy.min_k_plain, N >= policy.min_n_hn
+    G16Tile base;                                               // the tile whose cost a candidate must beat ({0, 0}: the small tile that would run)
+    int force;                                                  // policy.force: ignored | taken when it is a candidate | taken when >= 0
+    int ncand, cand[G16X_NCFG];                                 // candidates, in order (the first of equal cost wins)
+};
+const G16Route R_PLAIN    = {true,  1, 0, 1,   1, 0, true,  false, {0, 0},    FORCE_CANDIDATE, 2, {G16X_128x128, G16X_256x128}};
+const G16Route R_DELTA    = {false, -1, 0, 1,  1, 0, true,  false, {0, 0},    FORCE_NONE,      1, {G16X_128x128}};
+const G16Route R_GLU_BWD  = {false, 3, 3, 1,   4, 3, false, false, {128, 64}, FORCE_NONE,      1, {G16X_128x192}};      // (priced against 128x64 whether or not it would run)
+const G16Route R_GLU_FWD  = {false, 0, 2, 2,   4, 3, false, false, {64, 64},  FORCE_NONE,      1, {G16X_256x192}};      // 256 rows x (96 + 96) columns against 64 x (64 + 64)
+const G16Route R_HEADNORM = {false, 3, 3, 1,   2, 3, false, true,  {0, 0},    FORCE_ANY,       4, {G16X_128x128, G16X_128x192, G16X_256x128, G16X_256x192}};
+
+struct G16Choice {
+    int cfg;                                                    // large-tile family: its tile; -1: the small-tile family
+    G16Tile tile;
+    int waves;
+};
+// `large_ok`: what the caller alone knows about the large tiles' gate (one k-slice, the operand layout, the alignment of the epilogue's stores)
+G16Choice g16_choose(const G16Route &r, int64_t M, int64_t N, int64_t K, bool large_ok) {
+    const int ktiles = kk_cdiv(K, BK);
+    auto tiles = [&](G16Tile t) { return (int64_t)kk_cdiv(M, t.bm) * kk_cdiv(N, t.bn); };
+    auto cost = [&](G16Tile t) { return g16_cost(tiles(t), t.bm, t.bn * r.panels); };
+    G16Choice c = {-1, {64, 64}, 4};
+    if (r.thr128 && tiles({128, 128}) >= g16.thr128) c.tile = {128, 128};
+    else if (r.w8_ktiles < 0 || (r.w8_ktiles > 0 && ktiles >= r.w8_ktiles && tiles({128, 64}) >= g16.thr12864)) c = {-1, {128, 64}, 8};
+    if (!large_ok || !(g16.on & r.on_bit) || ktiles < r.min_ktiles || (r.min_k && K < g16.min_k_plain) || (r.min_n && N < g16.min_n_hn)) return c;
+    auto large = [&](int cfg) { G16Tile t; kk_g16x_tile(cfg, &t.bm, &t.bn); t.bn /= r.panels; return t; };
+    int best = -1;
+    long best_cost = cost(r.base.bm ? r.base : c.tile);
+    for (int i = 0; i < r.ncand; ++i) {
+        const long cc = cost(large(r.cand[i]));
+        if (cc < best_cost) { best = r.cand[i]; best_cost = cc; }
+    }
+    if (r.force == FORCE_ANY && g16.force >= 0) best = g16.force;
+    if (r.force == FORCE_CANDIDATE && std::find(r.cand, r.cand + r.ncand, g16.force) != r.cand + r.ncand) best = g16.force;
+    if (best >= 0) c = {best, large(best), 8};
+    return c;
+}
+// LDS stages of a small-tile launch whose k-slices hold `ktiles` k-tiles (a short reduction gains nothing from depth)
+int g16_ns(const G16Route &r, const G16Choice &c, int ktiles) {
+    if (c.tile.bn == 128 || ktiles < 3) return 2;
+    return std::min(std::max(r.ns ? r.ns : g16.stages, 2), c.waves == 8 ? 3 : 4);
+}
+
+// ---- split-K -------------------------------------------------------------------------------------------------------------------
+struct G16Split { int splits, k_per_split, split_major; };
+G16Split g16_split_plain(int tiles, int ktiles, int64_t N, int64_t K, float beta, int64_t ldc, int c_bf16, int split_k) {
+    int splits = split_k;
+    if (splits <= 0) {
+        splits = 1;
+        if (tiles * 2 <= g16.split_target) {
+            splits = kk_cdiv(g16.split_target, tiles);
+            const int cap = ktiles / 2 > 0 ? ktiles / 2 : 1;
+            if (splits > cap) splits = cap;
+        }
+    }
+    // beta == 0 with k-slices needs C zero-filled first: one more node in front of a GEMM that is latency-bound anyway
+    // (the encoder's 1000-row projections), so short reductions are not sliced then
+    // (+1 % on the train step)
+    if (split_k <= 0 && beta == 0.f && ktiles < 32) splits = 1;
+    if (splits > ktiles) splits = ktiles;
+    if (splits > 1 && (c_bf16 || !(beta == 1.f || (beta == 0.f && ldc == N)))) splits = 1;
+    if (split_k <= 0 && splits >= 6 && g16.split_major) {       // a multiple of 8 slices: one XCD per slice residue class
+        int s8 = ((splits + 4) / 8) * 8;
+        while (s8 > 8 && ktiles / s8 < 2) s8 -= 8;
+        if (ktiles / s8 >= 1) splits = s8;
+    }
+    int k_per_split = kk_cdiv(ktiles, splits) * BK;
+    splits = kk_cdiv(K, k_per_split);
+    const int split_major = (g16.split_major && splits > 1 && splits % 8 == 0) ? 1 : 0;
+    return {splits, k_per_split, split_major};
+}
+// grouped launch: the k-slices that `splits` asks for leave problem i (reduction T) with `sp` slices of `kps`
+G16Split g16_split_group(int64_t T, int splits) {
+    const int ktiles = kk_cdiv(T, BK);
+    int sp = std::min(splits, std::max(ktiles / 2, 1));
+    const int kps = kk_cdiv(ktiles, sp) * BK;
+    sp = kk_cdiv(T, kps);
+    return {sp, kps, 0};
+}
+
+// ---- kernels: explicit instantiations of exactly what the launch helpers and entry points below name -----------------------------
 template <bool TA, bool TB, int BM, int BN, int NS, int EPI = 0>
 __global__ __launch_bounds__(256) void gemm16_kernel(G16Args a) {
     __shared__ __attribute__((aligned(16))) char smem[NS * (BM + (EPI == 2 ? 2 : 1) * BN) * BK * 2];
     gemm16_body<TA, TB, BM, BN, NS, EPI>(a, blockIdx.x, smem);
 }
-
 // The same body run by EIGHT waves on the 128x64 tile (a 4x2 wave grid, one 32x32 MFMA chain per wave): twice the waves per
 // byte of LDS, which is what these latency-bound launches respond to (see the grouped weight gradients below).
 template <bool TA, bool TB, int NS>
@@ -34,48 +175,21 @@ __global__ __launch_bounds__(512) void gemm16_kernel_w8(G16Args a) {
     __shared__ __attribute__((aligned(16))) char smem[NS * (128 + 64) * BK * 2];
     gemm16_body<TA, TB, 128, 64, NS, 0, 8, 2>(a, blockIdx.x, smem);
 }
-template __global__ void gemm16_kernel_w8<false, false, 2>(G16Args);
-template __global__ void gemm16_kernel_w8<false, true, 2>(G16Args);
-template __global__ void gemm16_kernel_w8<true, false, 2>(G16Args);
-template __global__ void gemm16_kernel_w8<true, true, 2>(G16Args);
-template __global__ void gemm16_kernel_w8<false, false, 3>(G16Args);
-template __global__ void gemm16_kernel_w8<false, true, 3>(G16Args);
-template __global__ void gemm16_kernel_w8<true, false, 3>(G16Args);
-template __global__ void gemm16_kernel_w8<true, true, 3>(G16Args);
-// ... and the two GLU epilogues on that tile (linear1 + gate: two B panels, 96 KB of LDS; linear2 dgrad + gate backward)
+// ... with the GLU backward epilogue (linear2 dgrad + gate backward: +0.3 % on the step) ...
 template <bool TB, int NS, int EPI>
 __global__ __launch_bounds__(512) void gemm16_kernel_w8_glu(G16Args a) {
     __shared__ __attribute__((aligned(16))) char smem[NS * (128 + (EPI == 2 ? 2 : 1) * 64) * BK * 2];
     gemm16_body<false, TB, 128, 64, NS, EPI, 8, 2>(a, blockIdx.x, smem);
 }
-// EPI 3 on the eight-wave tile (KK_G16_W8_HN=0: the four-wave 64x64 form)
+// ... and with the head-norm epilogue (+0.8 % on the step)
 template <int NS>
 __global__ __launch_bounds__(512) void gemm16_kernel_w8_hn(G16Args a) {
     __shared__ __attribute__((aligned(16))) char smem[NS * (128 + 64) * BK * 2];
     gemm16_body<false, false, 128, 64, NS, 3, 8, 2>(a, blockIdx.x, smem);
 }
-template __global__ void gemm16_kernel_w8_hn<3>(G16Args);
-template __global__ void gemm16_kernel_w8_glu<false, 3, 2>(G16Args);
-template __global__ void gemm16_kernel_w8_glu<true, 3, 1>(G16Args);
-int g16_w8_hn = kk_tune_env("KK_G16_W8_HN", 1);        // measured: +0.8 % on the step (interleaved A/B)
-int g16_w8_glu = kk_tune_env("KK_G16_W8_GLU", 1);      // bit 0: dgrad + GLU backward, bit 1: linear1 + GLU; 4th part, interleaved: bit 0 +0.3 % (on), bit 1 -0.5 % (off)
-
-template <int NS>
-void launch_w8(int ta, int tb, const G16Args &a, dim3 grid, hipStream_t s) {
-    kk_note_kernelf("gemm16_w8<%d,%d,%d>", ta, tb, NS);
-    if (kk_capture(kk_last_kernel(), a, grid, 512, 0)) return;
-    if (!ta && !tb) hipLaunchKernelGGL((gemm16_kernel_w8<false, false, NS>), grid, dim3(512), 0, s, a);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm16_kernel_w8<false, true, NS>), grid, dim3(512), 0, s, a);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm16_kernel_w8<true, false, NS>), grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((gemm16_kernel_w8<true, true, NS>), grid, dim3(512), 0, s, a);
-}
-// 8-wave 128x64 tiles, 3 stages, for single GEMMs with >= g16_thr12864 such tiles: +0.8 % on the 8x512 step, +2.2 % at 8x1024
-// (interleaved A/B, tools/probes/g16w8.sh); KK_G16_W8=0 restores the 4-wave form, =2 two stages.
-int g16_w8 = kk_tune_env("KK_G16_W8", 3);
-
 // Several independent GEMMs of one operand layout in ONE launch (a layer's weight gradients: they have no consumer
-// before the optimizer, so they wait until the layer's backward is through and then fill the chip together — ~1000
-// 64x64 tiles with the full reduction length each, no split-K atomics, one launch instead of four to six).
+// before the optimizer, so they wait until the layer's backward is through and then fill the chip together: full reduction
+// lengths, no split-K atomics, one launch instead of four to six).  Eight waves on 128x64 tiles: +1 % on the step over 64x64.
 template <bool TA, bool TB, int BM, int BN, int NS, int WAVES = 4, int WC = 2>
 __global__ __launch_bounds__(64 * WAVES) void gemm16_group_kernel(G16Group g) {
     __shared__ __attribute__((aligned(16))) char smem[NS * (BM + BN) * BK * 2];
@@ -83,41 +197,21 @@ __global__ __launch_bounds__(64 * WAVES) void gemm16_group_kernel(G16Group g) {
     while (i + 1 < g.n && (int)blockIdx.x >= g.start[i + 1]) ++i;
     gemm16_body<TA, TB, BM, BN, NS, 0, WAVES, WC>(g.p[i], (int)blockIdx.x - g.start[i], smem);
 }
-template __global__ void gemm16_group_kernel<true, true, 128, 128, 2, 16, 4>(G16Group);
+// (explicit, in this order: the host stubs of kernels only named inside an if/else chain of a launch helper were not emitted, and the
+// compiler's register allocation of a kernel is not independent of the instantiations before it)
+#define G16_LAYOUTS(K, ...) \
+    template __global__ void K<false, false, __VA_ARGS__>(G16Args); template __global__ void K<false, true, __VA_ARGS__>(G16Args); \
+    template __global__ void K<true, false, __VA_ARGS__>(G16Args);  template __global__ void K<true, true, __VA_ARGS__>(G16Args);
+G16_LAYOUTS(gemm16_kernel_w8, 2)
+G16_LAYOUTS(gemm16_kernel_w8, 3)
+template __global__ void gemm16_kernel_w8_hn<3>(G16Args);
+template __global__ void gemm16_kernel_w8_glu<true, 3, 1>(G16Args);
 template __global__ void gemm16_group_kernel<true, true, 128, 64, 2, 8>(G16Group);
-template __global__ void gemm16_group_kernel<true, true, 128, 128, 2, 8>(G16Group);
-template __global__ void gemm16_group_kernel<true, true, 64, 64, 2>(G16Group);
-template __global__ void gemm16_group_kernel<true, true, 64, 64, 3>(G16Group);
-template __global__ void gemm16_group_kernel<true, true, 128, 64, 2>(G16Group);
-template __global__ void gemm16_group_kernel<true, true, 128, 128, 2>(G16Group);
-
-// (explicit instantiations: the host stubs of kernels only named inside launch_tile's if/else chain were not emitted)
-
-template __global__ void gemm16_kernel<false, false, 128, 128, 2>(G16Args);
-template __global__ void gemm16_kernel<false, true, 128, 128, 2>(G16Args);
-template __global__ void gemm16_kernel<true, false, 128, 128, 2>(G16Args);
-template __global__ void gemm16_kernel<true, true, 128, 128, 2>(G16Args);
-template __global__ void gemm16_kernel<false, false, 128, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<false, true, 128, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<true, false, 128, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<true, true, 128, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<false, false, 128, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<false, true, 128, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<true, false, 128, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<true, true, 128, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<false, false, 64, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<false, true, 64, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<true, false, 64, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<true, true, 64, 64, 2>(G16Args);
-template __global__ void gemm16_kernel<false, false, 64, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<false, true, 64, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<true, false, 64, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<true, true, 64, 64, 3>(G16Args);
-template __global__ void gemm16_kernel<false, false, 64, 64, 4>(G16Args);
-template __global__ void gemm16_kernel<false, true, 64, 64, 4>(G16Args);
-template __global__ void gemm16_kernel<true, false, 64, 64, 4>(G16Args);
-template __global__ void gemm16_kernel<true, true, 64, 64, 4>(G16Args);
-
+G16_LAYOUTS(gemm16_kernel, 128, 128, 2)
+G16_LAYOUTS(gemm16_kernel, 64, 64, 2)
+G16_LAYOUTS(gemm16_kernel, 64, 64, 3)
+G16_LAYOUTS(gemm16_kernel, 64, 64, 4)
+#undef G16_LAYOUTS
 template __global__ void gemm16_kernel<false, false, 64, 64, 2, 2>(G16Args);
 template __global__ void gemm16_kernel<false, false, 64, 64, 2, 3>(G16Args);
 template __global__ void gemm16_kernel<false, false, 64, 64, 3, 3>(G16Args);
@@ -132,60 +226,15 @@ void launch_tile(int ta, int tb, const G16Args &a, dim3 grid, hipStream_t s) {
     else if (ta && !tb) hipLaunchKernelGGL((gemm16_kernel<true, false, BM, BN, NS>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((gemm16_kernel<true, true, BM, BN, NS>), grid, dim3(256), 0, s, a);
 }
-
-// Tile choice (by tile count): with four waves per workgroup the 64x64 tile wins on every shape of this model measured
-// inside the train step (the launches are latency-bound: more, smaller workgroups keep more DMAs in flight); with EIGHT
-// waves the 128x64 tile is level or better from 128 tiles on (the decoder's 4096-row GEMMs), so those take it and the
-// encoder's 512-row GEMMs stay on 64x64.
-// Split-K target: a small-tile launch with fewer than target / 2 tiles splits its reduction until it has ~target workgroups.  384 (fill
-// the chip 1.5 x) was chosen stand-alone in round 1; INSIDE the step the launches it applies to are the side branch's (the text
-// encoder's 512-row GEMMs), where more workgroups + a zero-fill launch + fp32 atomics per launch cost the critical chain beside them more
-// than the shorter launch returns: 128 is -0.9 % on the 8 x 512 step (3.722 -> 3.690 ms interleaved), level at 8 x 1024
-// (profiles/r05_splitk_target_ab.txt).
-int g16_thr128 = 4096, g16_thr12864 = 128, g16_split_target = 128, g16_stages = 3, g16_split_major = 0;
-// Optional override of the tile policy, read ONCE when the library is loaded (no mutable policy behind the ABI):
-// KK_GEMM16_TUNE="thr128,thr12864,code" with code = flags*100000 + stages*10000 + split target, as tools/ encode it.
-struct G16EnvInit {
-    G16EnvInit() {
-        const char *e = getenv("KK_GEMM16_TUNE");
-        int a = 0, b = 0, c = 0;
-        if (e && sscanf(e, "%d,%d,%d", &a, &b, &c) == 3 && a > 0) {
-            g16_thr128 = a;
-            g16_thr12864 = b;
-            g16_stages = (c / 10000) % 10 ? (c / 10000) % 10 : 3;
-            g16_split_major = c / 100000 ? 1 : 0;
-            g16_split_target = c % 10000;
-        }
-    }
-} g16_env_init;
-int g16_group_tile = kk_tune_env("KK_GROUP_TILE", 1);                                         // grouped launches: 0 = 64x64, 1 = 128x64 (default: +1 % on the step), 2 = 128x128 tiles
-int g16_group_waves = kk_tune_env("KK_GROUP_WAVES", 8);   // 8-wave workgroups on the 128-row tiles (4: the old form)
-int g16_group_mfast = kk_tune_env("KK_GROUP_MFAST", 1);  // grouped launches: sweep direction by operand size (0: always n fastest)
-int g16_group_split = 0;                                        // grouped launches: 0 = by the split target, n = n k-slices
-
-// ---- the large-tile family (kk_gemm16x.hip) ------------------------------------------------------------------------------------
-// A CU's L2 -> LDS stream runs at ~20 B/clk whatever a kernel does, so a launch's floor is the bytes that pass
-// through its BUSIEST CU: rounds of workgroups x (BM + BN) x K x 2.  Every candidate tile is priced by that number (in units of
-// K x 2 bytes) and the cheapest one runs; ties go to the smaller tile (more workgroups in flight, shorter prologue / epilogue).
-int g16x_on = kk_tune_env("KK_G16X", 15);              // tools: bit 0 plain, 1 head-norm, 2 GLU forward / backward, 3 grouped weight gradients
-int g16x_min_k_group = kk_tune_env("KK_G16X_GROUP_MIN_K", 1024);
-int g16x_min_k_plain = kk_tune_env("KK_G16X_PLAIN_MIN_K", 1024);
-int g16x_group_chunks = kk_tune_env("KK_G16X_GROUP_CHUNKS", 1);      // grouped launches: an XCD takes a contiguous eighth of ALL tiles (0: of every problem)
-int g16x_min_n_hn = kk_tune_env("KK_G16X_HN_MIN_N", 1024);
-int g16x_dbg = kk_tune_env("KK_G16X_DBG", 0);         // tools: probe bits of g16x_body (1 no epilogue, 4 no MFMAs, 8 DMA + barriers only)
-int g16x_force = kk_tune_env("KK_G16X_FORCE", -1);
-#ifdef KK_TUNING_HOOKS
-void *g16x_trace = nullptr;                            // tools: destination of probe bit 32
-#endif
-int g16_cus() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) return v;
-        return 256;
-    }();
-    return n;
+template <int NS>
+void launch_w8(int ta, int tb, const G16Args &a, dim3 grid, hipStream_t s) {
+    kk_note_kernelf("gemm16_w8<%d,%d,%d>", ta, tb, NS);
+    if (kk_capture(kk_last_kernel(), a, grid, 512, 0)) return;
+    if (!ta && !tb) hipLaunchKernelGGL((gemm16_kernel_w8<false, false, NS>), grid, dim3(512), 0, s, a);
+    else if (!ta && tb) hipLaunchKernelGGL((gemm16_kernel_w8<false, true, NS>), grid, dim3(512), 0, s, a);
+    else if (ta && !tb) hipLaunchKernelGGL((gemm16_kernel_w8<true, false, NS>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((gemm16_kernel_w8<true, true, NS>), grid, dim3(512), 0, s, a);
 }
-long g16_cost(int64_t tiles, int bm, int bn) { return (long)((tiles + g16_cus() - 1) / g16_cus()) * (bm + bn); }
 
 // C[M, N] = A.B over the whole reduction K in one k-slice, on BM x BN tiles: what every launch derives the same way (alpha = 1, beta = 0,
 // fp32 C; write-through by the launch length: a weight gradient's — ta — is its reduction).  The entry points add their epilogue's fields.
@@ -202,12 +251,12 @@ G16Args g16_args(int ta, int tb, int64_t M, int64_t N, int64_t K, const void *A,
     return a;
 }
 
-// ss_rec / ss_seg of a grouped launch: when every problem is written exactly once per element by one workgroup (`ok`: the kernel has the
-// write-through fp32 epilogue; no k-slices; that epilogue's conditions; a tile inside ONE segment), its tiles leave the sums of squares of
+// ss_rec / ss_seg of a grouped launch: when every problem is written exactly once per element by one workgroup (no k-slices; the
+// conditions of the write-through fp32 epilogue, which both bodies have; a tile inside ONE segment), its tiles leave the sums of squares of
 // what they stored as records [*ss_count ..) of ss_rec and *ss_count is advanced; otherwise *ss_count stays and the caller's norm pass
 // reads those tensors itself
-void g16_group_ss(G16Group &g, bool ok, KkSegRec *rec, const int32_t *ss_seg, int32_t *ss_count) {
-    bool all_wt = ok && rec != nullptr && ss_seg != nullptr && ss_count != nullptr;
+void g16_group_ss(G16Group &g, KkSegRec *rec, const int32_t *ss_seg, int32_t *ss_count) {
+    bool all_wt = rec != nullptr && ss_seg != nullptr && ss_count != nullptr;
     for (int i = 0; i < g.n && all_wt; ++i)
         all_wt = (ss_seg[2 * i + 1] == 0 || ss_seg[2 * i + 1] % 128 == 0) && g.p[i].splits == 1 && g.p[i].wt && (g.p[i].ldc & 3) == 0 && (g.p[i].N & 7) == 0 && (reinterpret_cast<uintptr_t>(g.p[i].C) & 15) == 0;
     if (!all_wt) return;
@@ -221,21 +270,14 @@ void g16_group_ss(G16Group &g, bool ok, KkSegRec *rec, const int32_t *ss_seg, in
 
 }  // namespace
 
-// Tuning hook used by tools/ (not part of the C ABI).
-void kk_gemm16_tune(int thr128, int thr12864, int split_target) {
-    g16_thr128 = thr128;
-    g16_thr12864 = thr12864;
-    g16_stages = (split_target / 10000) % 10 ? (split_target / 10000) % 10 : 3;   // tools encode flags*100000 + stages*10000 + split target
-    g16_split_major = split_target / 100000 ? 1 : 0;                     // 1xxxxx: split-major split-K (A/B comparison)
-    g16_split_target = split_target % 10000;
-}
-void kk_gemm16_tune_group(int split) { g16_group_split = split % 100; g16_group_tile = split / 100; }
 #ifdef KK_TUNING_HOOKS
-// tools: large-tile family on/off bits, forced tile (-1 = by cost), probe bits
+// Tuning hooks used by tools/ (not part of the C ABI): the small tiles' thresholds; the large-tile family's on/off bits, forced tile
+// (-1 = by cost) and probe bits
+void kk_gemm16_tune(int thr128, int thr12864, int split_target) { g16.small_tiles(thr128, thr12864, split_target); }
 extern int g16x_lw;
-extern "C" int kk_gemm_tune16x(int on, int force, int dbg) { g16x_on = on & 255; g16x_lw = (on >> 8) & 1 ? 0 : ((on >> 9) & 1 ? 2 : 1); g16x_group_chunks = (on >> 10) & 1 ? 0 : 1; g16x_force = force; g16x_dbg = dbg; return 0; }
+extern "C" int kk_gemm_tune16x(int on, int force, int dbg) { g16.on = on & 255; g16x_lw = (on >> 8) & 1 ? 0 : ((on >> 9) & 1 ? 2 : 1); g16.group_chunks = (on >> 10) & 1 ? 0 : 1; g16.force = force; g16.dbg = dbg; return 0; }
 void kk_g16x_probe(int bits, void *buf);
-extern "C" int kk_gemm_trace16x(void *buf) { g16x_trace = buf; kk_g16x_probe(g16x_dbg, buf); return 0; }      // probe bit 32: 8 waves x 64 stamps (uint64) of workgroup 0
+extern "C" int kk_gemm_trace16x(void *buf) { kk_g16x_probe(g16.dbg, buf); return 0; }      // probe bit 32: 8 waves x 64 stamps (uint64) of workgroup 0
 #endif
 
 // True when this core can run the problem (both operands bf16 assumed by the caller).
@@ -249,67 +291,28 @@ bool kk_gemm16_eligible(int ta, int tb, int64_t M, int64_t N, int64_t K, const v
 int kk_gemm16_launch(int ta, int tb, int64_t M, int64_t N, int64_t K, float alpha, const void *A, int64_t lda, const void *B,
                      int64_t ldb, float beta, void *C, int64_t ldc, int c_bf16, const float *bias, const float *residual,
                      int64_t ldr, int64_t res_mod, int split_k, int xcd_swizzle, hipStream_t s) {
-    int BM = 64, BN = 64;
-    if (kk_cdiv(M, 128) * kk_cdiv(N, 128) >= g16_thr128) { BM = 128; BN = 128; }
-    else if (kk_cdiv(M, 128) * kk_cdiv(N, 64) >= g16_thr12864) { BM = 128; BN = 64; }
-    const int tiles = kk_cdiv(M, BM) * kk_cdiv(N, BN), ktiles = kk_cdiv(K, BK);
-    int splits = split_k;
-    if (splits <= 0) {
-        splits = 1;
-        if (tiles * 2 <= g16_split_target) {
-            splits = kk_cdiv(g16_split_target, tiles);
-            const int cap = ktiles / 2 > 0 ? ktiles / 2 : 1;
-            if (splits > cap) splits = cap;
-        }
-    }
-    // beta == 0 with k-slices needs C zero-filled first: one more node in front of a GEMM that is latency-bound anyway
-    // (the encoder's 1000-row projections), so short reductions are not sliced then
-    // (+1 % on the train step)
-    if (split_k <= 0 && beta == 0.f && ktiles < 32) splits = 1;
-    if (splits > ktiles) splits = ktiles;
-    if (splits > 1 && (c_bf16 || !(beta == 1.f || (beta == 0.f && ldc == N)))) splits = 1;
-    if (split_k <= 0 && splits >= 6 && g16_split_major) {       // a multiple of 8 slices: one XCD per slice residue class
-        int s8 = ((splits + 4) / 8) * 8;
-        while (s8 > 8 && ktiles / s8 < 2) s8 -= 8;
-        if (ktiles / s8 >= 1) splits = s8;
-    }
-    int k_per_split = kk_cdiv(ktiles, splits) * BK;
-    splits = kk_cdiv(K, k_per_split);
-    const int split_major = (g16_split_major && splits > 1 && splits % 8 == 0) ? 1 : 0;
-    G16Args a = g16_args(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, BM, BN, xcd_swizzle);
-    a.alpha = alpha; a.beta = beta; a.bias = bias; a.residual = residual; a.c_bf16 = c_bf16; a.ldr = ldr; a.res_mod = res_mod;
-    a.k_per_split = k_per_split; a.atomic = splits > 1 ? 1 : 0; a.splits = splits; a.split_major = split_major;
+    const G16Tile t = g16_choose(R_PLAIN, M, N, K, false).tile;      // (the k-slices are counted for the small tile)
+    const int ktiles = kk_cdiv(K, BK);
+    const G16Split sp = g16_split_plain(kk_cdiv(M, t.bm) * kk_cdiv(N, t.bn), ktiles, N, K, beta, ldc, c_bf16, split_k);
     // (long reductions only: at K = 512 a one-workgroup-per-CU launch shows its whole prologue and epilogue, two 128x64 workgroups per CU
     // hide each other's — measured 9.5 against 10.3 us at 8192 x 512 x 512, 46 against 37 us at K = 3072; weight-gradient layouts: grouped launches only)
-    if ((g16x_on & 1) && splits == 1 && !ta && K >= g16x_min_k_plain) {
-        const long cost_old = g16_cost(tiles, BM, BN);
-        int best = -1;
-        long best_cost = cost_old;
-        for (int cfg : {G16X_128x128, G16X_256x128}) {
-            int bm, bn;
-            kk_g16x_tile(cfg, &bm, &bn);
-            const long c = g16_cost((int64_t)kk_cdiv(M, bm) * kk_cdiv(N, bn), bm, bn);
-            if (c < best_cost) { best = cfg; best_cost = c; }
-        }
-        if (g16x_force == G16X_128x128 || g16x_force == G16X_256x128) best = g16x_force;
-        if (best >= 0) {
-            int bm, bn;
-            kk_g16x_tile(best, &bm, &bn);
-            a.tiles_m = kk_cdiv(M, bm); a.tiles_n = kk_cdiv(N, bn); a.dbg = g16x_dbg;
-            a.k_per_split = ktiles * BK; a.atomic = 0; a.splits = 1; a.split_major = 0;
-            return kk_g16x_plain(best, ta, tb, a, s);
-        }
+    const G16Choice c = g16_choose(R_PLAIN, M, N, K, sp.splits == 1 && !ta);
+    G16Args a = g16_args(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, c.tile.bm, c.tile.bn, xcd_swizzle);
+    a.alpha = alpha; a.beta = beta; a.bias = bias; a.residual = residual; a.c_bf16 = c_bf16; a.ldr = ldr; a.res_mod = res_mod;
+    a.k_per_split = sp.k_per_split; a.atomic = sp.splits > 1 ? 1 : 0; a.splits = sp.splits; a.split_major = sp.split_major;
+    if (c.cfg >= 0) {
+        a.dbg = g16.dbg;
+        return kk_g16x_plain(c.cfg, ta, tb, a, s);
     }
-    if (splits > 1 && beta == 0.f) {
+    if (sp.splits > 1 && beta == 0.f) {
         const int e = kk_zero_async(C, (size_t)M * N * sizeof(float), s);
         if (e != 0) return e;
     }
-    dim3 grid(a.tiles_m * a.tiles_n * splits);
-    const int ns = ktiles / splits < 3 ? 2 : g16_stages;        // (a short reduction gains nothing from depth)
-    if (BM == 128 && BN == 128) launch_tile<128, 128, 2>(ta, tb, a, grid, s);
-    else if (BM == 128 && g16_w8) { if (ns >= 3 && g16_w8 >= 3) launch_w8<3>(ta, tb, a, grid, s); else launch_w8<2>(ta, tb, a, grid, s); }
-    else if (BM == 128) { if (ns >= 3) launch_tile<128, 64, 3>(ta, tb, a, grid, s); else launch_tile<128, 64, 2>(ta, tb, a, grid, s); }
-    else if (ns >= 4) launch_tile<64, 64, 4>(ta, tb, a, grid, s);
+    dim3 grid(a.tiles_m * a.tiles_n * sp.splits);
+    const int ns = g16_ns(R_PLAIN, c, ktiles / sp.splits);
+    if (c.tile.bn == 128) launch_tile<128, 128, 2>(ta, tb, a, grid, s);
+    else if (c.waves == 8) { if (ns == 3) launch_w8<3>(ta, tb, a, grid, s); else launch_w8<2>(ta, tb, a, grid, s); }
+    else if (ns == 4) launch_tile<64, 64, 4>(ta, tb, a, grid, s);
     else if (ns == 3) launch_tile<64, 64, 3>(ta, tb, a, grid, s);
     else launch_tile<64, 64, 2>(ta, tb, a, grid, s);
     KK_LAUNCH_CHECK("kk_gemm");
@@ -321,22 +324,17 @@ int kk_gemm16_launch(int ta, int tb, int64_t M, int64_t N, int64_t K, float alph
 // for.  The decoder's 4096-row launches take that tile anyway; the text encoder's 512-row ones (32 tiles, a 64x64 launch otherwise)
 // take it FOR the epilogue: Delta is what lets the attention backward run as one launch (kk_attn_bwd).
 bool kk_gemm16_dgrad_delta_supported(int64_t M, int64_t N, int64_t K) {
-    return g16_w8 != 0 && M >= 1 && N % 64 == 0 && K % BK == 0 && kk_cdiv(M, 128) * kk_cdiv(N, 128) < g16_thr128;
+    return M >= 1 && N % 64 == 0 && K % BK == 0 && kk_cdiv(M, 128) * kk_cdiv(N, 128) < g16.thr128;
 }
 int kk_gemm16_dgrad_delta(int64_t M, int64_t N, int64_t K, const void *dy, int64_t lddy, const void *W, int64_t ldw, void *dx,
                           int64_t lddx, const void *O, int64_t ldo, float *delta, int S, int heads, int xcd_swizzle, hipStream_t s) {
-    G16Args a = g16_args(0, 1, M, N, K, dy, lddy, W, ldw, dx, lddx, 128, 64, xcd_swizzle);
+    const G16Choice c = g16_choose(R_DELTA, M, N, K, true);
+    G16Args a = g16_args(0, 1, M, N, K, dy, lddy, W, ldw, dx, lddx, c.tile.bm, c.tile.bn, xcd_swizzle);
     a.c_bf16 = 1;
     a.dl_o = static_cast<const __bf16 *>(O); a.dl_out = delta; a.dl_ldo = ldo; a.dl_S = S; a.dl_heads = heads;
-    if ((g16x_on & 1) && K >= g16x_min_k_plain) {
-        const long c_old = g16_cost((int64_t)a.tiles_m * a.tiles_n, 128, 64), c_new = g16_cost((int64_t)kk_cdiv(M, 128) * kk_cdiv(N, 128), 128, 128);
-        if (c_new < c_old) {
-            a.tiles_m = kk_cdiv(M, 128); a.tiles_n = kk_cdiv(N, 128);
-            return kk_g16x_plain(G16X_128x128, 0, 1, a, s);
-        }
-    }
+    if (c.cfg >= 0) return kk_g16x_plain(c.cfg, 0, 1, a, s);
     dim3 grid(a.tiles_m * a.tiles_n);
-    if (kk_cdiv(K, BK) >= 3 && g16_stages >= 3 && g16_w8 >= 3) launch_w8<3>(0, 1, a, grid, s);
+    if (g16_ns(R_DELTA, c, kk_cdiv(K, BK)) == 3) launch_w8<3>(0, 1, a, grid, s);
     else launch_w8<2>(0, 1, a, grid, s);
     KK_LAUNCH_CHECK("kk_gemm_dgrad_delta");
     return 0;
@@ -344,125 +342,36 @@ int kk_gemm16_dgrad_delta(int64_t M, int64_t N, int64_t K, const void *dy, int64
 
 int kk_gemm16_dgrad_glu(int64_t T, int64_t F, int64_t H, const void *dy, int64_t lddy, const void *W, const void *h1, void *dh1,
                         float *partials, const uint32_t *seed, uint32_t site, float p, int xcd_swizzle, hipStream_t s) {
-    G16Args a = g16_args(0, 1, T, F, H, dy, lddy, W, F, nullptr, 0, 64, 64, xcd_swizzle);      // (C is not written: the epilogue stores dh1)
+    const G16Choice c = g16_choose(R_GLU_BWD, T, F, H, true);
+    G16Args a = g16_args(0, 1, T, F, H, dy, lddy, W, F, nullptr, 0, c.tile.bm, c.tile.bn, xcd_swizzle);      // (C is not written: the epilogue stores dh1)
     a.glu_h = static_cast<const __bf16 *>(h1); a.glu_dh = static_cast<__bf16 *>(dh1); a.glu_partials = partials;
     a.glu_seed = p > 0.f ? seed : nullptr; a.glu_site = site; a.glu_p = p;
-    if ((g16x_on & 4) && kk_cdiv(H, BK) >= 3) {
-        const long c_old = g16_cost((int64_t)kk_cdiv(T, 128) * kk_cdiv(F, 64), 128, 64), c_new = g16_cost((int64_t)kk_cdiv(T, 128) * kk_cdiv(F, 192), 128, 192);
-        if (c_new < c_old) {
-            a.tiles_m = kk_cdiv(T, 128); a.tiles_n = kk_cdiv(F, 192);
-            return kk_g16x_glu_bwd(a, s);
-        }
-    }
-    if ((g16_w8_glu & 1) && kk_cdiv(H, BK) >= 3 && kk_cdiv(T, 128) * kk_cdiv(F, 64) >= g16_thr12864) {       // eight waves on 128x64 tiles, like the plain GEMMs
-        a.tiles_m = kk_cdiv(T, 128);
-        kk_note_kernel("gemm16_w8_glu<1,3,1>");
-        hipLaunchKernelGGL((gemm16_kernel_w8_glu<true, 3, 1>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
-        KK_LAUNCH_CHECK("kk_gemm_dgrad_glu");
-        return 0;
-    }
+    if (c.cfg >= 0) return kk_g16x_glu_bwd(a, s);
     dim3 grid(a.tiles_m * a.tiles_n);
-    kk_note_kernel("gemm16<0,1,64,64,*,1>");
-    if (kk_cdiv(H, BK) < 3) hipLaunchKernelGGL((gemm16_kernel<false, true, 64, 64, 2, 1>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gemm16_kernel<false, true, 64, 64, 3, 1>), grid, dim3(256), 0, s, a);
+    if (c.waves == 8) {                                         // eight waves on 128x64 tiles, like the plain GEMMs
+        kk_note_kernel("gemm16_w8_glu<1,3,1>");
+        hipLaunchKernelGGL((gemm16_kernel_w8_glu<true, 3, 1>), grid, dim3(512), 0, s, a);
+    } else {
+        kk_note_kernel("gemm16<0,1,64,64,*,1>");
+        if (g16_ns(R_GLU_BWD, c, kk_cdiv(H, BK)) == 2) hipLaunchKernelGGL((gemm16_kernel<false, true, 64, 64, 2, 1>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gemm16_kernel<false, true, 64, 64, 3, 1>), grid, dim3(256), 0, s, a);
+    }
     KK_LAUNCH_CHECK("kk_gemm_dgrad_glu");
     return 0;
 }
 
 int kk_gemm16_linear_glu(int64_t T, int64_t F, int64_t K, const void *x, int64_t ldx, const void *W, const float *bias, void *h1,
                          void *g, int64_t ldg, const uint32_t *seed, uint32_t site, float p, int xcd_swizzle, hipStream_t s) {
-    G16Args a = g16_args(0, 0, T, F, K, x, ldx, W, K, g, ldg, 64, 64, xcd_swizzle);      // N = F: a workgroup covers columns n and F + n of the [T, 2F] product
+    const G16Choice c = g16_choose(R_GLU_FWD, T, F, K, true);
+    G16Args a = g16_args(0, 0, T, F, K, x, ldx, W, K, g, ldg, c.tile.bm, c.tile.bn, xcd_swizzle);      // N = F: a workgroup covers columns n and F + n of the [T, 2F] product
     a.bias = bias; a.c_bf16 = 1;
     a.b_bytes = (uint32_t)(((2 * F - 1) * K + K) * 2);     // (both panels of W1)
     a.glu_dh = static_cast<__bf16 *>(h1);
     a.glu_seed = p > 0.f ? seed : nullptr; a.glu_site = site; a.glu_p = p;
-    if ((g16x_on & 4) && kk_cdiv(K, BK) >= 3) {               // 256 rows x (96 + 96) columns per workgroup against 64 x (64 + 64)
-        const long c_old = g16_cost((int64_t)kk_cdiv(T, 64) * kk_cdiv(F, 64), 64, 128), c_new = g16_cost((int64_t)kk_cdiv(T, 256) * kk_cdiv(F, 96), 256, 192);
-        if (c_new < c_old) {
-            a.tiles_m = kk_cdiv(T, 256); a.tiles_n = kk_cdiv(F, 96);
-            return kk_g16x_glu_fwd(a, s);
-        }
-    }
-    if ((g16_w8_glu & 2) && kk_cdiv(K, BK) >= 3 && kk_cdiv(T, 128) * kk_cdiv(F, 64) >= g16_thr12864) {
-        a.tiles_m = kk_cdiv(T, 128);
-        kk_note_kernel("gemm16_w8_glu<0,3,2>");
-        hipLaunchKernelGGL((gemm16_kernel_w8_glu<false, 3, 2>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
-        KK_LAUNCH_CHECK("kk_gemm_linear_glu");
-        return 0;
-    }
+    if (c.cfg >= 0) return kk_g16x_glu_fwd(a, s);
     kk_note_kernel("gemm16<0,0,64,64,2,2>");
     hipLaunchKernelGGL((gemm16_kernel<false, false, 64, 64, 2, 2>), dim3(a.tiles_m * a.tiles_n), dim3(256), 0, s, a);
     KK_LAUNCH_CHECK("kk_gemm_linear_glu");
-    return 0;
-}
-
-// dW_i[M_i, N_i] += dY_i[T_i, M_i]^T . X_i[T_i, N_i] for i < n, one launch (see gemm16_group_kernel).
-int kk_gemm16_wgrad_group(const KkWgradDesc *d, int n, int split_k, int overwrite, int xcd_swizzle, hipStream_t s, void *ss_rec,
-                          const int32_t *ss_seg, int32_t *ss_count) {
-    KkSegRec *rec = static_cast<KkSegRec *>(ss_rec);          // (ss_rec / ss_seg / ss_count: see g16_group_ss)
-    if (n < 1 || n > GROUP_MAX) return kk_fail(KK_EINVAL, "kk_gemm_wgrad_group: 1..%d problems per launch, got %d", GROUP_MAX, n);
-    int total = 0;
-    const int BM = g16_group_tile >= 1 ? 128 : 64, BN = g16_group_tile >= 2 ? 128 : 64;
-    for (int i = 0; i < n; ++i) {
-        if (d[i].M <= 0 || d[i].N <= 0 || d[i].T <= 0 || !d[i].dy || !d[i].x || !d[i].dw)
-            return kk_fail(KK_EINVAL, "kk_gemm_wgrad_group: bad problem %d", i);
-        if (!kk_gemm16_eligible(1, 1, d[i].M, d[i].N, d[i].T, d[i].dy, d[i].lddy, d[i].x, d[i].ldx))
-            return kk_fail(KK_EINVAL, "kk_gemm_wgrad_group: problem %d needs 16-byte aligned bf16 operands with row strides %% 8 == 0", i);
-        total += kk_cdiv(d[i].M, BM) * kk_cdiv(d[i].N, BN);
-    }
-    int splits = 1;
-    {   // 128x128 tiles of the large-tile family: full reductions only, long ones (short launches sit on the side branch, where
-        // a 96 KB workgroup keeps the main chain's workgroups waiting)
-        int total_x = 0;
-        int64_t kmin = 1ll << 40;
-        for (int i = 0; i < n; ++i) { total_x += kk_cdiv(d[i].M, 128) * kk_cdiv(d[i].N, 128); kmin = std::min<int64_t>(kmin, d[i].T); }
-        const bool old_splits = split_k > 1 || g16_group_split > 1 || (split_k <= 0 && !overwrite && total * 2 <= g16_split_target);
-        if ((g16x_on & 8) && !old_splits && kmin >= g16x_min_k_group && g16_cost(total_x, 128, 128) < g16_cost(total, BM, BN)) {
-            G16Group g = {};
-            g.n = n;
-            g.xcd_chunks = (xcd_swizzle && g16x_group_chunks) ? 1 : 0;
-            for (int i = 0; i < n; ++i) {
-                G16Args &a = g.p[i];
-                a = g16_args(1, 1, d[i].M, d[i].N, d[i].T, d[i].dy, d[i].lddy, d[i].x, d[i].ldx, d[i].dw, d[i].lddw, 128, 128, g.xcd_chunks ? 0 : xcd_swizzle);
-                a.beta = overwrite ? 0.f : 1.f; a.dbg = g16x_dbg;
-                a.m_fast = (g16_group_mfast && xcd_swizzle && d[i].M < d[i].N) ? 1 : 0;
-                g.start[i + 1] = g.start[i] + a.tiles_m * a.tiles_n;
-            }
-            g16_group_ss(g, true, rec, ss_seg, ss_count);      // (g16x_body's write-through fp32 epilogue)
-            return kk_g16x_group(g, g.start[n], s);
-        }
-    }
-    if (split_k > 0) splits = split_k;                            // the caller's k-slice count (0 = by the split target)
-    else if (g16_group_split > 0) splits = g16_group_split;
-    else if (total * 2 <= g16_split_target) splits = kk_cdiv(g16_split_target, total);
-    if (overwrite) splits = 1;                                    // (k-slices accumulate with atomics: they need the old value)
-    G16Group g = {};
-    g.n = n;
-    int min_per = 1 << 30;
-    for (int i = 0; i < n; ++i) {
-        const int ktiles = kk_cdiv(d[i].T, BK);
-        int sp = std::min(splits, std::max(ktiles / 2, 1));
-        const int kps = kk_cdiv(ktiles, sp) * BK;
-        sp = kk_cdiv(d[i].T, kps);
-        min_per = std::min(min_per, kps / BK);
-        G16Args &a = g.p[i];
-        a = g16_args(1, 1, d[i].M, d[i].N, d[i].T, d[i].dy, d[i].lddy, d[i].x, d[i].ldx, d[i].dw, d[i].lddw, BM, BN, xcd_swizzle);
-        a.beta = overwrite ? 0.f : 1.f;
-        a.k_per_split = kps; a.splits = sp; a.atomic = sp > 1 ? 1 : 0;
-        a.m_fast = (g16_group_mfast && xcd_swizzle && d[i].M < d[i].N) ? 1 : 0;
-        g.start[i + 1] = g.start[i] + a.tiles_m * a.tiles_n * sp;
-    }
-    g16_group_ss(g, BM == 128 && BN == 64 && g16_group_waves == 8, rec, ss_seg, ss_count);      // (gemm16_body's write-through fp32 epilogue: the eight-wave 128x64 tile)
-    dim3 grid(g.start[n]);
-    kk_note_kernelf("gemm16_group<%d,%d,w%d>", BM, BN, BM == 128 ? g16_group_waves : 4);
-    if (BN == 128 && g16_group_waves == 16) hipLaunchKernelGGL((gemm16_group_kernel<true, true, 128, 128, 2, 16, 4>), grid, dim3(1024), 0, s, g);
-    else if (BN == 128 && g16_group_waves == 8) hipLaunchKernelGGL((gemm16_group_kernel<true, true, 128, 128, 2, 8>), grid, dim3(512), 0, s, g);
-    else if (BN == 128) hipLaunchKernelGGL((gemm16_group_kernel<true, true, 128, 128, 2>), grid, dim3(256), 0, s, g);
-    else if (BM == 128 && g16_group_waves == 8) hipLaunchKernelGGL((gemm16_group_kernel<true, true, 128, 64, 2, 8>), grid, dim3(512), 0, s, g);
-    else if (BM == 128) hipLaunchKernelGGL((gemm16_group_kernel<true, true, 128, 64, 2>), grid, dim3(256), 0, s, g);
-    else if (min_per < 3 || g16_stages < 3) hipLaunchKernelGGL((gemm16_group_kernel<true, true, 64, 64, 2>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((gemm16_group_kernel<true, true, 64, 64, 3>), grid, dim3(256), 0, s, g);
-    KK_LAUNCH_CHECK("kk_gemm_wgrad_group");
     return 0;
 }
 
@@ -470,40 +379,68 @@ int kk_gemm16_qkv_headnorm(int64_t T, int parts, int heads, int64_t K, const voi
                            void *raw, int64_t ldraw, void *y, int64_t ldy, int S, const float *const *gains, int rope_mask,
                            const float *cos_t, const float *sin_t, int xcd_swizzle, hipStream_t s) {
     const int64_t N = (int64_t)parts * heads * 64;
-    G16Args a = g16_args(0, 0, T, N, K, x, ldx, W, K, raw, ldraw, 64, 64, xcd_swizzle);
+    const bool stores16 = ldraw % 8 == 0 && ldy % 8 == 0 && (((uintptr_t)raw | (uintptr_t)y) & 15) == 0;      // (the large tiles' 16-byte stores)
+    const G16Choice c = g16_choose(R_HEADNORM, T, N, K, stores16);
+    G16Args a = g16_args(0, 0, T, N, K, x, ldx, W, K, raw, ldraw, c.tile.bm, c.tile.bn, xcd_swizzle);
     a.bias = bias; a.c_bf16 = 1;
     for (int i = 0; i < parts; ++i) a.hn_gain[i] = gains[i];
     a.hn_cos = cos_t; a.hn_sin = sin_t; a.hn_y = static_cast<__bf16 *>(y); a.hn_ldy = ldy;
     a.hn_S = S; a.hn_H = heads * 64; a.hn_rope_mask = rope_mask;
-    if ((g16x_on & 2) && kk_cdiv(K, BK) >= 3 && N >= g16x_min_n_hn && ldraw % 8 == 0 && ldy % 8 == 0 && (((uintptr_t)raw | (uintptr_t)y) & 15) == 0) {      // (16-byte stores)
-        const bool w8 = g16_w8_hn && kk_cdiv(T, 128) * kk_cdiv(N, 64) >= g16_thr12864;
-        int best = -1;
-        long best_cost = w8 ? g16_cost((int64_t)kk_cdiv(T, 128) * kk_cdiv(N, 64), 128, 64) : g16_cost((int64_t)kk_cdiv(T, 64) * kk_cdiv(N, 64), 64, 64);
-        for (int cfg : {G16X_128x128, G16X_128x192, G16X_256x128, G16X_256x192}) {
-            int bm, bn;
-            kk_g16x_tile(cfg, &bm, &bn);
-            const long c = g16_cost((int64_t)kk_cdiv(T, bm) * kk_cdiv(N, bn), bm, bn);
-            if (c < best_cost) { best = cfg; best_cost = c; }
-        }
-        if (g16x_force >= 0) best = g16x_force;
-        if (best >= 0) {
-            int bm, bn;
-            kk_g16x_tile(best, &bm, &bn);
-            a.tiles_m = kk_cdiv(T, bm); a.tiles_n = kk_cdiv(N, bn); a.dbg = g16x_dbg;
-            return kk_g16x_headnorm(best, a, s);
-        }
-    }
-    if (g16_w8_hn && kk_cdiv(K, BK) >= 3 && kk_cdiv(T, 128) * kk_cdiv(N, 64) >= g16_thr12864) {       // eight waves on 128x64 tiles, like the plain GEMMs
-        a.tiles_m = kk_cdiv(T, 128);
-        kk_note_kernel("gemm16_w8_hn<3>");
-        hipLaunchKernelGGL((gemm16_kernel_w8_hn<3>), dim3(a.tiles_m * a.tiles_n), dim3(512), 0, s, a);
-        KK_LAUNCH_CHECK("kk_gemm_qkv_headnorm");
-        return 0;
+    if (c.cfg >= 0) {
+        a.dbg = g16.dbg;
+        return kk_g16x_headnorm(c.cfg, a, s);
     }
     dim3 grid(a.tiles_m * a.tiles_n);
-    kk_note_kernel("gemm16<0,0,64,64,*,3>");
-    if (kk_cdiv(K, BK) < 3) hipLaunchKernelGGL((gemm16_kernel<false, false, 64, 64, 2, 3>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gemm16_kernel<false, false, 64, 64, 3, 3>), grid, dim3(256), 0, s, a);
+    if (c.waves == 8) {                                         // eight waves on 128x64 tiles, like the plain GEMMs
+        kk_note_kernel("gemm16_w8_hn<3>");
+        hipLaunchKernelGGL((gemm16_kernel_w8_hn<3>), grid, dim3(512), 0, s, a);
+    } else {
+        kk_note_kernel("gemm16<0,0,64,64,*,3>");
+        if (g16_ns(R_HEADNORM, c, kk_cdiv(K, BK)) == 2) hipLaunchKernelGGL((gemm16_kernel<false, false, 64, 64, 2, 3>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gemm16_kernel<false, false, 64, 64, 3, 3>), grid, dim3(256), 0, s, a);
+    }
     KK_LAUNCH_CHECK("kk_gemm_qkv_headnorm");
+    return 0;
+}
+
+// dW_i[M_i, N_i] += dY_i[T_i, M_i]^T . X_i[T_i, N_i] for i < n, one launch (see gemm16_group_kernel): eight waves on 128x64 tiles, or
+// the large-tile family's 128x128 — full reductions only, long ones (short launches sit on the side branch, where a 96 KB workgroup
+// keeps the main chain's workgroups waiting)
+int kk_gemm16_wgrad_group(const KkWgradDesc *d, int n, int split_k, int overwrite, int xcd_swizzle, hipStream_t s, void *ss_rec,
+                          const int32_t *ss_seg, int32_t *ss_count) {
+    if (n < 1 || n > GROUP_MAX) return kk_fail(KK_EINVAL, "kk_gemm_wgrad_group: 1..%d problems per launch, got %d", GROUP_MAX, n);
+    int total = 0, total_x = 0;
+    int64_t kmin = 1ll << 40;
+    for (int i = 0; i < n; ++i) {
+        if (d[i].M <= 0 || d[i].N <= 0 || d[i].T <= 0 || !d[i].dy || !d[i].x || !d[i].dw)
+            return kk_fail(KK_EINVAL, "kk_gemm_wgrad_group: bad problem %d", i);
+        if (!kk_gemm16_eligible(1, 1, d[i].M, d[i].N, d[i].T, d[i].dy, d[i].lddy, d[i].x, d[i].ldx))
+            return kk_fail(KK_EINVAL, "kk_gemm_wgrad_group: problem %d needs 16-byte aligned bf16 operands with row strides %% 8 == 0", i);
+        total += kk_cdiv(d[i].M, 128) * kk_cdiv(d[i].N, 64);
+        total_x += kk_cdiv(d[i].M, 128) * kk_cdiv(d[i].N, 128);
+        kmin = std::min<int64_t>(kmin, d[i].T);
+    }
+    const bool by_target = total * 2 <= g16.split_target;      // (k-slices accumulate with atomics: they need the old value, so never with overwrite)
+    const bool sliced = split_k > 1 || (split_k <= 0 && !overwrite && by_target);
+    const bool large = (g16.on & 8) && !sliced && kmin >= g16.min_k_group && g16_cost(total_x, 128, 128) < g16_cost(total, 128, 64);
+    const int splits = overwrite ? 1 : split_k > 0 ? split_k : by_target ? kk_cdiv(g16.split_target, total) : 1;      // the caller's k-slice count (0 = by the split target)
+    G16Group g = {};
+    g.n = n;
+    g.xcd_chunks = (large && xcd_swizzle && g16.group_chunks) ? 1 : 0;
+    for (int i = 0; i < n; ++i) {
+        const G16Split sp = g16_split_group(d[i].T, splits);
+        G16Args &a = g.p[i];
+        a = g16_args(1, 1, d[i].M, d[i].N, d[i].T, d[i].dy, d[i].lddy, d[i].x, d[i].ldx, d[i].dw, d[i].lddw, 128, large ? 128 : 64, g.xcd_chunks ? 0 : xcd_swizzle);
+        a.beta = overwrite ? 0.f : 1.f;
+        a.k_per_split = sp.k_per_split; a.splits = sp.splits; a.atomic = sp.splits > 1 ? 1 : 0;
+        a.m_fast = (xcd_swizzle && d[i].M < d[i].N) ? 1 : 0;    // sweep direction by operand size
+        if (large) a.dbg = g16.dbg;
+        g.start[i + 1] = g.start[i] + a.tiles_m * a.tiles_n * sp.splits;
+    }
+    g16_group_ss(g, static_cast<KkSegRec *>(ss_rec), ss_seg, ss_count);
+    if (large) return kk_g16x_group(g, g.start[n], s);
+    kk_note_kernel("gemm16_group<128,64,w8>");
+    hipLaunchKernelGGL((gemm16_group_kernel<true, true, 128, 64, 2, 8>), dim3(g.start[n]), dim3(512), 0, s, g);
+    KK_LAUNCH_CHECK("kk_gemm_wgrad_group");
     return 0;
 }

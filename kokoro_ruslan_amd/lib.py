@@ -406,10 +406,6 @@ def gemm_tune16(enable: int = 1, thr128: int = 0, thr12864: int = 0, split_targe
     _tuning_hook("kk_gemm_tune16")(enable, thr128, thr12864, split_target)
 
 
-def gemm_tune_group(split: int = 0) -> None:
-    _tuning_hook("kk_gemm_tune_group")(split)
-
-
 def last_kernel() -> str:
     """The kernel variant the last launching call of this thread took (kk_last_kernel): what tests assert routes with."""
     return load().kk_last_kernel().decode()
