@@ -140,6 +140,39 @@ class _FbKey(NamedTuple):
     tile_norms: bool                                # the grouped weight-gradient launches leave tile-norm records
 
 
+class _AttnOps(NamedTuple):
+    """The workspace views of one attention sub-layer (KokoroEngine._attn_ops): what its forward and its backward both address,
+    named once.  q / k / v are column slices of the containers below them.  A field the caller did not ask for is None (the
+    decode step names the first five alone)."""
+    q_n: torch.Tensor                               # per-head normalised (+ RoPE) q, k, v: what the attention kernels read
+    k_n: torch.Tensor
+    v_n: torch.Tensor
+    ctx: torch.Tensor
+    lse: torch.Tensor
+    q_raw: Optional[torch.Tensor] = None            # the projections before the head norm
+    k_raw: Optional[torch.Tensor] = None
+    v_raw: Optional[torch.Tensor] = None
+    gains: Optional[Tuple] = None                   # the (q, k, v) head-norm gains
+    raw: Optional[torch.Tensor] = None              # the sub-layer's own projection: q|k|v fused [Nq, 3H] (self), q alone (cross)
+    nrm: Optional[torch.Tensor] = None
+    kv_raw: Optional[torch.Tensor] = None           # cross-attention: this layer's K|V slice [Nk, 2H] of the all-layer buffers
+    # with grads:
+    dgains: Optional[Tuple] = None                  # the gains' gradient vectors
+    d_out: Optional[torch.Tensor] = None            # masked gradient of the output projection's result (_tail_bwd wrote it)
+    dctx: Optional[torch.Tensor] = None
+    delta: Optional[torch.Tensor] = None
+    dn: Optional[torch.Tensor] = None               # gradient containers shaped like nrm / raw
+    draw: Optional[torch.Tensor] = None
+    dq_n: Optional[torch.Tensor] = None
+    dk_n: Optional[torch.Tensor] = None
+    dv_n: Optional[torch.Tensor] = None
+    dq_raw: Optional[torch.Tensor] = None
+    dk_raw: Optional[torch.Tensor] = None
+    dv_raw: Optional[torch.Tensor] = None
+    dkv_n: Optional[torch.Tensor] = None            # cross-attention with a K/V branch: the layer's slices of the all-layer gradients
+    dkv_raw: Optional[torch.Tensor] = None
+
+
 class Arena:
     """Flat fp32 slabs p / g / m / v / ema with one 1024-aligned, zero-padded segment per tensor."""
 
@@ -239,6 +272,7 @@ class KokoroEngine:
         # that baked its address in (captured graphs, descriptor tables) is dropped with it (_invalidate).
         self._ws: Dict[str, torch.Tensor] = {}
         self._views: Dict[Tuple, torch.Tensor] = {}
+        self._ops: Dict[Tuple, _AttnOps] = {}          # attention operand records by shape (_attn_ops): views, dropped with them
         self.ws_generation = 0
         self.ws_bytes = 0
         self.max_graphs = int(os.environ.get("KK_MAX_GRAPHS", "24"))     # LRU bound of captured batch shapes
@@ -647,6 +681,7 @@ class KokoroEngine:
     def _invalidate(self) -> None:
         """Forget everything that holds workspace addresses: views, descriptor tables, captured graphs."""
         self._views.clear()
+        self._ops.clear()
         self._tables.clear()
         self._graphs.clear()
         self.ws_generation += 1
@@ -783,11 +818,23 @@ class KokoroEngine:
             if self._grads_fresh and self._ow_seen is not None:
                 self._ow_seen.update((dw.data_ptr(), dw.numel()) for _, _, dw in part)
 
-    def _ln_fwd(self, key, x, prefix, dtype=torch.float32):
+    def _ln_out(self, ln, rows, H):
+        """(gamma, beta, y, mean, rstd) of the LayerNorm ln = (workspace key, parameter prefix, dtype of y) over [rows, H]: the one
+        place that spells the ".y" / ".mean" / ".rstd" keys.  None gives five Nones (a sub-layer tail that no LayerNorm follows); a
+        bare key gives the saved statistics alone (the backward, which holds the parameters and the input itself)."""
+        if ln is None:
+            return None, None, None, None, None
+        if isinstance(ln, str):
+            return None, None, None, self._buf(ln + ".mean", rows), self._buf(ln + ".rstd", rows)
+        key, prefix, dtype = ln
         P = self.arena.P
+        return (P[prefix + ".weight"], P[prefix + ".bias"], self._buf(key + ".y", rows, H, dtype=dtype), self._buf(key + ".mean", rows),
+                self._buf(key + ".rstd", rows))
+
+    def _ln_fwd(self, key, x, prefix, dtype=torch.float32):
         rows, H = x.shape
-        y, mean, rstd = self._buf(key + ".y", rows, H, dtype=dtype), self._buf(key + ".mean", rows), self._buf(key + ".rstd", rows)
-        kk.call("kk_layernorm_fwd", x, P[prefix + ".weight"], P[prefix + ".bias"], y, mean, rstd, rows, H, _b16(y))
+        g, b, y, mean, rstd = self._ln_out((key, prefix, dtype), rows, H)
+        kk.call("kk_layernorm_fwd", x, g, b, y, mean, rstd, rows, H, _b16(y))
         return y
 
     def _partials(self, key, rows, H, ncols, dst0, dst1, split):
@@ -820,8 +867,9 @@ class KokoroEngine:
         P, G = self.arena.P, self.arena.G
         rows, H = x.shape
         part = self._partials(key, rows, H, 2 * H, G[prefix + ".weight"], G[prefix + ".bias"], H)
-        kk.call("kk_layernorm_bwd", dy, x, P[prefix + ".weight"], self._buf(key + ".mean", rows), self._buf(key + ".rstd", rows),
-                dx, 1 if accumulate else 0, G[prefix + ".weight"], G[prefix + ".bias"], part, rows, H, _b16(dy))
+        *_, mean, rstd = self._ln_out(key, rows, H)
+        kk.call("kk_layernorm_bwd", dy, x, P[prefix + ".weight"], mean, rstd, dx, 1 if accumulate else 0, G[prefix + ".weight"],
+                G[prefix + ".bias"], part, rows, H, _b16(dy))
 
     def _tail_bwd(self, key, dn, x, prefix, dres, accumulate, head) -> None:
         """Backward of LayerNorm `key` (input x = the residual stream after the sub-layer `head`), fused — when that
@@ -844,9 +892,9 @@ class KokoroEngine:
             dy = self._buf("tmp.d_attn_proj" + (".x" if hprefix.endswith(".cross_attn") else ""), rows, H, dtype=dt)
             self._reduce_lists[self._tmp_ns].append((part[:, 2 * H:], G[hprefix + ".w_o.bias"], None, nb, H, H, 4 * H))
             p2 = 0.0
-        kk.call("kk_sublayer_in_bwd", dn, _b16(dn), x, P[prefix + ".weight"], self._buf(key + ".mean", rows), self._buf(key + ".rstd", rows),
-                dres, 1 if accumulate else 0, f2, gain, rstd_f, dy, _b16(dy), part, rows, H, S, self.rng, site, p, site + 1, p2,
-                site + 2, dpr)
+        *_, mean, rstd = self._ln_out(key, rows, H)
+        kk.call("kk_sublayer_in_bwd", dn, _b16(dn), x, P[prefix + ".weight"], mean, rstd, dres, 1 if accumulate else 0, f2, gain, rstd_f,
+                dy, _b16(dy), part, rows, H, S, self.rng, site, p, site + 1, p2, site + 2, dpr)
 
     def _reduce_partials(self, shape_key) -> None:
         """One launch that adds the column sums of every partial matrix written so far (by streams already joined into
@@ -875,13 +923,8 @@ class KokoroEngine:
         """Fused tail of a sub-layer on the dropout path (kk_sublayer_out_fwd): x_out = x_res + masks * [RMSNorm](y), and
         the LayerNorm `next_ln = (key, prefix, dtype)` of x_out when the caller names one; returns that LayerNorm's
         output (else None)."""
-        P = self.arena.P
         rows, H = y.shape
-        n = mean = rstd = g = b = None
-        if next_ln is not None:
-            key, prefix, dtype = next_ln
-            n, mean, rstd = self._buf(key + ".y", rows, H, dtype=dtype), self._buf(key + ".mean", rows), self._buf(key + ".rstd", rows)
-            g, b = P[prefix + ".weight"], P[prefix + ".bias"]
+        g, b, n, mean, rstd = self._ln_out(next_ln, rows, H)
         kk.call("kk_sublayer_out_fwd", y, _b16(y), gain, rstd_f, x_res, x_out, g, b, n, _b16(n), mean, rstd, rows, H, S, self.rng,
                 site, p, site + 1, p2, site + 2, dpr)
         return n
@@ -891,41 +934,88 @@ class KokoroEngine:
                   layer=0):
         """x_out = x_res + w_o(attention(...)) + b_o.  xq [B*Sq,H] (post-LN), xkv [B*Sk,H] (None = self-attention).
         Returns LayerNorm_next_ln(x_out) when the fused dropout tail computed it, else None."""
-        P, H, h = self.arena.P, self.dims.hidden, self.dims.heads
-        Nq, Nk = B * Sq, B * Sk
-        dt = xq.dtype                                   # storage of every activation of the sub-layer
+        h, own_kv = self.dims.heads, xkv is None      # own_kv: q|k|v from one fused projection; RoPE on q and k only
         i16 = _b16(xq)
-        cos, sin = self._rope_tables(max(Sq, Sk)) if rope else (None, None)
-        gq, gk, gv = P[prefix + ".q_norm.weight"], P[prefix + ".k_norm.weight"], P[prefix + ".v_norm.weight"]
-        if xkv is None:       # q|k|v from one fused projection; RoPE on q and k only
-            raw, nrm = self._buf(key + ".qkv_raw", Nq, 3 * H, dtype=dt), self._buf(key + ".qkv_n", Nq, 3 * H, dtype=dt)
-            self._proj_headnorm(xq, self._Wf(prefix + ".w_q.weight", 3), raw, nrm, Sq, (gq, gk, gv), 3 if rope else 0, cos, sin)
-            q_raw, k_raw, v_raw, q_n, k_n, v_n = raw, raw[:, H:], raw[:, 2 * H:], nrm, nrm[:, H:], nrm[:, 2 * H:]
-        else:
-            q_raw, q_n = self._buf(key + ".q_raw", Nq, H, dtype=dt), self._buf(key + ".q_n", Nq, H, dtype=dt)
-            kv_raw, kv_n = self._cross_kv(layer, Nk, dt)                              # filled by _cross_kv_fwd_all
-            self._proj_headnorm(xq, self._W(prefix + ".w_q.weight"), q_raw, q_n, Sq, (gq,), 0, None, None)
-            k_raw, v_raw, k_n, v_n = kv_raw, kv_raw[:, H:], kv_n, kv_n[:, H:]
-        ctx, lse = self._buf(key + ".ctx", Nq, H, dtype=dt), self._buf(key + ".lse", B, h, Sq)
+        cos, sin = self._rope_tables(max(Sq, Sk)) if rope and own_kv else (None, None)
+        o = self._attn_ops(key, prefix, xq, xkv, B, Sq, Sk, layer)
+        # (cross-attention: the K|V slices were filled by _cross_kv_fwd_all)
+        self._proj_headnorm(xq, self._attn_wq(prefix, xkv), o.raw, o.nrm, Sq, o.gains[:3 if own_kv else 1],
+                            3 if cos is not None else 0, cos, sin)
         keep = self._attn_keep(key, B, Sq, Sk, p, i16)
         if (self.attn_warm & 3) and i16 and key.startswith("dec") and self.use_shadow:
             # the forward warms the weights of the GEMMs behind it into every XCD's L2 (kk_attn_warm_next): its own output projection, and
-            # the next sub-layer's first matrix (cross-attention: w_q; feed-forward: linear1)
+            # (bit 1) the next sub-layer's first matrix (cross-attention: w_q; feed-forward: linear1)
             base = prefix.rsplit(".", 1)[0]                # "decoder.layers.<i>"
-            nxt = base + (".cross_attn.w_q.weight" if xkv is None else ".ff.linear1.weight")
-            w0, w1 = self._W(prefix + ".w_o.weight"), self._W(nxt)
-            kk.load().kk_attn_warm_next(w0.data_ptr(), w0.numel() * w0.element_size(), w1.data_ptr() if self.attn_warm & 2 else None,
-                                        w1.numel() * w1.element_size())
-        if keep is not None and key in self._keep_ready:      # the bits are there already (kk_attn_keep_gen): the forward reads them
-            kk.call("kk_attn_fwd_rb", q_n, k_n, v_n, ctx, lse, B, h, Sq, Sk, q_n.stride(0), k_n.stride(0), v_n.stride(0), H, key_mask,
-                    1 if causal else 0, 0.125, self.rng, site + 3, p, self.math, i16, keep)
-        elif keep is not None:    # the forward also stores the dropout keep decisions (1 bit per score) for the backward's pair launch
-            kk.call("kk_attn_fwd_kb", q_n, k_n, v_n, ctx, lse, B, h, Sq, Sk, q_n.stride(0), k_n.stride(0), v_n.stride(0), H, key_mask,
-                    1 if causal else 0, 0.125, self.rng, site + 3, p, self.math, i16, keep)
+            nxt = base + (".cross_attn.w_q.weight" if own_kv else ".ff.linear1.weight")
+            self._attn_warm(self._W(prefix + ".w_o.weight"), self._W(nxt), bool(self.attn_warm & 2))
+        # with keep bits the forward stores the dropout keep decisions (1 bit per score) for the backward's pair launch (_kb), or reads
+        # them where kk_attn_keep_gen has written them already (_rb)
+        name = "kk_attn_fwd" if keep is None else "kk_attn_fwd_rb" if key in self._keep_ready else "kk_attn_fwd_kb"
+        self._attn_launch(name, o, B, h, Sq, Sk, key_mask, causal, site + 3, p, own=() if keep is None else (keep,))
+        return self._attn_out(key, prefix, o.ctx, B * Sq, Sq, x_res, x_out, site, p, dpr, next_ln)
+
+    def _attn_ops(self, key, prefix, xq, xkv, B, Sq, Sk, layer=0, grads=False, kv_grads=True) -> _AttnOps:
+        """The operand views of attention sub-layer `key` (self-attention: xkv None; cross-attention: decoder layer `layer`), with
+        grads also those of its backward — dK / dV of cross-attention only with kv_grads (the K/V branch: _cross_kv_bwd_all)."""
+        dt = xq.dtype                                   # storage of every activation of the sub-layer
+        # built once per shape and stream namespace (the "tmp." keys): the views stay what they are until a workspace buffer moves
+        # (_invalidate drops the records with the views), and slicing them anew per call was most of a launch's host time
+        memo = (self._tmp_ns, key, prefix, dt, xkv is None, B, Sq, Sk, layer, grads, kv_grads)
+        o = self._ops.get(memo)
+        if o is not None:
+            return o
+        P, G, H, h = self.arena.P, self.arena.G, self.dims.hidden, self.dims.heads
+        Nq, Nk = B * Sq, B * Sk
+        norms = [f"{prefix}.{c}_norm.weight" for c in "qkv"]
+        if xkv is None:
+            raw, nrm = self._buf(key + ".qkv_raw", Nq, 3 * H, dtype=dt), self._buf(key + ".qkv_n", Nq, 3 * H, dtype=dt)
+            kv_raw, k_raw, v_raw, k_n, v_n = None, raw[:, H:], raw[:, 2 * H:], nrm[:, H:], nrm[:, 2 * H:]
         else:
-            kk.call("kk_attn_fwd", q_n, k_n, v_n, ctx, lse, B, h, Sq, Sk, q_n.stride(0), k_n.stride(0), v_n.stride(0), H, key_mask,
-                    1 if causal else 0, 0.125, self.rng, site + 3, p, self.math, i16)
-        return self._attn_out(key, prefix, ctx, Nq, Sq, x_res, x_out, site, p, dpr, next_ln)
+            raw, nrm = self._buf(key + ".q_raw", Nq, H, dtype=dt), self._buf(key + ".q_n", Nq, H, dtype=dt)
+            kv_raw, kv_n = self._cross_kv(layer, Nk, dt)
+            k_raw, v_raw, k_n, v_n = kv_raw, kv_raw[:, H:], kv_n, kv_n[:, H:]
+        o = _AttnOps(nrm, k_n, v_n, self._buf(key + ".ctx", Nq, H, dtype=dt), self._buf(key + ".lse", B, h, Sq),
+                     q_raw=raw, k_raw=k_raw, v_raw=v_raw, gains=tuple(P[n] for n in norms), raw=raw, nrm=nrm, kv_raw=kv_raw)
+        if grads:
+            # cross-attention: dctx / delta are read by the K/V branch on its own stream, so each layer keeps its own
+            ck = "tmp" if xkv is None else key
+            dk_n = dv_n = dk_raw = dv_raw = dkv_n = dkv_raw = None
+            if xkv is None:
+                dn, draw = self._buf("tmp.dqkv_n", Nq, 3 * H, dtype=dt), self._buf("tmp.dqkv_raw", Nq, 3 * H, dtype=dt)
+                dk_n, dv_n, dk_raw, dv_raw = dn[:, H:], dn[:, 2 * H:], draw[:, H:], draw[:, 2 * H:]
+            else:
+                dn, draw = self._buf("tmp.dq_n", Nq, H, dtype=dt), self._buf("tmp.dq_raw", Nq, H, dtype=dt)
+                if kv_grads:
+                    dkv_raw, dkv_n = self._cross_kv(layer, Nk, dt, "d")
+                    dk_n, dv_n, dk_raw, dv_raw = dkv_n, dkv_n[:, H:], dkv_raw, dkv_raw[:, H:]
+            o = o._replace(dgains=tuple(G[n] for n in norms), dctx=self._buf(ck + ".dctx", Nq, H, dtype=dt),
+                           d_out=self._buf("tmp.d_attn_proj" + ("" if xkv is None else ".x"), Nq, H, dtype=dt),
+                           delta=self._buf(ck + ".delta", B, h, Sq), dn=dn, draw=draw, dq_n=dn, dk_n=dk_n, dv_n=dv_n,
+                           dq_raw=draw, dk_raw=dk_raw, dv_raw=dv_raw, dkv_n=dkv_n, dkv_raw=dkv_raw)
+        if len(self._ops) >= 4096:                      # (dynamic batching: every new shape adds its records)
+            self._ops.clear()
+        self._ops[memo] = o
+        return o
+
+    def _attn_wq(self, prefix, xkv):
+        """Weight operand of the sub-layer's own projection: q|k|v fused (self-attention) or q alone."""
+        return self._Wf(prefix + ".w_q.weight", 3) if xkv is None else self._W(prefix + ".w_q.weight")
+
+    def _attn_launch(self, name, o, B, h, Sq, Sk, key_mask, causal, site, p, outs=(), own=()):
+        """Every kk_attn_* launch of the engine, their positional order written once: the operands of `o`, the problem, the row strides,
+        the mask ... storage tail.  The forward entry points (no outs) write o.ctx and o.lse; the backward ones read o.dctx, o.lse
+        and o.delta and write `outs` (dQ | dK, dV | all three).  own: what only this entry point takes, in its order — keep bits;
+        the head-norm tables; ctx and its stride (kk_attn_bwd_dq); the dS workspace and its size (kk_attn_bwd_ws).  B, h: the
+        decode step passes 1 and B * heads over its time-major caches."""
+        mid = (o.dctx, o.lse, o.delta, *outs) if outs else (o.ctx, o.lse)
+        kk.call(name, o.q_n, o.k_n, o.v_n, *mid, B, h, Sq, Sk, o.q_n.stride(0), o.k_n.stride(0), o.v_n.stride(0), mid[0].stride(0),
+                *[t.stride(0) for t in outs], key_mask, 1 if causal else 0, 0.125, self.rng, site, p, self.math, _b16(o.q_n), *own)
+
+    def _attn_warm(self, w0, w1=None, second=True):
+        """kk_attn_warm_next: the next attention forward or pair launch of this thread touches the lines of w0 (and w1) so that the
+        GEMMs behind it find them in L2.  second=False names w1 by its size alone, which the library reads as "w0 only"."""
+        kk.load().kk_attn_warm_next(w0.data_ptr(), w0.numel() * w0.element_size(), w1.data_ptr() if w1 is not None and second else None,
+                                    w1.numel() * w1.element_size() if w1 is not None else 0)
 
     def _attn_out(self, key, prefix, ctx, Nq, Sq, x_res, x_out, site, p, dpr, next_ln, split_k=0):
         """The output projection and residual tail of an attention sub-layer: x_out = x_res + w_o(ctx) + b_o, and LayerNorm_next_ln."""
@@ -938,11 +1028,7 @@ class KokoroEngine:
         p16 = self.attn_proj_bf16 and i16 and key.startswith("dec")
         if (p16 and self.fuse_linear_tail and _b16(Wo) and self.math == kk.KK_MATH_BF16 and kk.load().kk_linear_tail_pays(Nq, H, H)):
             # projection + tail as ONE row-owner launch (kk_linear_tail_fwd: same bits as the two launches below)
-            n = mean = rstd = g = b = None
-            if next_ln is not None:
-                lkey, lprefix, ldt = next_ln
-                n, mean, rstd = self._buf(lkey + ".y", Nq, H, dtype=ldt), self._buf(lkey + ".mean", Nq), self._buf(lkey + ".rstd", Nq)
-                g, b = P[lprefix + ".weight"], P[lprefix + ".bias"]
+            g, b, n, mean, rstd = self._ln_out(next_ln, Nq, H)
             kk.call("kk_linear_tail_fwd", ctx, ctx.stride(0), Wo, P[prefix + ".w_o.bias"], H, None, 1, None, None, x_res, x_out, g, b, n,
                     _b16(n), mean, rstd, Nq, H, Sq, self.rng, site, p, site + 1, 0.0, site + 2, dpr)
             return n
@@ -979,10 +1065,14 @@ class KokoroEngine:
     def _cross_kv(self, layer, Nk, dt, which="", ns=""):
         """(raw, normed) K|V of cross-attention layer `layer`: column slices [.., 2H] of the all-layer buffers (row stride
         layers*2H); which = "d" for their gradients; ns = a key prefix of the buffers (generate_batch: its own)."""
-        H, L = self.dims.hidden, self.dims.dec_layers
-        raw = self._buf(f"{ns}dec.ca.{which}kv_raw_all", Nk, 2 * H * L, dtype=dt)
-        nrm = self._buf(f"{ns}dec.ca.{which}kv_n_all", Nk, 2 * H * L, dtype=dt)
+        H = self.dims.hidden
+        raw, nrm = self._cross_kv_all(Nk, dt, which, ns)
         return raw[:, 2 * H * layer:2 * H * (layer + 1)], nrm[:, 2 * H * layer:2 * H * (layer + 1)]
+
+    def _cross_kv_all(self, Nk, dt, which="", ns=""):
+        """The all-layer buffers themselves: (raw, normed) K|V of every cross-attention layer, [Nk, layers * 2H]."""
+        W = 2 * self.dims.hidden * self.dims.dec_layers
+        return self._buf(f"{ns}dec.ca.{which}kv_raw_all", Nk, W, dtype=dt), self._buf(f"{ns}dec.ca.{which}kv_n_all", Nk, W, dtype=dt)
 
     def _proj_headnorm(self, x, W, raw, nrm, S, gains, rope_mask, cos, sin, split_k=0):
         """raw = x.W^T (an attention projection of len(gains) parts x heads x 64 columns, no bias: transformers.py:131-136)
@@ -1006,8 +1096,7 @@ class KokoroEngine:
         weights are contiguous in the arena), then the per-head RMSNorm of each layer's slice (no RoPE:
         transformers.py:268-277 applies it to self-attention only)."""
         P, H, h, L = self.arena.P, self.dims.hidden, self.dims.heads, self.dims.dec_layers
-        raw_all = self._buf(f"{ns}dec.ca.kv_raw_all", Nk, 2 * H * L, dtype=dt)
-        nrm_all = self._buf(f"{ns}dec.ca.kv_n_all", Nk, 2 * H * L, dtype=dt)
+        raw_all, nrm_all = self._cross_kv_all(Nk, dt, ns=ns)
         last = L if last is None else last                 # layers [first, last): a column slice of the all-layer buffers
         gains = [P[f"decoder.layers.{l}.cross_attn.{kv}_norm.weight"] for l in range(first, last) for kv in ("k", "v")]
         c0, c1 = 2 * H * first, 2 * H * last
@@ -1016,8 +1105,8 @@ class KokoroEngine:
 
     def _cross_kv_bwd_all(self, xkv, Nk, dt, d_xkv, wgrad=True, dgrad=True):
         """Weight gradient of all layers' K/V projections and the memory gradient: two GEMMs over the all-layer buffer."""
-        a, H, L = self.arena, self.dims.hidden, self.dims.dec_layers
-        draw_all = self._buf("dec.ca.dkv_raw_all", Nk, 2 * H * L, dtype=dt)
+        a, L = self.arena, self.dims.dec_layers
+        draw_all, _ = self._cross_kv_all(Nk, dt, "d")     # (what every layer's _attn_bwd wrote its slice of)
         if wgrad:
             with self._grouped_wgrads():                # (a group of one — the 128x64-tile, full-reduction launch — or a member of the
                 self._wgrad(draw_all, xkv, a.fused(a.g, "decoder.layers.0.cross_attn.w_k.weight", 2 * L))   # caller's open group)
@@ -1028,133 +1117,81 @@ class KokoroEngine:
                   site=0, p=0.0, dpr=0.0, layer=0):
         """Given d_out = dL/d(sub-layer output, pre-residual), accumulate parameter grads, write d_xq (dL/d xq) and,
         for cross-attention, d_xkv (+= when d_xkv_beta == 1)."""
-        a, P, G, H, h = self.arena, self.arena.P, self.arena.G, self.dims.hidden, self.dims.heads
-        Nq, Nk = B * Sq, B * Sk
-        dt = xq.dtype
-        i16 = _b16(xq)
-        cos, sin = self._rope_tables(max(Sq, Sk)) if rope else (None, None)
-        ctx, lse = self._buf(key + ".ctx", Nq, H, dtype=dt), self._buf(key + ".lse", B, h, Sq)
-        # cross-attention: dctx / delta are read by the K/V branch on its own stream, so each layer keeps its own
-        ck = "tmp" if xkv is None else key
-        dctx, delta = self._buf(ck + ".dctx", Nq, H, dtype=dt), self._buf(ck + ".delta", B, h, Sq)
+        a, G, H, h, own_kv = self.arena, self.arena.G, self.dims.hidden, self.dims.heads, xkv is None
+        Nq, Nk, i16 = B * Sq, B * Sk, _b16(xq)
+        kv_branch = own_kv or d_xkv is not None           # (cross-attention: its two GEMMs run once for all layers, _cross_kv_bwd_all)
+        cos, sin = self._rope_tables(max(Sq, Sk)) if rope and own_kv else (None, None)
+        o = self._attn_ops(key, prefix, xq, xkv, B, Sq, Sk, layer, grads=True, kv_grads=kv_branch)
         # _tail_bwd (the fused LayerNorm backward before this call) already wrote the masked gradient of the projection
         # output and the column sums for w_o.bias
-        d_out = self._buf("tmp.d_attn_proj" + ("" if xkv is None else ".x"), Nq, H, dtype=dt)
-        self._wgrad(d_out, ctx, G[prefix + ".w_o.weight"], None)
+        d_out = o.d_out
+        self._wgrad(d_out, o.ctx, G[prefix + ".w_o.weight"], None)
         Wo = self._W(prefix + ".w_o.weight")
         # Delta = rowsum(dctx * ctx): from the epilogue of this GEMM when the pair launch below takes it as an input, else computed
         # by the dQ kernel from fragments it holds anyway (and read by the dK/dV kernel launched after it)
-        pair = bool(self.attn_bwd_pair and self.fuse_headnorm_bwd and i16 and _b16(d_out) and _b16(Wo) and (xkv is None or d_xkv is not None)
+        pair = bool(self.attn_bwd_pair and self.fuse_headnorm_bwd and i16 and _b16(d_out) and _b16(Wo) and kv_branch
                     and min(Sq, Sk) > self.attn_pair_min_seq and kk.load().kk_gemm_dgrad_delta_supported(Nq, H, H))
         if pair:
-            kk.call("kk_gemm_dgrad_delta", Nq, H, H, d_out, d_out.stride(0), Wo, Wo.shape[1], dctx, dctx.stride(0), ctx, ctx.stride(0),
-                    delta, Sq, h)
+            kk.call("kk_gemm_dgrad_delta", Nq, H, H, d_out, d_out.stride(0), Wo, Wo.shape[1], o.dctx, o.dctx.stride(0), o.ctx,
+                    o.ctx.stride(0), o.delta, Sq, h)
         else:
-            self._dgrad(d_out, Wo, dctx)
-        if xkv is None:
-            raw, nrm = self._buf(key + ".qkv_raw", Nq, 3 * H, dtype=dt), self._buf(key + ".qkv_n", Nq, 3 * H, dtype=dt)
-            dn, draw = self._buf("tmp.dqkv_n", Nq, 3 * H, dtype=dt), self._buf("tmp.dqkv_raw", Nq, 3 * H, dtype=dt)
-            q_raw, k_raw, v_raw, q_n, k_n, v_n = raw, raw[:, H:], raw[:, 2 * H:], nrm, nrm[:, H:], nrm[:, 2 * H:]
-            dq_n, dk_n, dv_n, dq_raw, dk_raw, dv_raw = dn, dn[:, H:], dn[:, 2 * H:], draw, draw[:, H:], draw[:, 2 * H:]
-        else:
-            q_raw, q_n = self._buf(key + ".q_raw", Nq, H, dtype=dt), self._buf(key + ".q_n", Nq, H, dtype=dt)
-            kv_raw, kv_n = self._cross_kv(layer, Nk, dt)
-            dq_n, dq_raw = self._buf("tmp.dq_n", Nq, H, dtype=dt), self._buf("tmp.dq_raw", Nq, H, dtype=dt)
-            k_raw, v_raw, k_n, v_n = kv_raw, kv_raw[:, H:], kv_n, kv_n[:, H:]
-        ld = lambda t: t.stride(0)
-        gq, gk, gv = P[prefix + ".q_norm.weight"], P[prefix + ".k_norm.weight"], P[prefix + ".v_norm.weight"]
-        dgq, dgk, dgv = G[prefix + ".q_norm.weight"], G[prefix + ".k_norm.weight"], G[prefix + ".v_norm.weight"]
-        cz = 1 if causal else 0
-        fuse = self.fuse_headnorm_bwd
-
-        def hn_tables(tag, S, entries):
-            """KkAttnHeadNorm descriptors of one backward launch (cached: every pointer is a persistent buffer) with their
-            partial gain-gradient rows registered for the reduction at the end of the backward."""
-            nb = kk.load().kk_attn_bwd_blocks(B, h, S)
-            part = self._buf(f"{key}.hnpart.{tag}", len(entries), nb, 64)
-            tk = ("hn", self._tmp_ns, key, tag, B, S, part.data_ptr()) + tuple(
-                (r.data_ptr(), r.stride(0), g_.data_ptr(), c_.data_ptr() if c_ is not None else 0) for r, g_, _, c_, _ in entries)
-            table = self._table(tk, lambda: kk.attn_headnorm([(r, g_, part[j], c_, s_) for j, (r, g_, _, c_, s_) in enumerate(entries)]))
-            for j, (_, _, dg_, _, _) in enumerate(entries):
-                self._reduce_lists[self._tmp_ns].append((part[j], dg_, None, nb, 64, 64))
-            return table
-
-        def warm_bwd():
-            """the dQ half of the pair launch warms the weights of the dgrad GEMM(s) behind it (kk_attn_warm_next)"""
-            if not (self.attn_warm & 12) or not (i16 and key.startswith("dec") and self.use_shadow):
-                return
-            w0 = self._Wf(prefix + ".w_q.weight", 3) if xkv is None else self._W(prefix + ".w_q.weight")
-            w1 = None
-            if self.attn_warm & 8:       # ... and of the output projection whose dgrad comes after the tail behind that (the self-attention's, from the cross-attention)
-                base = prefix.rsplit(".", 1)[0]
-                w1 = self._W(base + ".self_attn.w_o.weight") if xkv is not None else None
-            kk.load().kk_attn_warm_next(w0.data_ptr(), w0.numel() * w0.element_size(), w1.data_ptr() if w1 is not None else None,
-                                        w1.numel() * w1.element_size() if w1 is not None else 0)
-
-        def bwd_one_call(*args):
-            """kk_attn_bwd, or — where the library says the shape pays (kk_attn_bwd_two_pass: no shape at present, see there) —
-            kk_attn_bwd_ws with this stream's dS workspace (2 bytes per score; "tmp.": private to the stream)."""
-            if self.attn_two_pass and kk.load().kk_attn_bwd_two_pass(B, h, Sq, Sk, cz):
-                need = kk.load().kk_attn_bwd_ws_bytes(B, h, Sq, Sk)
-                kk.call("kk_attn_bwd_ws", *args, self._buf("tmp.attn_dS", need, dtype=torch.uint8), need)
-                return
+            self._dgrad(d_out, Wo, o.dctx)
+        # where dQ, dK and dV land: the raw projections' gradients, the head norms' backward being the epilogue of the attention
+        # backward kernels (their tables: RoPE on q and k of self-attention), or the normed ones, with kk_headnorm_rope_bwd behind
+        epi = pair or self.fuse_headnorm_bwd
+        (gq, gk, gv), (dgq, dgk, dgv) = o.gains, o.dgains
+        dq, dk, dv = (o.dq_raw, o.dk_raw, o.dv_raw) if epi else (o.dq_n, o.dk_n, o.dv_n)
+        hq = self._hn_table(key, "q", B, Sq, [(o.q_raw, gq, dgq, cos, sin)]) if epi else None
+        hkv = None
+        if epi and kv_branch:      # (built before the dQ launch also where dK / dV have a launch of their own: same table, same order)
+            hkv = self._hn_table(key, "kv", B, Sk, [(o.k_raw, gk, dgk, cos, sin), (o.v_raw, gv, dgv, None, None)])
+        launch = (o, B, h, Sq, Sk, key_mask, causal, site + 3, p)
+        if pair and self.attn_two_pass and kk.load().kk_attn_bwd_two_pass(B, h, Sq, Sk, 1 if causal else 0):
+            # where the library says the shape pays (no shape at present, see there): the dK/dV kernel also stores dS, and a dQ pass
+            # without softmax work reads it from this stream's workspace (2 bytes per score; "tmp.": private to the stream)
+            need = kk.load().kk_attn_bwd_ws_bytes(B, h, Sq, Sk)
+            self._attn_launch("kk_attn_bwd_ws", *launch, (dq, dk, dv), (hq, hkv, self._buf("tmp.attn_dS", need, dtype=torch.uint8), need))
+        elif pair:         # dQ | dK, dV in one launch
             keep = self._attn_keep(key, B, Sq, Sk, p, i16)          # (the buffer the forward of this sub-layer filled)
-            warm_bwd()
-            if keep is not None:
-                kk.call("kk_attn_bwd_kb", *args, keep)
-            else:
-                kk.call("kk_attn_bwd", *args)
-
-        if xkv is None:
-            if pair:       # dQ | dK, dV in one launch, the head norms' backward as their epilogues
-                bwd_one_call(q_n, k_n, v_n, dctx, lse, delta, dq_raw, dk_raw, dv_raw, B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H,
-                             ld(dq_raw), ld(dk_raw), ld(dv_raw), key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16,
-                             hn_tables("q", Sq, [(q_raw, gq, dgq, cos, sin)]),
-                             hn_tables("kv", Sk, [(k_raw, gk, dgk, cos, sin), (v_raw, gv, dgv, None, None)]))
-            elif fuse:     # the head norms' backward is the epilogue of the two attention backward kernels
-                kk.call("kk_attn_bwd_dq", q_n, k_n, v_n, dctx, lse, delta, dq_raw, B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H, ld(dq_raw),
-                        key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16, ctx, H, hn_tables("q", Sq, [(q_raw, gq, dgq, cos, sin)]))
-                kk.call("kk_attn_bwd_dkv", q_n, k_n, v_n, dctx, lse, delta, dk_raw, dv_raw, B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H,
-                        ld(dk_raw), ld(dv_raw), key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16,
-                        hn_tables("kv", Sk, [(k_raw, gk, dgk, cos, sin), (v_raw, gv, dgv, None, None)]))
-            else:
-                kk.call("kk_attn_bwd_dq", q_n, k_n, v_n, dctx, lse, delta, dq_n, B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H, ld(dq_n),
-                        key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16, ctx, H, None)
-                kk.call("kk_attn_bwd_dkv", q_n, k_n, v_n, dctx, lse, delta, dk_n, dv_n, B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H,
-                        ld(dk_n), ld(dv_n), key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16, None)
-                kk.call("kk_headnorm_rope_bwd", dn, 3 * H, raw, 3 * H, draw, 3 * H, Nq, h, Sq, 3, gq, gk, gv, dgq, dgk, dgv,
-                        self._headnorm_partials(key, Nq, (dgq, dgk, dgv)), 3 if rope else 0, cos, sin, i16)
-            self._wgrad(draw, xq, a.fused(a.g, prefix + ".w_q.weight", 3))
-            self._dgrad(draw, self._Wf(prefix + ".w_q.weight", 3), d_xq)
-            return
-        if pair:
-            dkv_raw, _ = self._cross_kv(layer, Nk, dt, "d")
-            bwd_one_call(q_n, k_n, v_n, dctx, lse, delta, dq_raw, dkv_raw, dkv_raw[:, H:], B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H,
-                         ld(dq_raw), ld(dkv_raw), ld(dkv_raw), key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16,
-                         hn_tables("q", Sq, [(q_raw, gq, dgq, None, None)]),
-                         hn_tables("kv", Sk, [(k_raw, gk, dgk, None, None), (v_raw, gv, dgv, None, None)]))
-        elif fuse:
-            kk.call("kk_attn_bwd_dq", q_n, k_n, v_n, dctx, lse, delta, dq_raw, B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H, ld(dq_raw),
-                    key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16, ctx, H,
-                    hn_tables("q", Sq, [(q_raw, gq, dgq, None, None)]))      # also writes delta
-            if d_xkv is not None:    # key/value branch; its two GEMMs run once for all layers (_cross_kv_bwd_all)
-                dkv_raw, _ = self._cross_kv(layer, Nk, dt, "d")
-                kk.call("kk_attn_bwd_dkv", q_n, k_n, v_n, dctx, lse, delta, dkv_raw, dkv_raw[:, H:], B, h, Sq, Sk, ld(q_n), ld(k_n),
-                        ld(v_n), H, ld(dkv_raw), ld(dkv_raw), key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16,
-                        hn_tables("kv", Sk, [(k_raw, gk, dgk, None, None), (v_raw, gv, dgv, None, None)]))
+            if (self.attn_warm & 12) and i16 and key.startswith("dec") and self.use_shadow:
+                # the dQ half of the pair launch warms the weights of the dgrad GEMM(s) behind it, and (bit 3, from the cross-attention)
+                # the self-attention's output projection, whose dgrad comes after the tail behind that
+                w1 = self._W(prefix.rsplit(".", 1)[0] + ".self_attn.w_o.weight") if self.attn_warm & 8 and not own_kv else None
+                self._attn_warm(self._attn_wq(prefix, xkv), w1)
+            self._attn_launch("kk_attn_bwd" if keep is None else "kk_attn_bwd_kb", *launch, (dq, dk, dv),
+                              (hq, hkv) if keep is None else (hq, hkv, keep))
         else:
-            kk.call("kk_attn_bwd_dq", q_n, k_n, v_n, dctx, lse, delta, dq_n, B, h, Sq, Sk, ld(q_n), ld(k_n), ld(v_n), H, ld(dq_n),
-                    key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16, ctx, H, None)      # also writes delta
-            if d_xkv is not None:
-                dkv_raw, dkv_n = self._cross_kv(layer, Nk, dt, "d")
-                kk.call("kk_attn_bwd_dkv", q_n, k_n, v_n, dctx, lse, delta, dkv_n, dkv_n[:, H:], B, h, Sq, Sk, ld(q_n), ld(k_n),
-                        ld(v_n), H, ld(dkv_n), ld(dkv_n), key_mask, cz, 0.125, self.rng, site + 3, p, self.math, i16, None)
-                kk.call("kk_headnorm_rope_bwd", dkv_n, ld(dkv_n), kv_raw, ld(kv_raw), dkv_raw, ld(dkv_raw), Nk, h, Sk, 2, gk, gv, None,
-                        dgk, dgv, None, self._headnorm_partials(key + ".kv", Nk, (dgk, dgv)), 0, None, None, i16)
-            kk.call("kk_headnorm_rope_bwd", dq_n, H, q_raw, H, dq_raw, H, Nq, h, Sq, 1, gq, None, None, dgq, None, None,
-                    self._headnorm_partials(key + ".q", Nq, (dgq,)), 0, None, None, i16)
-        self._wgrad(dq_raw, xq, G[prefix + ".w_q.weight"])
-        self._dgrad(dq_raw, self._W(prefix + ".w_q.weight"), d_xq)
+            self._attn_launch("kk_attn_bwd_dq", *launch, (dq,), (o.ctx, o.ctx.stride(0), hq))      # also writes delta
+            if kv_branch:
+                self._attn_launch("kk_attn_bwd_dkv", *launch, (dk, dv), (hkv,))
+        if not epi:        # self-attention: one 3-part launch; cross-attention: K|V (if that branch runs), then q
+            if kv_branch and not own_kv:
+                self._headnorm_bwd(key + ".kv", o.dkv_n, o.kv_raw, o.dkv_raw, Nk, Sk, (gk, gv), (dgk, dgv), 0, None, None)
+            n = 3 if own_kv else 1
+            self._headnorm_bwd(key if own_kv else key + ".q", o.dn, o.raw, o.draw, Nq, Sq, o.gains[:n], o.dgains[:n],
+                               3 if cos is not None else 0, cos, sin)
+        self._wgrad(o.draw, xq, a.fused(a.g, prefix + ".w_q.weight", 3) if own_kv else G[prefix + ".w_q.weight"])
+        self._dgrad(o.draw, self._attn_wq(prefix, xkv), d_xq)
+
+    def _hn_table(self, key, tag, B, S, entries):
+        """KkAttnHeadNorm descriptors of one attention backward launch of sub-layer `key` (cached: every pointer is a persistent
+        buffer) with their partial gain-gradient rows registered for the reduction at the end of the backward.
+        entries = [(raw projection, gain, gain gradient, cos | None, sin | None)]."""
+        nb = kk.load().kk_attn_bwd_blocks(B, self.dims.heads, S)
+        part = self._buf(f"{key}.hnpart.{tag}", len(entries), nb, 64)
+        tk = ("hn", self._tmp_ns, key, tag, B, S, part.data_ptr()) + tuple(
+            (r.data_ptr(), r.stride(0), g_.data_ptr(), c_.data_ptr() if c_ is not None else 0) for r, g_, _, c_, _ in entries)
+        table = self._table(tk, lambda: kk.attn_headnorm([(r, g_, part[j], c_, s_) for j, (r, g_, _, c_, s_) in enumerate(entries)]))
+        for j, (_, _, dg_, _, _) in enumerate(entries):
+            self._reduce_lists[self._tmp_ns].append((part[j], dg_, None, nb, 64, 64))
+        return table
+
+    def _headnorm_bwd(self, pkey, dn, raw, draw, rows, S, gains, dgains, rope_mask, cos, sin):
+        """The per-head RMSNorm (+ RoPE) backward of len(gains) <= 3 parts as its own launch (the unfused arm): draw from dn and raw,
+        the gain gradients as partial rows under `pkey`."""
+        pad = (None,) * (3 - len(gains))
+        kk.call("kk_headnorm_rope_bwd", dn, dn.stride(0), raw, raw.stride(0), draw, draw.stride(0), rows, self.dims.heads, S, len(gains),
+                *gains, *pad, *dgains, *pad, self._headnorm_partials(pkey, rows, dgains), rope_mask, cos, sin, _b16(dn))
 
     # ------------------------------------------------------------------ text encoder: all layers in one launch
     def _encoder_stack_ok(self, B: int, Pn: int) -> bool:
@@ -1176,26 +1213,28 @@ class KokoroEngine:
         layers = []
         for i in range(L):
             lay = self._enc_layer(i)
-            pf, key, (nkey, npf, ndt) = lay.prefix, lay.key, lay.next_ln["ff"]
+            pf, key, ndt = lay.prefix, lay.key, lay.next_ln["ff"][2]
             sa, ff = key + ".sa", key + ".ff"
+            ln2_g, ln2_b, y2, mean2, rstd2 = self._ln_out(lay.next_ln["sa"], Ne, H)
+            next_g, next_b, next_y, next_mean, next_rstd = self._ln_out(lay.next_ln["ff"], Ne, H)
             layers.append(dict(
                 w_qkv=self._Wf(pf + ".self_attn.w_q.weight", 3), g_q=P[pf + ".self_attn.q_norm.weight"],
                 g_k=P[pf + ".self_attn.k_norm.weight"], g_v=P[pf + ".self_attn.v_norm.weight"],
                 w_o=self._W(pf + ".self_attn.w_o.weight"), b_o=P[pf + ".self_attn.w_o.bias"],
-                ln2_g=P[pf + ".norm2.weight"], ln2_b=P[pf + ".norm2.bias"],
+                ln2_g=ln2_g, ln2_b=ln2_b,
                 w1=self._W(pf + ".ff.linear1.weight"), b1=P[pf + ".ff.linear1.bias"],
                 w2=self._W(pf + ".ff.linear2.weight"), b2=P[pf + ".ff.linear2.bias"], ffn_gain=P[pf + ".ff.output_norm.weight"],
-                next_g=P[npf + ".weight"], next_b=P[npf + ".bias"],
+                next_g=next_g, next_b=next_b,
                 y1=self._buf(key + ".ln1.y", Ne, H, dtype=edt),
                 qkv_raw=self._buf(sa + ".qkv_raw", Ne, 3 * H, dtype=edt), qkv_n=self._buf(sa + ".qkv_n", Ne, 3 * H, dtype=edt),
                 ctx=self._buf(sa + ".ctx", Ne, H, dtype=edt), lse=self._buf(sa + ".lse", B, h, Pn),
                 proj=self._buf(sa + ".proj", Ne, H),
                 x_in=x0 if i == 0 else self._buf(f"enc{i - 1}.xo", Ne, H), xm=self._buf(key + ".xm", Ne, H),
-                y2=self._buf(key + ".ln2.y", Ne, H, dtype=edt), mean2=self._buf(key + ".ln2.mean", Ne), rstd2=self._buf(key + ".ln2.rstd", Ne),
+                y2=y2, mean2=mean2, rstd2=rstd2,
                 h1=self._buf(ff + ".h1", Ne, 2 * F, dtype=edt), g=self._buf(ff + ".g", Ne, F, dtype=edt),
                 f2=self._buf(ff + ".f2", Ne, H, dtype=edt), rstd_f=self._buf(ff + ".rstd_f", Ne),
-                xo=self._buf(key + ".xo", Ne, H), next_y=self._buf(nkey + ".y", Ne, H, dtype=ndt),
-                next_mean=self._buf(nkey + ".mean", Ne), next_rstd=self._buf(nkey + ".rstd", Ne),
+                xo=self._buf(key + ".xo", Ne, H), next_y=next_y,
+                next_mean=next_mean, next_rstd=next_rstd,
                 next_y_bf16=1 if ndt == torch.bfloat16 else 0, site=lay.site["sa"], p=float(p_enc), dpr=float(self._dpr(i, L))))
         sig = ("encstack", B, Pn, float(p_enc), self.train_dropout, self.enc_placement) + tuple(v.data_ptr() for v in layers[0].values() if hasattr(v, "data_ptr"))
         desc = self._table(sig, lambda: kk.enc_stack(B, Pn, H, F, h, text_mask, cos, sin, self.rng, self._enc_sync, layers, self.enc_placement,
@@ -1837,16 +1876,13 @@ class KokoroEngine:
             qb = self._buf(key + ".q", 1, BH, dtype=ddt)
             kk.call("kk_decode_cache_append", nrm, qb, Kc, Vc, t_dev, B, H, _b16(nrm))
             ctx, lse = self._buf(key + ".ctx", 1, BH, dtype=ddt), self._buf(key + ".lse", 1, B * h, 1)
-            kk.call("kk_attn_fwd", qb, Kc, Vc, ctx, lse, 1, B * h, 1, max_expected, BH, BH, BH, BH, kmask, 0, 0.125, self.rng,
-                    0, 0.0, self.math, _b16(qb))
+            self._attn_launch("kk_attn_fwd", _AttnOps(qb, Kc, Vc, ctx, lse), 1, B * h, 1, max_expected, kmask, False, 0, 0.0)
             return ctx.view(B, H)
 
         def cross_attn(i, key, q_n):
             _, kv_n = self._cross_kv(i, B * T, ddt, ns=kv_ns)              # filled by _cross_kv_fwd_all
-            k_n, v_n = kv_n, kv_n[:, H:]
             ctx, lse = self._buf(key + ".ca.ctx", B, H, dtype=ddt), self._buf(key + ".ca.lse", B, h, 1)
-            kk.call("kk_attn_fwd", q_n, k_n, v_n, ctx, lse, B, h, 1, T, q_n.stride(0), k_n.stride(0), v_n.stride(0), H, fm2, 0, 0.125,
-                    self.rng, 3, 0.0, self.math, _b16(q_n))
+            self._attn_launch("kk_attn_fwd", _AttnOps(q_n, kv_n, kv_n[:, H:], ctx, lse), B, h, 1, T, fm2, False, 3, 0.0)
             return ctx
 
         return self._decoder_step(ns, B, pe_row, 1, cos_row, sin_row, 1, 0, self_attn, cross_attn)
